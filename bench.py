@@ -12,16 +12,22 @@ sharded as contiguous ranges of 65 536 / N voices per GPU, no data-path collecti
 per GPU instead; at N > 1 the weak figure is also measured (outside the timed region) and reported as
 `config.scaling_alt`.  `--mix` adds the on-device stereo mix-down + one RCCL all-reduce of [2][frames] per step.
 
-Prints ONE JSON line on rank 0 (contract in the round brief) with `roofline`, `cpu_baseline` and -- at N = 1, measured
-after the timed region -- a `secondary` list: the tolerance mode of the same workload, and BASELINE configs 2, 4, 5.
+Prints ONE JSON line on rank 0 (contract in the round brief) with `ms_per_step`, `roofline` and `cpu_baseline`.  At N = 1 the
+`secondary` list, measured after the timed region (the tolerance mode of the same workload, BASELINE configs 2, 4, 5, the
+reference's criterion benches), goes to stderr as a JSON line of its own.  `--dump-outputs DIR` writes what the last timed
+step computed; the timed steps start from the bank's initial state, so runs with the same arguments compute the same samples.
 """
 import argparse
+import atexit
 import ctypes
 import ctypes as C
+import functools
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 
@@ -38,13 +44,28 @@ TOTAL_VOICES = 65536   # BASELINE.json: "65536-voice SVF+FM graph"
 NATIVE_FLAGS = "-O3 -march=native -ffp-contract=off -fno-fast-math"
 
 
+@functools.lru_cache(maxsize=None)
+def _host_build_dir():
+    """A private directory, removed at exit, for what this script compiles for THIS host while it runs (the -march=native oracle,
+    tools/launch_overhead.cpp): the checkout may be read-only to whoever runs the benchmark."""
+    d = tempfile.mkdtemp(prefix="fundsp_bench_")
+    atexit.register(shutil.rmtree, d, True)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def _native_oracle_so():
+    """Path of the -O3 -march=native build of oracle/ made on THIS host (oracle/Makefile `native`), once per process."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "native", "NATIVE_DIR=" + _host_build_dir()])
+    return os.path.join(_host_build_dir(), "libfundsp_oracle_native.so")
+
+
 def _native_oracle():
     """(oracle module, ctypes handle of the -O3 -march=native build of oracle/ made on THIS host)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle as O
 
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "native"])
-    L = C.CDLL(os.path.join(ROOT, "oracle", "_native", "libfundsp_oracle_native.so"))
+    L = C.CDLL(_native_oracle_so())
     L.o_bank_render.restype = C.c_double
     L.o_bank_render.argtypes = [C.POINTER(O.BankJob), C.POINTER(C.c_float)]
     L.o_fast_simd_flavour.restype = C.c_char_p
@@ -483,7 +504,7 @@ def secondary(F, W, torch, sr, mode):
     # ... the same launch pattern from a COMPILED host, straight through the C ABI (tools/launch_overhead.cpp, built here with g++):
     # what the Python binding adds per 64-frame block is the difference to T64.us_per_launch above
     try:
-        exe = os.path.join(ROOT, "tools", "_launch_overhead")
+        exe = os.path.join(_host_build_dir(), "launch_overhead")
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "launch_overhead.cpp"), "-o", exe,
                                "-L", os.path.join(ROOT, "fundsp_amd"), "-lfundsp_hip", "-Wl,-rpath," + os.path.join(ROOT, "fundsp_amd"),
                                "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"],
@@ -743,8 +764,7 @@ def _oracle_on_native_build():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle as O
 
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "native"])
-    native = os.path.join(ROOT, "oracle", "_native", "libfundsp_oracle_native.so")
+    native = _native_oracle_so()
     if getattr(O, "_native_path", None) != native:
         O._lib = None
         O.build = lambda: native
@@ -896,6 +916,15 @@ class quiet_stdout:
         return False
 
 
+def print_result(res):
+    """The result line: the LAST line on stdout, one JSON object, read whole by whoever runs the benchmark.  The secondary
+    measurements (N = 1: some 20 KB of JSON, which made the line too long to be read) go to stderr, one JSON line of their own."""
+    secondary = res.pop("secondary", None)
+    if secondary is not None:
+        print(json.dumps({"secondary": secondary}), file=sys.stderr, flush=True)
+    print(json.dumps(res), flush=True)
+
+
 class Peers:
     """How the ranks of one bench run meet: barrier, max-over-ranks, and the mix-down communicator.
 
@@ -958,7 +987,16 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="wall-time budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--criterion", action="store_true", help="only the reference's own criterion benches (benches/benchmark.rs) as banks: one JSON line {\"criterion\": ..}")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs 2 / 4 / 5, tolerance mode)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32; at most 64 MB in all: a fixed, seeded "
+                         "sample of whole voices when an output is larger) -- out = the voice-out buffer, mix = the stereo mix-down of --mix; "
+                         "<name>.rank<r>.npy per rank at N > 1")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.criterion:
+        ap.error("--dump-outputs writes the timed path's outputs; --criterion has no timed path")
+    return args
 
 
 def launch_plan(args, env, device_count):
@@ -1021,7 +1059,7 @@ def main(argv=None):
         with quiet_stdout():
             if comm is not None:
                 comm.close()
-        print(json.dumps(results[0]), flush=True)
+        print_result(results[0])
         return
     if plan == "torchrun-rank":
         import torch.distributed as dist
@@ -1043,7 +1081,7 @@ def main(argv=None):
         with quiet_stdout():
             res = run_rank(args, torch, F, Peers(world, rank, dist=dist, comm=comm), local_rank)
         if rank == 0:
-            print(json.dumps(res), flush=True)
+            print_result(res)
         dist.barrier()
         if comm is not None:
             comm.close()
@@ -1055,7 +1093,7 @@ def main(argv=None):
         res = run_rank(args, torch, F, Peers(1, 0, comm=comm), 0)
         if comm is not None:
             comm.close()
-    print(json.dumps(res), flush=True)
+    print_result(res)
 
 
 HEADLINE_KERNEL_SOURCES = ("fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_engine.hpp", "fd_opts.hpp", "fd_kinds_fm.hpp", "fd_kinds_fm.hip")
@@ -1110,6 +1148,36 @@ def mix_step(F, torch, args, wl, peers, mode):
         mix = F.sum_voices(wl["out"])  # voices are already panned to stereo
     peers.comm.allreduce(mix, slot=peers.slot)
     return mix
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: data of all the files together (under 64 MB with their headers)
+
+
+def dump_sample(outputs, limit, seed=0):
+    """{name: (parts, axis)} of device tensors -> {name: tensor} within `limit` bytes in all.  An output that fits its share of the
+    limit is copied whole; a larger one is cut to whole slices along `axis` (the voices of a voice-out buffer, the frames of a mix),
+    the same seeded choice of slices in every run.  The parts of one output (the launches of a note) are joined along dim 1 (frames)."""
+    import numpy as np
+    import torch
+
+    def nbytes(parts):
+        return sum(p.numel() * p.element_size() for p in parts)
+
+    got, left = {}, limit
+    items = sorted(outputs.items(), key=lambda kv: nbytes(kv[1][0]))   # the small ones whole first, the rest of the limit to the big one
+    for i, (name, (parts, axis)) in enumerate(items):
+        share, size, n = left // (len(items) - i), nbytes(parts), parts[0].shape[axis]
+        if size > share:
+            k = share * n // size
+            if k < 1:
+                raise SystemExit(f"--dump-outputs: one slice of '{name}' along dim {axis} is larger than its {share}-byte share")
+            idx = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(n, k, replace=False))).to(parts[0].device)
+            parts = [p.index_select(axis, idx) for p in parts]
+        else:
+            parts = [p.clone() for p in parts]
+        got[name] = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        left -= nbytes([got[name]])
+    return got
 
 
 class PowerMeter:
@@ -1183,6 +1251,8 @@ class PowerMeter:
 def run_rank(args, torch, F, peers, device):
     """One rank's share of the run (a process under torch.distributed.run, or a host thread of a one-process run).
     Returns the result record on rank 0, None elsewhere."""
+    import numpy as np
+
     from fundsp_amd import dist as fdist
     from fundsp_amd import workloads as W
 
@@ -1198,8 +1268,9 @@ def run_rank(args, torch, F, peers, device):
         peers.barrier()
         torch.cuda.synchronize()
 
-    def timed_run(scaling, steps, warmup):
-        """K steps of the rank's shard between two fences; returns (max-over-ranks seconds, kernel ms list, workload, V)."""
+    def timed_run(scaling, steps, warmup, dump=False):
+        """K steps of the rank's shard between two fences; returns (max-over-ranks seconds, kernel ms list, workload, V).
+        dump: wl["dump"] = the outputs of the last timed step (dump_sample)."""
         if scaling == "strong":
             first, V = fdist.shard_range(base_voices, rank, world)   # contiguous ranges of the whole-node bank
         else:
@@ -1253,6 +1324,9 @@ def run_rank(args, torch, F, peers, device):
             step()
             torch.cuda.synchronize()
             window_steps += 1
+        # the spin-up's step count depends on the clock: back to the bank's initial state, so that the W + K steps that follow compute
+        # the same samples in every run with the same arguments (--dump-outputs compares builds on them)
+        bank.reset()
         for _ in range(warmup):
             step()
         fence()
@@ -1282,6 +1356,16 @@ def run_rank(args, torch, F, peers, device):
             peers.comm.wait(peers.slot)   # the last all-reduce belongs to the timed region
         fence()
         elapsed = peers.max(time.perf_counter() - t0, torch)
+        if dump:   # what the caller of the path holds after the last timed step, before the steps below overwrite it
+            outputs = {}
+            if wl.get("outs") is not None:   # the note's launches, [n_out][n][V] each
+                outputs["out"] = (wl["outs"], 2)
+            elif wl["out"] is not None:
+                outputs["out"] = ([wl["out"]], 2 if wl["layout"] == F.LAYOUT_VOICE_MINOR else 0)
+            if args.mix:
+                outputs["mix"] = ([mixes[-1]], 1)
+            wl["dump"] = dump_sample(outputs, DUMP_BYTES // world)
+            torch.cuda.synchronize()   # (the copies to the host run on another stream)
         if pairs is not None:
             kernel_ms = [a.elapsed_time(b) for a, b in pairs]
         if plan is not None:   # the kernels' own HIP-event times: three more steps of the same work, waiting for every launch
@@ -1299,7 +1383,11 @@ def run_rank(args, torch, F, peers, device):
     # default one (the default stream's handle is 0 = "the bank's own stream"), and the event pairs around the launches must sit on it too
     run_stream = torch.cuda.Stream()
     with torch.cuda.stream(run_stream):
-        elapsed, kernel_ms, wl, V = timed_run(args.scaling, args.steps, args.warmup)
+        elapsed, kernel_ms, wl, V = timed_run(args.scaling, args.steps, args.warmup, dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, x in wl.pop("dump").items():
+            np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if distributed else "") + ".npy"), x.float().cpu().numpy())
     total_voices = base_voices if args.scaling == "strong" else base_voices * world
     scaling_alt = None
     if distributed and args.config == 3:   # the other scaling law, outside the timed region, a few steps

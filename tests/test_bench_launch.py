@@ -117,6 +117,14 @@ def test_secondary_cpu_baselines_are_the_native_monomorphised_legs():
         assert r["scalar_voice_value" if cfg == 2 else "tree_walk_value"] > 0
 
 
+def test_host_builds_of_the_bench_stay_out_of_the_checkout():
+    """The -march=native oracle is compiled while the benchmark runs, by a user who may not be allowed to write into the checkout: it goes
+    to a private directory of the process, not under oracle/."""
+    so = bench._native_oracle_so()
+    assert os.path.exists(so) and not os.path.abspath(so).startswith(ROOT + os.sep)
+    assert os.path.dirname(so) == bench._host_build_dir() and bench._native_oracle_so() == so
+
+
 def test_pmc_latest_is_quoted_only_for_the_kernel_it_was_counted_on():
     """bench.py quotes profiles/pmc_latest.json as roofline.traffic only when the record carries the hash of the sources the headline
     kernel is compiled from in THIS tree (the file silently went stale whenever the kernel changed)."""
@@ -125,3 +133,39 @@ def test_pmc_latest_is_quoted_only_for_the_kernel_it_was_counted_on():
     rec = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
     assert len(bench.headline_kernel_source_hash()) == 64
     assert "k_render_pipe" in rec["kernel"] and len(rec.get("kernel_source_sha256", "")) == 64
+
+
+def test_result_line_is_the_last_stdout_line_and_carries_no_secondary_list(capsys):
+    """The result line is read whole by whoever runs the benchmark: the N = 1 secondary list (some 20 KB) goes to stderr."""
+    import json
+
+    bench.print_result({"value": 1.0, "ms_per_step": 5.0, "secondary": [{"name": "config2", "what": "x" * 30000}]})
+    out, err = capsys.readouterr()
+    assert out.count("\n") == 1 and json.loads(out) == {"value": 1.0, "ms_per_step": 5.0}
+    assert json.loads(err)["secondary"][0]["name"] == "config2"
+
+
+def test_steps_and_warmup_are_checked():
+    assert bench.parse_args(["--steps", "7", "--warmup", "0"]).steps == 7
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--dump-outputs", "d", "--criterion"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+
+
+def test_dump_sample_is_bounded_seeded_and_joins_the_launches_of_a_note():
+    """--dump-outputs: whole outputs when they fit, else the same seeded voices in every run; the total stays within the limit."""
+    import torch
+
+    out = torch.arange(1 * 480 * 1000, dtype=torch.float32).reshape(1, 480, 1000)   # [n_out][frames][voices]
+    mix = torch.ones(2, 480)
+    a = bench.dump_sample({"out": ([out], 2), "mix": ([mix], 1)}, 200_000)
+    b = bench.dump_sample({"out": ([out[:, :240], out[:, 240:]], 2), "mix": ([mix], 1)}, 200_000)   # the same frames in two launches
+    assert torch.equal(a["mix"], mix) and a["out"].shape[:2] == (1, 480) and 0 < a["out"].shape[2] < 1000
+    assert sum(x.numel() * 4 for x in a.values()) <= 200_000
+    assert torch.equal(a["out"], b["out"])
+    voices = a["out"][0, 0].long()                                             # out[0, 0, v] == v: the voices taken, in order
+    assert torch.equal(a["out"], out[:, :, voices]) and bool((voices[1:] > voices[:-1]).all())
+    small = bench.dump_sample({"out": ([out], 2)}, out.numel() * 4)
+    assert torch.equal(small["out"], out) and small["out"].data_ptr() != out.data_ptr()   # a copy: later steps overwrite the buffer
+    with pytest.raises(SystemExit):
+        bench.dump_sample({"out": ([out], 2)}, 1000)                           # one voice (480 frames) does not fit
