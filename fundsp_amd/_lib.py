@@ -22,6 +22,16 @@ DEFAULT_SR = 44100.0
 # every symbol include/fundsp_hip.h declares: name -> (restype, argtypes)
 _P, _i, _f, _d, _sz, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint64
 _fp, _u64p, _cs = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_char_p
+FDN_FILTER_NONE, FDN_FILTER_LOWPOLE, FDN_FILTER_SVF = 0, 1, 2   # fdsp_fdn_network::filter
+FDN_IN_LINE, FDN_IN_LOOP = 0, 1                                 # fdsp_fdn_network::place: fdn(x >> F) | fdn2(x, F)
+
+
+class FdnNetwork(C.Structure):
+    """struct fdsp_fdn_network (include/fundsp_hip.h)"""
+    _fields_ = [("lines", _i), ("inputs", _i), ("outputs", _i), ("taps", _i), ("filter", _i), ("svf_mode", _i), ("place", _i),
+                ("per_instance", _i), ("delays", C.POINTER(_d)), ("weights", _fp), ("cutoff", _fp), ("q", _fp), ("gain", _fp), ("line_gain", _fp)]
+
+
 SYMBOLS = {
     "fdsp_last_error": (_cs, []),
     "fdsp_kind_count": (_i, []),
@@ -51,6 +61,8 @@ SYMBOLS = {
     "fdsp_reverb3_stereo_svf_create_on": (_i, [_i, _sz, _d, _d, _i, _f, _f, _f, C.POINTER(_P)]),
     "fdsp_fdn_create": (_i, [_sz, _i, C.POINTER(_d), _i, C.POINTER(C.c_float), _i, _i, C.POINTER(_P)]),
     "fdsp_fdn_create_on": (_i, [_i, _sz, _i, C.POINTER(_d), _i, C.POINTER(C.c_float), _i, _i, C.POINTER(_P)]),
+    "fdsp_fdn_network_create": (_i, [_sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
+    "fdsp_fdn_network_create_on": (_i, [_i, _sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
     "fdsp_bank_set_bus": (_i, [_P, _i, _f, _f]),
     "fdsp_bank_get_bus": (_i, [_P, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f)]),
     "fdsp_jit_compiler": (C.c_char_p, []),

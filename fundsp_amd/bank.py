@@ -88,6 +88,14 @@ class Bank:
                     b.set_sample_rate(sample_rate)
                 b.reset()
                 return b
+        nplan = G.fdn_network_plan(graph, voices) if fdn_kernel and plan is None else None
+        if nplan is not None:
+            # a filter in the lines or the loop (fdn2), per-line weights, per-voice parameters: the filtered lane-per-frame kernel
+            rates = {_lib.DEFAULT_SR, float(sample_rate or _lib.DEFAULT_SR)}
+            if all(int(np.floor(float(np.min(nplan["delays"])) * r + 0.5)) >= 128 for r in rates):
+                b = cls.fdn_network(voices, **nplan, sample_rate=sample_rate)
+                b.reset()
+                return b
         bus = G.bus_plan(graph) if fdn_kernel else None
         if bus is not None and G.lane_per_frame_shape(bus[0]):
             # `multipass() & 0.2 * reverb_stereo(..)` (README.md:436) and its relatives: the reverb's own bank with the gain and the dry bus folded into
@@ -107,7 +115,7 @@ class Bank:
             # flushes denormals when the network has a Feedback node, as the one graph would), 200-700 x faster
             eff = cls.from_graph(parts[1], voices, sample_rate=sample_rate)
             if isinstance(eff, Bank) and eff.kind in LANE_PER_FRAME_KINDS:
-                src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, flush_denormals=flush_denormals or "Feedback<" in parts[1].type)
+                src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, flush_denormals=flush_denormals or "Feedback<" in parts[1].type or "Feedback2<" in parts[1].type)
                 return Chain(src, eff, construction_hash=probe_hash(graph))
             eff.close()
         name, ctype, csrc = graph.kind_name(), graph.type, graph.source
@@ -185,6 +193,55 @@ class Bank:
         w = (C.c_float * int(taps))(*[float(x) for x in weights])
         check(lib().fdsp_fdn_create_on(int(device), int(instances), int(lines), d, int(taps), w, int(inputs), int(outputs), C.byref(h)))
         return cls("fdn", instances, _handle=h)
+
+    @classmethod
+    def fdn_network(cls, instances, lines, delays, weights=None, filter=None, place="line", cutoff=None, q=1.0, gain=1.0, line_gain=None,
+                    inputs=1, outputs=1, sample_rate=None, device=-1):
+        """Bank of `instances` x a Hadamard feedback delay network with a filter in its lines or its loop (fdsp_fdn_network_create):
+
+            place="line":  split / multisplit >> fdn(stacki(|i| delay(delays[i]) [>> fir(weights[i])] [>> F_i] [* line_gain[i]])) >> join / multijoin
+            place="loop":  split / multisplit >> fdn2(stacki(|i| delay(delays[i]) [>> fir(weights[i])]), stacki(|i| F_i [* line_gain[i]])) >> ..
+
+        `filter`: None, "lowpole" (lowpole_hz(cutoff[i])) or a FixedSvf mode "lowpass" .. "highshelf" (at cutoff[i], q[i], gain[i]).  `delays`,
+        `cutoff`, `q`, `gain`, `line_gain` are scalars, [lines] or [instances, lines] arrays; `weights` is None (no Fir node), [taps] (every line),
+        [lines, taps] or [instances, lines, taps].  Any [instances, ..] array makes the parameters per instance.  The bank is created at
+        `sample_rate` (default DEFAULT_SR), where every delay must be at least 128 samples."""
+        V, N = int(instances), int(lines)
+        w = None if weights is None else np.asarray(weights, dtype=np.float32)
+        taps = 0 if w is None else int(w.shape[-1])
+        if w is not None and w.ndim == 1:
+            w = np.broadcast_to(w, (N, taps))
+        arrs = dict(delays=np.asarray(delays, dtype=np.float64))
+        if filter is not None:
+            if cutoff is None:
+                raise ValueError("fdn_network: a filter needs its cutoff")
+            arrs["cutoff"] = np.asarray(cutoff, dtype=np.float32)
+            if filter != "lowpole":
+                arrs["q"] = np.asarray(q, dtype=np.float32)
+                arrs["gain"] = np.asarray(gain, dtype=np.float32)
+        if line_gain is not None:
+            arrs["line_gain"] = np.asarray(line_gain, dtype=np.float32)
+        per = any(a.ndim == 2 for a in arrs.values()) or (w is not None and w.ndim == 3)
+        shape = (V, N) if per else (N,)
+        arrs = {k: np.ascontiguousarray(np.broadcast_to(a, shape), dtype=a.dtype) for k, a in arrs.items()}
+        if w is not None:
+            w = np.ascontiguousarray(np.broadcast_to(w, shape + (taps,)), dtype=np.float32)
+        net = _lib.FdnNetwork()
+        net.lines, net.inputs, net.outputs, net.taps = N, int(inputs), int(outputs), taps
+        net.filter = _lib.FDN_FILTER_NONE if filter is None else _lib.FDN_FILTER_LOWPOLE if filter == "lowpole" else _lib.FDN_FILTER_SVF
+        net.svf_mode = 0 if filter in (None, "lowpole") else int(SVF_MODES[filter] if isinstance(filter, str) else filter)
+        net.place = {"line": _lib.FDN_IN_LINE, "loop": _lib.FDN_IN_LOOP}[place]
+        net.per_instance = 1 if per else 0
+        net.delays = arrs["delays"].ctypes.data_as(C.POINTER(C.c_double))
+        net.weights = _fptr(w) if w is not None else None
+        for k in ("cutoff", "q", "gain", "line_gain"):
+            setattr(net, k, _fptr(arrs[k]) if k in arrs else None)
+        h = C.c_void_p()
+        sr = float(sample_rate) if sample_rate is not None else _lib.DEFAULT_SR
+        check(lib().fdsp_fdn_network_create_on(int(device), V, C.byref(net), sr, C.byref(h)))
+        b = cls("fdn_network", V, _handle=h)
+        b.sample_rate = sr
+        return b
 
     def clone(self):
         """AudioNode: Clone -- a new bank that continues exactly where this one stands (fdsp_bank_clone: slots, rings, sample
@@ -460,7 +517,7 @@ class Bank:
 
 
 PIPE_ID = 6   # Pipe::ID (audionode.rs:1375-1492; fd_nodes.hpp)
-LANE_PER_FRAME_KINDS = ("reverb_stereo", "reverb4_stereo", "reverb3_stereo", "fdn")
+LANE_PER_FRAME_KINDS = ("reverb_stereo", "reverb4_stereo", "reverb3_stereo", "fdn", "fdn_network")
 
 # A one-slot node whose constructor stores what `G::ping(true, AttoHash::new(G::ID))` returns -- the hash a combinator's constructor hands
 # down to its nodes (audionode.rs:871-876, 1389-1394) -- so that the host can read it: the probe walks the TYPE only, no node state.

@@ -15,6 +15,7 @@
 #include "fd_engine.hpp"
 #include "fd_fdn.hpp"
 #include "fd_reverb3.hpp"
+#include "fd_fdnx.hpp"
 #include "fd_opts.hpp"
 
 namespace {
@@ -389,7 +390,8 @@ int build_default_table_set(int set) {
 
 struct FdnBank {  // reverb_stereo / reverb4_stereo banks (fd_fdn.hip): rings + per-line state instead of the slot SoA
     int kind = 0;  // 0 = reverb_stereo(room, time, damping), 1 = reverb4_stereo(room, time), 2 = the generic network (fdsp_fdn_create: desc),
-                   // 3 = reverb3_stereo(time, diffusion = `damping`, lowpole_hz(cutoff)): the allpass loop of fd_reverb3.hip (c3 / st3; `c` only carries nin / nout)
+                   // 3 = reverb3_stereo(time, diffusion = `damping`, lowpole_hz(cutoff)): the allpass loop of fd_reverb3.hip (c3 / st3; `c` only carries nin / nout),
+                   // 4 = a filtered / per-instance network (fdsp_fdn_network_create: xdesc, cx / sx / xtab of fd_fdnx.hip; `c` only carries nin / nout)
     double room = 0.0, time = 0.0, damping = 0.0;
     fd::Rv3Filter flt;      // kind 3: the loop filter
     fd::Rv3Const c3;
@@ -397,6 +399,10 @@ struct FdnBank {  // reverb_stereo / reverb4_stereo banks (fd_fdn.hip): rings + 
     fd::FdnDesc desc;
     fd::FdnConst c;
     fd::FdnState st;
+    fd::FdnxDesc xdesc;
+    fd::FdnxConst cx{};
+    fd::FdnxState sx{};
+    fd::FdnxInst* xtab = nullptr;   // kind 4: the parameter table at the bank's rate (one entry, or one per instance)
     fd::FdnBus bus;           // fdsp_bank_set_bus: wet * node [& dry * multipass()] folded into the render kernels' epilogue
     float* stage = nullptr;   // planar staging of voice-minor launches: [V][inputs][frames] | [V][outputs][frames] (fd_fdn.hip "voice-minor I/O")
     size_t stage_n = 0;
@@ -992,6 +998,10 @@ static void fdn_free(FdnBank* f) {
     if (f->st3.wpos) hipFree(f->st3.wpos);
     f->st3.rings = nullptr;   // (pre, wpre, fval outlive a re-configuration: rv3_free_persistent)
     f->st3.wpos = nullptr;
+    for (void* p : {(void*)f->sx.rings, (void*)f->sx.wpos, (void*)f->sx.v1, (void*)f->sx.v2, (void*)f->sx.fb, (void*)f->sx.s1, (void*)f->sx.s2, (void*)f->xtab})
+        if (p) hipFree(p);
+    f->sx = fd::FdnxState{};
+    f->xtab = nullptr;
 }
 static void rv3_free_persistent(FdnBank* f) {
     if (f->st3.pre) hipFree(f->st3.pre);
@@ -1041,6 +1051,53 @@ static int rv3_configure(fdsp_bank* b, double sr) {
     HIPCHK(hipGetLastError());
     return FDSP_OK;
 }
+// filtered / per-instance networks: the table and the lines for a sample rate.  Transactional like fdn_configure: the new rings start empty
+// (Delay::set_sample_rate, delay.rs:105-113), the coefficients follow the rate (filter.rs:58-61, svf.rs:989-992), and the Fir carry, the
+// filter states and the feedback value stay (fir.rs:52-54, feedback.rs:125-127, 254-257)
+static int fdnx_configure(fdsp_bank* b, double sr) {
+    FdnBank* f = b->fdn;
+    std::vector<fd::FdnxInst> tab;
+    fd::FdnxConst c;
+    const int shortest = fd::fdnx_make_table(f->xdesc, b->V, sr, tab, &c);
+    if (shortest < 0) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
+    if (shortest < 128)
+        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+    const size_t n = b->V;
+    fd::FdnxState st{};
+    fd::FdnxInst* dtab = nullptr;
+    hipError_t e = hipMalloc((void**)&st.rings, n * c.ring_stride * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&st.wpos, n * sizeof(int));
+    for (float** p : {&st.v1, &st.v2, &st.fb, &st.s1, &st.s2})
+        if (e == hipSuccess) e = hipMalloc((void**)p, n * 32 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dtab, tab.size() * sizeof(fd::FdnxInst));
+    if (e == hipSuccess) e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(fd::FdnxInst), hipMemcpyHostToDevice, b->stream);
+    if (e != hipSuccess) {
+        FdnBank tmp;
+        tmp.sx = st;
+        tmp.xtab = dtab;
+        fdn_free(&tmp);
+        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("fdsp_fdn_network_create buffers: ") + hipGetErrorString(e));
+    }
+    c.tab = dtab;
+    fd::fdnx_launch_reset(c, st, n, b->stream);
+    if (f->sx.v1) {
+        hipMemcpyAsync(st.v1, f->sx.v1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+        hipMemcpyAsync(st.v2, f->sx.v2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+        hipMemcpyAsync(st.fb, f->sx.fb, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+        hipMemcpyAsync(st.s1, f->sx.s1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+        hipMemcpyAsync(st.s2, f->sx.s2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+    }
+    hipStreamSynchronize(b->stream);
+    fdn_free(f);  // the old buffers
+    f->cx = c;
+    f->sx = st;
+    f->xtab = dtab;
+    f->c.nin = f->xdesc.nin;
+    f->c.nout = f->xdesc.nout;
+    b->sr = sr;
+    HIPCHK(hipGetLastError());
+    return FDSP_OK;
+}
 static void fdn_free_stage(FdnBank* f) {
     if (f && f->stage) hipFree(f->stage);
     if (f) { f->stage = nullptr; f->stage_n = 0; }
@@ -1053,6 +1110,7 @@ static void fdn_free_stage(FdnBank* f) {
 static int fdn_configure(fdsp_bank* b, double sr) {
     FdnBank* f = b->fdn;
     if (f->kind == 3) return rv3_configure(b, sr);
+    if (f->kind == 4) return fdnx_configure(b, sr);
     fd::FdnConst c;
     if (f->kind == 2) fd::fdn_make_const_generic(f->desc, sr, &c);
     else if (f->kind == 1) fd::fdn_make_const_reverb4(f->room, f->time, sr, &c);
@@ -1099,7 +1157,7 @@ int fdsp_reverb_stereo_create(size_t instances, double room_size, double time, d
 }
 
 static int fdn_bank_create_on(int kind, int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out, const fd::FdnDesc* desc = nullptr,
-                              const fd::Rv3Filter* flt = nullptr);
+                              const fd::Rv3Filter* flt = nullptr, const fd::FdnxDesc* xdesc = nullptr, double sample_rate = FDSP_DEFAULT_SR);
 int fdsp_reverb_stereo_create_on(int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out) {
     return fdn_bank_create_on(0, device, instances, room_size, time, damping, out);
 }
@@ -1131,6 +1189,51 @@ int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* de
 int fdsp_fdn_create(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out) {
     return fdsp_fdn_create_on(-1, instances, lines, delays, taps, weights, inputs, outputs, out);
 }
+int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
+    if (out) *out = nullptr;
+    if (!net) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: network NULL");
+    const int N = net->lines;
+    if (N != 2 && N != 4 && N != 8 && N != 16 && N != 32) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: lines takes 2, 4, 8, 16 or 32 (FrameHadamard needs a power of two; the kernel holds at most 32 lines in registers)");
+    if (net->taps < 0 || net->taps > 3) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: taps takes 0 (no Fir node) .. 3");
+    if ((net->inputs != 1 && net->inputs != 2) || (net->outputs != 1 && net->outputs != 2))
+        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: inputs / outputs take 1 (split / join) or 2 (multisplit::<U2, _> / multijoin::<U2, _>)");
+    if (net->filter < FDSP_FDN_FILTER_NONE || net->filter > FDSP_FDN_FILTER_SVF) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: filter takes FDSP_FDN_FILTER_NONE, _LOWPOLE or _SVF");
+    if (net->filter == FDSP_FDN_FILTER_SVF && (net->svf_mode < FDSP_SVF_LOWPASS || net->svf_mode > FDSP_SVF_HIGHSHELF))
+        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: svf_mode takes FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF");
+    if (net->place != FDSP_FDN_IN_LINE && net->place != FDSP_FDN_IN_LOOP) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: place takes FDSP_FDN_IN_LINE (fdn) or FDSP_FDN_IN_LOOP (fdn2)");
+    if (net->place == FDSP_FDN_IN_LOOP && net->filter == FDSP_FDN_FILTER_NONE) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the loop form (fdn2) needs a filter");
+    if (!net->delays) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays NULL");
+    if (net->taps > 0 && !net->weights) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: weights NULL");
+    const bool shelf = net->filter == FDSP_FDN_FILTER_SVF && net->svf_mode >= FDSP_SVF_BELL;
+    if (net->filter != FDSP_FDN_FILTER_NONE && !net->cutoff) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the filter's cutoff is missing");
+    if (net->filter == FDSP_FDN_FILTER_SVF && !net->q) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the FixedSvf's q is missing");
+    if (shelf && !net->gain) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: bell / lowshelf / highshelf need a gain");
+    if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: sample_rate must be positive");
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: no instances");
+    fd::FdnxDesc d;
+    d.lines = N;
+    d.taps = net->taps;
+    d.nin = net->inputs;
+    d.nout = net->outputs;
+    d.filter = net->filter;
+    d.svf_mode = net->svf_mode;
+    d.place = net->place;
+    d.per_instance = net->per_instance ? 1 : 0;
+    d.has_gain = net->line_gain ? 1 : 0;
+    const size_t P = d.per_instance ? instances : 1, M = P * (size_t)N;
+    d.delay.assign(net->delays, net->delays + M);
+    for (double t : d.delay)
+        if (!(t >= 0.0) || !(t < 1e6)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+    if (net->taps > 0) d.w.assign(net->weights, net->weights + M * net->taps);
+    if (net->filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net->cutoff, net->cutoff + M);
+    if (net->filter == FDSP_FDN_FILTER_SVF) d.q.assign(net->q, net->q + M);
+    if (shelf) d.gain.assign(net->gain, net->gain + M);
+    if (d.has_gain) d.line_gain.assign(net->line_gain, net->line_gain + M);
+    return fdn_bank_create_on(4, device, instances, 1.0, 1.0, 0.0, out, nullptr, nullptr, &d, sample_rate);
+}
+int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
+    return fdsp_fdn_network_create_on(-1, instances, net, sample_rate, out);
+}
 static int rv3_create(int device, size_t instances, double time, double diffusion, const fd::Rv3Filter& flt, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (!(time > 0.0) || !(diffusion >= 0.0 && diffusion <= 1.0) || !(flt.cutoff > 0.0f))
@@ -1160,7 +1263,7 @@ int fdsp_reverb3_stereo_svf_create(size_t instances, double time, double diffusi
 }
 
 static int fdn_bank_create_on(int kind, int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out, const fd::FdnDesc* desc,
-                              const fd::Rv3Filter* flt) {
+                              const fd::Rv3Filter* flt, const fd::FdnxDesc* xdesc, double sample_rate) {
     if (!out) return fail(FDSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (instances == 0 || !(room_size > 0.0) || !(time > 0.0)) return fail(FDSP_EINVAL, "bad reverb_stereo / reverb4_stereo arguments");
@@ -1179,6 +1282,7 @@ static int fdn_bank_create_on(int kind, int device, size_t instances, double roo
     b->fdn->damping = damping;
     if (desc) b->fdn->desc = *desc;
     if (flt) b->fdn->flt = *flt;
+    if (xdesc) b->fdn->xdesc = *xdesc;
     b->fdn->st = fd::FdnState{};
     b->ops = nullptr;
     b->V = instances;
@@ -1192,7 +1296,7 @@ static int fdn_bank_create_on(int kind, int device, size_t instances, double roo
         fdsp_bank_destroy(b);
         return fail(FDSP_EDEVICE, "stream/event creation failed");
     }
-    int rc = fdn_configure(b, b->sr);
+    int rc = fdn_configure(b, sample_rate);
     if (rc != FDSP_OK) {
         fdsp_bank_destroy(b);
         return rc;
@@ -1248,7 +1352,8 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     fdsp_bank* b = nullptr;
     int rc;
     if (src->fdn)
-        rc = fdn_bank_create_on(src->fdn->kind, src->device, src->V, src->fdn->room, src->fdn->time, src->fdn->damping, &b, &src->fdn->desc, &src->fdn->flt);
+        rc = fdn_bank_create_on(src->fdn->kind, src->device, src->V, src->fdn->room, src->fdn->time, src->fdn->damping, &b, &src->fdn->desc, &src->fdn->flt,
+                                &src->fdn->xdesc, src->fdn->kind == 4 ? src->sr : FDSP_DEFAULT_SR);
     else
         rc = fdsp_bank_create_on(src->device, src->ops->name.c_str(), src->V, src->ring_frames, &b);
     if (rc != FDSP_OK) return rc;
@@ -1276,6 +1381,13 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
             if (e == hipSuccess) e = hipMemcpyAsync(d3.wpre, a3.wpre, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(d3.fval, a3.fval, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
             if (e != hipSuccess) return bail(e, "reverb3 state");
+        } else if (src->fdn->kind == 4) {
+            const fd::FdnxState &a = src->fdn->sx, &d = b->fdn->sx;
+            e = hipMemcpyAsync(d.rings, a.rings, n * src->fdn->cx.ring_stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d.wpos, a.wpos, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
+            for (auto m : {&fd::FdnxState::v1, &fd::FdnxState::v2, &fd::FdnxState::fb, &fd::FdnxState::s1, &fd::FdnxState::s2})
+                if (e == hipSuccess) e = hipMemcpyAsync(d.*m, a.*m, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+            if (e != hipSuccess) return bail(e, "network state");
         } else {
         const fd::FdnState &a = src->fdn->st, &d = b->fdn->st;
         e = hipMemcpyAsync(d.rings, a.rings, n * src->fdn->c.ring_stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
@@ -1377,6 +1489,7 @@ int fdsp_bank_reset(fdsp_bank* b) {
     if (b->fdn) {
         HIPCHK(await_last_render(b));
         if (b->fdn->kind == 3) fd::rv3_launch_reset(b->fdn->c3, b->fdn->st3, b->V, b->stream);
+        else if (b->fdn->kind == 4) fd::fdnx_launch_reset(b->fdn->cx, b->fdn->sx, b->V, b->stream);
         else fd::fdn_launch_reset(b->fdn->c, b->fdn->st, b->V, b->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(sync_bank_stream(b));
@@ -1561,9 +1674,10 @@ int fdsp_bank_process(fdsp_bank* b, size_t frames, const float* d_in, float* d_o
         const int tick = mode == FDSP_MODE_TICK ? 1 : 0, nin = f->c.nin, nout = f->c.nout;
         // voice-minor buffers of banks with at least a tile of instances go through the planar staging copy (the lane = frame kernels read
         // 256-byte runs of it instead of gathering a line per frame); the staging buffer grows outside captures only, like the partial mixes
-        bool staged = layout == FDSP_LAYOUT_VOICE_MINOR && b->V >= 64 && (f->kind == 3 || f->c.generic || fd::tl_opts.fdn_kernel == 0 || f->c.sections == 2);
+        bool staged = layout == FDSP_LAYOUT_VOICE_MINOR && b->V >= 64 && (f->kind >= 3 || f->c.generic || fd::tl_opts.fdn_kernel == 0 || f->c.sections == 2);
         auto render = [&](const float* pi, float* po, size_t fs, int lay) {
             if (f->kind == 3) fd::rv3_launch_render(f->c3, f->st3, b->V, pi, po, frames, fs, lay, s, f->bus);   // (Reverb has no process override: one arithmetic)
+            else if (f->kind == 4) fd::fdnx_launch_render(f->cx, f->sx, b->V, pi, po, frames, fs, lay, tick, s, f->bus);
             else fd::fdn_launch_render(f->c, f->st, b->V, pi, po, frames, fs, lay, tick, s, f->bus);
         };
         const size_t need = b->V * (size_t)(nin + nout) * frames;

@@ -662,9 +662,154 @@ def fdn_plan(g):
     return dict(lines=n, delays=delays, taps=taps, weights=[float(x) for x in ws[0]], inputs=nin, outputs=nout)
 
 
+def fdn_network_plan(g, voices=None):
+    """The arguments of Bank.fdn_network (fdsp_fdn_network_create) when `g` is a Hadamard feedback delay network with a filter in its lines or
+    in its loop --
+
+        split(N) | multisplit(2, N/2)  >>  fdn(stacki(N, lambda i: delay(t_i) [>> fir(w_i..)] [>> F_i] [* g_i]))          >>  join(N) | multijoin(2, N/2)
+        split(N) | multisplit(2, N/2)  >>  fdn2(stacki(N, lambda i: delay(t_i) [>> fir(w_i..)]), stacki(N, lambda i: F_i [* g_i]))  >>  ..
+
+    with N in 2, 4, 8, 16, 32, F_i lowpole_hz(c_i) or one FixedSvf mode (lowpass_hz .. highshelf_hz) for all lines, FIR weights per line and
+    every parameter a scalar or a per-voice array of length `voices` -- else None.  (fdn_plan's uniform `delay >> fir(w)` network is one of
+    these too; Bank.from_graph takes fdn_plan's kernel for it.)"""
+    name, kids = _parse_type(g.type)
+    chain = []
+
+    def flat(n, path, out):  # a Pipe chain, left to right, with the parameter path of every element; `* g` as a ("*", path) element
+        if n[0] == "Pipe" and len(n[1]) == 2:
+            flat(n[1][0], path + (0,), out)
+            flat(n[1][1], path + (1,), out)
+        elif n[0] == "Unop" and len(n[1]) == 2 and n[1][1][0] == "UMulScalar":
+            flat(n[1][0], path + (0,), out)
+            out.append((("*", []), path))
+        else:
+            out.append((n, path))
+        return out
+
+    chain = flat((name, kids), (), [])
+    if len(chain) != 3:
+        return None
+    (sp, _), (fb, fpath), (jn, _) = chain
+    try:
+        if sp[0] == "Split":
+            nin, n_in = 1, int(sp[1][0][0])
+        elif sp[0] == "MultiSplit" and int(sp[1][0][0]) == 2:
+            nin, n_in = 2, 2 * int(sp[1][1][0])
+        else:
+            return None
+        if jn[0] == "Join":
+            nout, n_out = 1, int(jn[1][0][0])
+        elif jn[0] == "MultiJoin" and int(jn[1][0][0]) == 2:
+            nout, n_out = 2, 2 * int(jn[1][1][0])
+        else:
+            return None
+    except (IndexError, ValueError):
+        return None
+    loop = fb[0] == "Feedback2"
+    if fb[0] not in ("Feedback", "Feedback2") or fb[1][-1][0] != "FbHadamard":
+        return None
+    stacks = fb[1][:-1]
+    if any(st[0] != "MultiStack" for st in stacks):
+        return None
+    n = int(stacks[0][1][0][0])
+    if n not in (2, 4, 8, 16, 32) or n_in != n or n_out != n or any(int(st[1][0][0]) != n for st in stacks):
+        return None
+    # the elements of one line: x's (and y's) Pipe chain, with parameter paths relative to line i's
+    xs = flat(stacks[0][1][1], (), [])
+    ys = flat(stacks[1][1][1], (), []) if loop else []
+    kinds = [e[0][0] for e in xs]
+    if not kinds or kinds[0] != "Delay":
+        return None
+    taps, k = 0, 1
+    if k < len(kinds) and kinds[k] == "Fir":
+        try:
+            taps = int(xs[k][0][1][0][0])
+        except (IndexError, ValueError):
+            return None
+        if not 1 <= taps <= 3:
+            return None
+        k += 1
+    tail = xs[k:] if not loop else ys
+    if loop and k != len(xs):
+        return None           # fdn2's x: delay [>> fir] only
+    filt = None
+    if tail and (tail[0][0][0] == "FixedSvf" or (tail[0][0][0] == "OnePole" and [c[0] for c in tail[0][0][1]] == ["OP_LOWPOLE", "1"])):
+        filt = tail[0]
+        tail = tail[1:]
+    if loop and filt is None:
+        return None
+    gain = None
+    if tail and tail[0][0][0] == "*":
+        gain = tail[0]
+        tail = tail[1:]
+    if tail:
+        return None           # something else in the line
+    # parameters: one value per (side, line, path within the line, field)
+    vals = {}
+    for path, field, value, _u in g.params:
+        vals[(tuple(path), field)] = np.asarray(value)
+    lens = set()
+    used = 0
+
+    def col(side, path, field, dtype=np.float32):
+        nonlocal used
+        vs = []
+        for i in range(n):
+            key = (fpath + (side, i) + path, field)
+            if key not in vals:
+                raise KeyError(key)
+            v = vals[key]
+            if v.ndim > 1:
+                raise KeyError(key)
+            if v.ndim == 1:
+                lens.add(len(v))
+            vs.append(v)
+        used += n
+        if all(v.ndim == 0 for v in vs):
+            return np.array([float(np.float32(v)) for v in vs], dtype=dtype)
+        if len({len(v) for v in vs if v.ndim == 1}) > 1:
+            raise KeyError(field)   # per-voice arrays of different lengths
+        m = max(len(v) for v in vs if v.ndim == 1)
+        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float32).astype(dtype), (m,)) for v in vs], axis=1)   # [voices, lines]
+
+    out = dict(lines=n, inputs=nin, outputs=nout, place="loop" if loop else "line")
+    try:
+        out["delays"] = col(0, xs[0][1], "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
+        if taps:
+            ws = [col(0, xs[1][1], f"w[{j}]") for j in range(taps)]
+            out["weights"] = np.stack(ws, axis=-1)              # [lines, taps] | [voices, lines, taps]
+        side = 1 if loop else 0
+        if filt is not None:
+            ftype = filt[0][0]
+            out["cutoff"] = col(side, filt[1], "cutoff")
+            if ftype == "FixedSvf":
+                modes = col(side, filt[1], "mode")
+                if modes.ndim != 1 or len(set(modes.tolist())) != 1:
+                    return None   # the mode is a type parameter in Rust: one for the network
+                mode = int(modes[0])
+                inv = {v: k for k, v in SVF_MODES.items()}
+                if mode not in inv:
+                    return None
+                out["filter"] = inv[mode]
+                out["q"] = col(side, filt[1], "q")
+                out["gain"] = col(side, filt[1], "gain")
+            else:
+                out["filter"] = "lowpole"
+        if gain is not None:
+            out["line_gain"] = col(side, gain[1], "scalar")
+    except KeyError:
+        return None
+    if used != len(g.params):
+        return None           # something else carries parameters (builders on the nodes): not this shape
+    if len(lens) > 1 or (voices is not None and lens and lens != {int(voices)}):
+        return None           # per-voice arrays must have one value per voice
+    return out
+
+
 def lane_per_frame_shape(g):
     """whether `g` is one of the nodes / networks with a lane-per-frame kernel (what Bank.from_graph builds as an FDN / reverb bank)"""
-    return getattr(g, "stock_reverb", None) is not None or getattr(g, "reverb3_plan", None) is not None or fdn_plan(g) is not None
+    return (getattr(g, "stock_reverb", None) is not None or getattr(g, "reverb3_plan", None) is not None or fdn_plan(g) is not None
+            or fdn_network_plan(g) is not None)
 
 
 def bus_plan(g):

@@ -217,6 +217,34 @@ int fdsp_reverb4_stereo_create(size_t instances, double room_size, double time, 
  * rows as 256-byte runs: 8 * lines + 4 * (inputs + outputs) bytes per instance-frame), which needs every delay to exceed two blocks
  * (128 samples) at the bank's sample rate -- FDSP_EINVAL otherwise; such a graph still renders lane-per-voice through
  * fdsp_graph_compile.  Flushes f32 denormals like every graph with a Feedback node.  Handle semantics of the reverb banks. */
+/* Feedback delay networks beyond fdsp_fdn_create's shape: a recursive filter in every line or in the feedback loop, per-line FIR weights,
+ * and every parameter per line and, with per_instance = 1, per instance.  The two forms (N = lines: 2, 4, 8, 16 or 32):
+ *   FDSP_FDN_IN_LINE:  split | multisplit >> fdn(stacki(|i| delay(t_i) [>> fir(w_i)] [>> F_i] [* g_i])) >> join | multijoin
+ *                      -- the output and the feedback both see the filtered line (Feedback, src/feedback.rs:108-146);
+ *   FDSP_FDN_IN_LOOP:  split | multisplit >> fdn2(stacki(|i| delay(t_i) [>> fir(w_i)]), stacki(|i| F_i [* g_i])) >> join | multijoin
+ *                      -- the output is the line before F; the feedback is Hadamard(F(x) * g) (Feedback2, src/feedback.rs:181-330).
+ * F is lowpole_hz(cutoff_i) (FDSP_FDN_FILTER_LOWPOLE, src/filter.rs:19-66) or the FixedSvf of `svf_mode` at (cutoff_i, q_i, gain_i)
+ * (FDSP_FDN_FILTER_SVF, src/svf.rs:861-1031; gain is read by bell / lowshelf / highshelf only), or nothing (FDSP_FDN_FILTER_NONE, line
+ * form only).  taps = 0 means the line has no Fir node; line_gain = NULL that it has no `* g`.  Arrays are [lines] (per_instance = 0) or
+ * [instances][lines] (per_instance = 1); weights have `taps` entries per line, oldest tap first.  Coefficients are computed in f32 at
+ * the bank's rate.  The bank is created at `sample_rate`; every delay must be at least 128 samples there (two blocks: the lane-per-frame
+ * kernel's rule) -- FDSP_EINVAL otherwise, and at a later fdsp_bank_set_sample_rate.  A change of rate empties the delay lines and keeps
+ * the FIR carry, the filter states and the feedback value, like the reference.  Flushes f32 denormals.  Handle semantics of the reverb
+ * banks: process (both layouts, both modes), reset, clone, fdsp_bank_set_bus. */
+enum { FDSP_FDN_FILTER_NONE = 0, FDSP_FDN_FILTER_LOWPOLE = 1, FDSP_FDN_FILTER_SVF = 2 };
+enum { FDSP_FDN_IN_LINE = 0, FDSP_FDN_IN_LOOP = 1 };
+typedef struct fdsp_fdn_network {
+    int lines, inputs, outputs, taps;   /* taps 0 = no Fir node */
+    int filter;                         /* FDSP_FDN_FILTER_NONE | _LOWPOLE | _SVF */
+    int svf_mode;                       /* FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF */
+    int place;                          /* FDSP_FDN_IN_LINE (fdn) | FDSP_FDN_IN_LOOP (fdn2) */
+    int per_instance;                   /* 0: arrays are [lines]; 1: [instances][lines] */
+    const double* delays;               /* seconds */
+    const float* weights;               /* [..][lines][taps] */
+    const float *cutoff, *q, *gain;     /* filter parameters (NULL where the filter has none) */
+    const float* line_gain;             /* the `* g` behind the filter, NULL = no such node */
+} fdsp_fdn_network;
+int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out);
 /* reverb3_stereo(time, diffusion, lowpole_hz(cutoff)) (src/prelude.rs:1858-1871): the allpass-loop reverb Reverb<F> of src/reverb.rs:152-279
  * with the documented loop filter, a one-pole lowpass (src/filter.rs:19-66).  `instances` independent reverbs, 2 inputs / 2 outputs each, all
  * with the same parameters.  One wave per instance, one lane per FRAME of a 64-sample block: all 76 delay lines of the structure (4 input
@@ -268,6 +296,7 @@ int fdsp_reverb4_stereo_create_on(int device, size_t instances, double room_size
 int fdsp_reverb3_stereo_create_on(int device, size_t instances, double time, double diffusion, float lowpole_cutoff_hz, fdsp_bank** out);
 int fdsp_reverb3_stereo_svf_create_on(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff_hz, float q, float gain, fdsp_bank** out);
 int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out);
+int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out);
 int fdsp_bank_device(const fdsp_bank* bank);
 void fdsp_bank_destroy(fdsp_bank* bank);
 /* `Clone` (every AudioNode is Clone, src/audionode.rs:35; Net and Sequencer clone their units): a new bank of the same

@@ -571,6 +571,14 @@ class Bank {
         b.kind_ = "fdn";
         return b;
     }
+    // a Hadamard network with a filter in its lines or its loop, per-line weights and per-instance parameters (fdsp_fdn_network_create,
+    // fundsp_hip.h): `net` points at [lines] or [instances][lines] arrays the call copies; the bank runs at `sample_rate` from the start
+    static Bank fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate) {
+        Bank b;
+        check(fdsp_fdn_network_create(instances, &net, sample_rate, &b.h_));
+        b.kind_ = "fdn_network";
+        return b;
+    }
     Bank(Bank&& o) noexcept { *this = std::move(o); }
     Bank& operator=(Bank&& o) noexcept {
         if (this != &o) {

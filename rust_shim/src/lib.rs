@@ -33,6 +33,29 @@ pub mod ffi {
     pub struct FdspComm {
         _private: [u8; 0],
     }
+    /// `struct fdsp_fdn_network` (fdsp_fdn_network_create): a filtered / per-instance Hadamard network
+    #[repr(C)]
+    pub struct FdspFdnNetwork {
+        pub lines: c_int,
+        pub inputs: c_int,
+        pub outputs: c_int,
+        pub taps: c_int,
+        pub filter: c_int,
+        pub svf_mode: c_int,
+        pub place: c_int,
+        pub per_instance: c_int,
+        pub delays: *const f64,
+        pub weights: *const f32,
+        pub cutoff: *const f32,
+        pub q: *const f32,
+        pub gain: *const f32,
+        pub line_gain: *const f32,
+    }
+    pub const FDSP_FDN_FILTER_NONE: c_int = 0;
+    pub const FDSP_FDN_FILTER_LOWPOLE: c_int = 1;
+    pub const FDSP_FDN_FILTER_SVF: c_int = 2;
+    pub const FDSP_FDN_IN_LINE: c_int = 0;
+    pub const FDSP_FDN_IN_LOOP: c_int = 1;
     pub const FDSP_OK: c_int = 0;
     pub const FDSP_LAYOUT_VOICE_MINOR: c_int = 0;
     pub const FDSP_LAYOUT_PLANAR: c_int = 1;
@@ -55,6 +78,7 @@ pub mod ffi {
         pub fn fdsp_reverb3_stereo_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, lowpole_cutoff_hz: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_reverb3_stereo_svf_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, svf_mode: c_int, cutoff_hz: f32, q: f32, gain: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_create_on(device: c_int, instances: usize, lines: c_int, delays: *const f64, taps: c_int, weights: *const f32, inputs: c_int, outputs: c_int, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_fdn_network_create_on(device: c_int, instances: usize, net: *const FdspFdnNetwork, sample_rate: f64, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_bank_destroy(bank: *mut FdspBank);
         pub fn fdsp_bank_clone(bank: *const FdspBank, out: *mut *mut FdspBank) -> c_int; // Clone: slots, rings, sample rate, options, events
         pub fn fdsp_bank_inputs(bank: *const FdspBank) -> c_int;
@@ -94,6 +118,24 @@ pub mod ffi {
     }
 }
 use ffi::*;
+
+/// The network of `HipBank::fdn_network` (see there): filter = FDSP_FDN_FILTER_*, svf_mode = FDSP_SVF_* order (0 lowpass .. 8 highshelf),
+/// place = FDSP_FDN_IN_LINE | FDSP_FDN_IN_LOOP; `taps` = 0 means no Fir node, `line_gain` = None no `* g` node.
+pub struct FdnNetwork<'a> {
+    pub inputs: usize,
+    pub outputs: usize,
+    pub taps: usize,
+    pub filter: c_int,
+    pub svf_mode: c_int,
+    pub place: c_int,
+    pub per_instance: bool,
+    pub delays: &'a [f64],
+    pub weights: &'a [f32],
+    pub cutoff: Option<&'a [f32]>,
+    pub q: Option<&'a [f32]>,
+    pub gain: Option<&'a [f32]>,
+    pub line_gain: Option<&'a [f32]>,
+}
 
 /// The engine's last error message for this thread.
 pub fn last_error() -> String {
@@ -197,6 +239,42 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
             fdsp_fdn_create_on(device as c_int, instances, delays.len() as c_int, delays.as_ptr(), weights.len() as c_int, weights.as_ptr(), inputs as c_int, outputs as c_int, &mut bank)
         })?;
         Self::adopt(bank, "fdn", instances)
+    }
+
+    /// `instances` x a Hadamard network with a filter in its lines (`place` = FDSP_FDN_IN_LINE:
+    /// `fdn(stacki(|i| delay(t_i) [>> fir(w_i)] [>> F_i] [* g_i]))`) or in its loop (FDSP_FDN_IN_LOOP:
+    /// `fdn2(stacki(|i| delay(t_i) [>> fir(w_i)]), stacki(|i| F_i [* g_i]))`), split / multisplit in front and join / multijoin behind
+    /// (include/fundsp_hip.h `fdsp_fdn_network`).  Every slice holds one value per line, or with `per_instance` one per instance and line
+    /// (`weights`: `taps` per line); the bank is created at `sample_rate`, where every delay must be at least 128 samples.
+    pub fn fdn_network(instances: usize, net: &FdnNetwork, sample_rate: f64, device: i32) -> Result<Self, String> {
+        let sets = if net.per_instance { instances } else { 1 };
+        let lines = if sets == 0 { 0 } else { net.delays.len() / sets };
+        let per_line = |a: Option<&[f32]>, k: usize| a.map_or(true, |a| a.len() == sets * lines * k);
+        if lines * sets != net.delays.len() || !per_line(Some(net.weights), net.taps) || !per_line(net.cutoff, 1) || !per_line(net.q, 1)
+            || !per_line(net.gain, 1) || !per_line(net.line_gain, 1)
+        {
+            return Err("HipBank::fdn_network: every slice needs one value per line (per instance and line with per_instance)".into());
+        }
+        let ptr = |a: Option<&[f32]>| a.map_or(core::ptr::null(), |a| a.as_ptr());
+        let c = FdspFdnNetwork {
+            lines: lines as c_int,
+            inputs: net.inputs as c_int,
+            outputs: net.outputs as c_int,
+            taps: net.taps as c_int,
+            filter: net.filter,
+            svf_mode: net.svf_mode,
+            place: net.place,
+            per_instance: net.per_instance as c_int,
+            delays: net.delays.as_ptr(),
+            weights: if net.taps > 0 { net.weights.as_ptr() } else { core::ptr::null() },
+            cutoff: ptr(net.cutoff),
+            q: ptr(net.q),
+            gain: ptr(net.gain),
+            line_gain: ptr(net.line_gain),
+        };
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_fdn_network_create_on(device as c_int, instances, &c, sample_rate, &mut bank) })?;
+        Self::adopt(bank, "fdn_network", instances)
     }
 
     fn adopt(bank: *mut FdspBank, kind: &str, voices: usize) -> Result<Self, String> {
