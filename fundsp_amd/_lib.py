@@ -32,6 +32,15 @@ class FdnNetwork(C.Structure):
                 ("per_instance", _i), ("delays", C.POINTER(_d)), ("weights", _fp), ("cutoff", _fp), ("q", _fp), ("gain", _fp), ("line_gain", _fp)]
 
 
+RESYNTH_PASS, RESYNTH_BAND, RESYNTH_GAIN = 0, 1, 2   # fdsp_resynth_spec::processor
+
+
+class ResynthSpec(C.Structure):
+    """struct fdsp_resynth_spec (include/fundsp_hip.h)"""
+    _fields_ = [("window_length", _i), ("inputs", _i), ("outputs", _i), ("processor", _i), ("source", _i * 8), ("per_instance", _i),
+                ("flush_denormals", _i), ("lo_hz", _fp), ("hi_hz", _fp), ("gain", _fp)]
+
+
 SYMBOLS = {
     "fdsp_last_error": (_cs, []),
     "fdsp_kind_count": (_i, []),
@@ -63,6 +72,11 @@ SYMBOLS = {
     "fdsp_fdn_create_on": (_i, [_i, _sz, _i, C.POINTER(_d), _i, C.POINTER(C.c_float), _i, _i, C.POINTER(_P)]),
     "fdsp_fdn_network_create": (_i, [_sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
     "fdsp_fdn_network_create_on": (_i, [_i, _sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
+    "fdsp_resynth_create": (_i, [_sz, C.POINTER(ResynthSpec), C.POINTER(_P)]),
+    "fdsp_resynth_create_on": (_i, [_i, _sz, C.POINTER(ResynthSpec), C.POINTER(_P)]),
+    "fdsp_resynth_set_band": (_i, [_P, _fp, _sz, _sz]),
+    "fdsp_resynth_set_gain": (_i, [_P, _fp, _sz, _sz]),
+    "fdsp_resynth_tables": (_i, [_i, _fp, _fp]),
     "fdsp_bank_set_bus": (_i, [_P, _i, _f, _f]),
     "fdsp_bank_get_bus": (_i, [_P, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f)]),
     "fdsp_jit_compiler": (C.c_char_p, []),

@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import FdspError  # noqa: E402
 from ._lib import FADE_POWER, FADE_SMOOTH, LAYOUT_PLANAR, LAYOUT_VOICE_MINOR, MIX_PAN, MIX_SUM, MODE_PROCESS, MODE_TICK, check, lib
 
+RESYNTH_PROCESSORS = {"pass": 0, "band": 1, "gain": 2}   # fdsp_resynth_spec::processor
 SVF_MODES = dict(lowpass=0, highpass=1, bandpass=2, notch=3, peak=4, allpass=5, bell=6, lowshelf=7, highshelf=8)
 BQ_KINDS = dict(butter=0, resonator=1, lowpass=2, highpass=3, bell=4)
 
@@ -60,6 +61,26 @@ class Bank:
         reference renders the WHOLE graph flushed, and so does the oracle)."""
         from . import graph as G
 
+        rs = getattr(graph, "resynth_plan", None)
+        if rs is not None:   # resynth(..) itself: the batched FFT kernels (fdsp_resynth_create)
+            b = cls.resynth(voices, **rs, flush_denormals=flush_denormals)
+            if sample_rate is not None:
+                b.set_sample_rate(sample_rate)
+            return b
+        parts = getattr(graph, "pipe_parts", None)
+        if parts is not None and getattr(parts[1], "resynth_plan", None) is not None and not G.has_resynth(parts[0]):
+            # `front >> resynth(..)` -- the reference's criterion bench noise() >> resynth::<U1, U1, _>(1024, ..): the front keeps its fused kernel,
+            # the resynthesizer its FFT kernels; the front is seeded from the whole graph's construction hash (Resynth::ID = 80 enters it through the
+            # probe's ResynthPing) and both halves flush denormals when the front has a Feedback node, as the one graph would
+            ftz = flush_denormals or "Feedback" in parts[0].type
+            eff = cls.resynth(voices, **parts[1].resynth_plan, flush_denormals=ftz)
+            if sample_rate is not None:
+                eff.set_sample_rate(sample_rate)
+            src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, fdn_kernel=fdn_kernel, flush_denormals=ftz)
+            return Chain(src, eff, construction_hash=probe_hash(graph))
+        if G.has_resynth(graph):
+            raise ValueError("resynth(..) renders as a whole graph or as the last node of a pipe, `front >> resynth(..)` (a Chain); "
+                             "inside a stack, sum, bus or feedback, or followed by more nodes, it is not supported")
         stock = getattr(graph, "stock_reverb", None) if fdn_kernel else None
         if stock is not None and graph.type.startswith("Pipe<") and "Feedback<" in graph.type:
             # reverb_stereo(..) / reverb4_stereo(..) themselves (graph.py marks the object its constructor returns): their lane-per-frame kernels
@@ -243,6 +264,66 @@ class Bank:
         b.sample_rate = sr
         return b
 
+    @classmethod
+    def resynth(cls, instances, window, inputs=1, outputs=1, processor="pass", source=None, band=None, gain=None, flush_denormals=False,
+                device=-1):
+        """Bank of `instances` x resynth::<I, O, _>(window, closure) (resynth.rs:216-372) through the batched FFT kernels
+        (fdsp_resynth_create).  `processor`: "pass" (fft.set(o, i, fft.at(source[o], i))), "band" (the same where lo <= frequency(i) <= hi)
+        or "gain" (fft.at(source[o], i) * gain[o][i]).  `source`: the input channel of every output (-1 = silent; default o % inputs).
+        `band`: (lo, hi) pairs, shape [outputs, 2] or [instances, outputs, 2] (or one pair for every output); `gain`: [window/2 + 1],
+        [outputs, window/2 + 1] or [instances, outputs, window/2 + 1].  Any [instances, ..] table makes the tables per instance."""
+        V, N, I, O = int(instances), int(window), int(inputs), int(outputs)
+        spec = _lib.ResynthSpec()
+        spec.window_length, spec.inputs, spec.outputs = N, I, O
+        spec.processor = RESYNTH_PROCESSORS[processor] if isinstance(processor, str) else int(processor)
+        src = [o % I for o in range(O)] if source is None else [int(x) for x in source]
+        if len(src) != O:
+            raise ValueError(f"resynth: source has {len(src)} entries for {O} outputs")
+        for o in range(8):
+            spec.source[o] = src[o] if o < O else -1
+        spec.flush_denormals = 1 if flush_denormals else 0
+        keep = []
+        per = False
+        if spec.processor == _lib.RESYNTH_BAND:
+            if band is None:
+                raise ValueError("resynth: processor 'band' needs band=(lo, hi)")
+            t = np.asarray(band, dtype=np.float32)
+            per = t.ndim == 3
+            t = np.ascontiguousarray(np.broadcast_to(t, (V, O, 2) if per else (O, 2)))
+            lo, hi = np.ascontiguousarray(t[..., 0]), np.ascontiguousarray(t[..., 1])
+            keep += [lo, hi]
+            spec.lo_hz, spec.hi_hz = _fptr(lo), _fptr(hi)
+        if spec.processor == _lib.RESYNTH_GAIN:
+            if gain is None:
+                raise ValueError("resynth: processor 'gain' needs gain")
+            t = np.asarray(gain, dtype=np.float32)
+            per = t.ndim == 3
+            if t.shape[-1] != N // 2 + 1:
+                raise ValueError(f"resynth: gain rows take window/2 + 1 = {N // 2 + 1} bins, got {t.shape[-1]}")
+            t = np.ascontiguousarray(np.broadcast_to(t, (V, O, N // 2 + 1) if per else (O, N // 2 + 1)))
+            keep.append(t)
+            spec.gain = _fptr(t)
+        spec.per_instance = 1 if per else 0
+        h = C.c_void_p()
+        check(lib().fdsp_resynth_create_on(int(device), V, C.byref(spec), C.byref(h)))
+        b = cls("resynth", V, _handle=h)
+        b.window = N
+        return b
+
+    def set_band(self, band, first=0):
+        """Replace (lo, hi) table rows from `first` (fdsp_resynth_set_band).  `band` takes the constructor's shapes: one (lo, hi) pair or
+        [outputs, 2] for one row (broadcast over the outputs), [rows, outputs | 1, 2] for several."""
+        t = resynth_table_rows(band, 2, self.outputs(), "band")
+        check(lib().fdsp_resynth_set_band(self._h, _fptr(t), int(first), t.shape[0]))
+
+    def set_gain(self, gain, first=0):
+        """Replace gain table rows from `first` (fdsp_resynth_set_gain).  `gain` takes the constructor's shapes: [bins] or [outputs, bins]
+        for one row (broadcast over the outputs), [rows, outputs | 1, bins] for several; bins = window/2 + 1."""
+        if getattr(self, "window", None) is None:
+            raise ValueError("set_gain: not a resynthesizer bank")
+        t = resynth_table_rows(gain, self.window // 2 + 1, self.outputs(), "gain")
+        check(lib().fdsp_resynth_set_gain(self._h, _fptr(t), int(first), t.shape[0]))
+
     def clone(self):
         """AudioNode: Clone -- a new bank that continues exactly where this one stands (fdsp_bank_clone: slots, rings, sample
         rate, arithmetic mode, launch options, scheduler events, reverb state)."""
@@ -250,6 +331,8 @@ class Bank:
         check(lib().fdsp_bank_clone(self._h, C.byref(h)))
         b = Bank(self.kind, self.voices, _handle=h)
         b.sample_rate = self.sample_rate
+        if hasattr(self, "window"):
+            b.window = self.window
         return b
 
     def device(self):
@@ -514,6 +597,17 @@ class Bank:
         ms = C.c_float()
         check(lib().fdsp_bank_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+def resynth_table_rows(values, width, outputs, what):
+    """A resynthesizer's table rows as the C ABI reads them: a contiguous f32 [rows, outputs, width] array (width 2 for (lo, hi), window/2 + 1
+    for gains).  [width] and [outputs | 1, width] are one row, [rows, outputs | 1, width] several; anything else raises ValueError (the library
+    reads rows * outputs * width floats from the pointer it is given)."""
+    t = np.asarray(values, dtype=np.float32)
+    if t.ndim == 0 or t.ndim > 3 or t.shape[-1] != width or (t.ndim >= 2 and t.shape[-2] not in (1, outputs)) or (t.ndim == 3 and t.shape[0] == 0):
+        raise ValueError(f"resynth {what} table: takes [{width}], [outputs = {outputs} or 1, {width}] or [rows, outputs or 1, {width}]; got shape {t.shape}")
+    rows = t.shape[0] if t.ndim == 3 else 1
+    return np.ascontiguousarray(np.broadcast_to(t.reshape((rows,) + t.shape[-2:] if t.ndim >= 2 else (1, 1, width)), (rows, outputs, width)))
 
 
 PIPE_ID = 6   # Pipe::ID (audionode.rs:1375-1492; fd_nodes.hpp)

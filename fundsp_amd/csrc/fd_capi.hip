@@ -15,6 +15,7 @@
 #include "fd_engine.hpp"
 #include "fd_fdn.hpp"
 #include "fd_reverb3.hpp"
+#include "fd_resynth.hpp"
 #include "fd_fdnx.hpp"
 #include "fd_opts.hpp"
 
@@ -408,8 +409,21 @@ struct FdnBank {  // reverb_stereo / reverb4_stereo banks (fd_fdn.hip): rings + 
     size_t stage_n = 0;
 };
 
+struct RsBank {  // resynthesizer banks (fdsp_resynth_create, fd_resynth.hpp): tables, frame ring, input ring, device sample counter
+    fd::RsConst c{};
+    fd::RsState st{};
+    int ftz = 0;              // 1: the flush-to-zero instantiation (a Feedback node in front)
+    int per_instance = 0;
+    float2* tw = nullptr;
+    float* hann = nullptr;
+    float* hz = nullptr;
+    float2* band = nullptr;   // [rows][O] (lo, hi)
+    float* gain = nullptr;    // [rows][O][N/2 + 1]
+};
+
 struct fdsp_bank {
     FdnBank* fdn = nullptr;
+    RsBank* rs = nullptr;
     float* ring = nullptr;       // delay-ring memory [ring node][position][voice] for kinds with Delay / Tap nodes
     uint32_t ring_cap = 0;       // positions per ring node
     const fd::KindOps* ops = nullptr;
@@ -1234,6 +1248,179 @@ int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_netw
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
     return fdsp_fdn_network_create_on(-1, instances, net, sample_rate, out);
 }
+
+// ---- resynthesizer banks (fd_resynth.hpp) ----------------------------------------------------------------------------------------------
+static void rs_free(RsBank* r) {
+    if (!r) return;
+    for (void* p : {(void*)r->st.frames, (void*)r->st.xin, (void*)r->st.samples, (void*)r->st.fstep, (void*)r->tw, (void*)r->hann, (void*)r->hz, (void*)r->band, (void*)r->gain})
+        if (p) hipFree(p);
+    delete r;
+}
+static int rs_check_spec(size_t instances, const fdsp_resynth_spec* sp) {
+    if (!sp) return fail(FDSP_EINVAL, "fdsp_resynth_create: spec NULL");
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_resynth_create: no instances");
+    const int N = sp->window_length;
+    if (N < 4 || N > 8192 || (N & (N - 1)) != 0) return fail(FDSP_EINVAL, "fdsp_resynth_create: window_length takes a power of two from 4 to 8192");
+    if (sp->inputs < 1 || sp->inputs > 8 || sp->outputs < 1 || sp->outputs > 8) return fail(FDSP_EINVAL, "fdsp_resynth_create: inputs and outputs take 1 .. 8");
+    if (sp->processor < FDSP_RESYNTH_PASS || sp->processor > FDSP_RESYNTH_GAIN)
+        return fail(FDSP_EINVAL, "fdsp_resynth_create: processor takes FDSP_RESYNTH_PASS, FDSP_RESYNTH_BAND or FDSP_RESYNTH_GAIN");
+    for (int o = 0; o < sp->outputs; o++)
+        if (sp->source[o] < -1 || sp->source[o] >= sp->inputs)
+            return fail(FDSP_EINVAL, "fdsp_resynth_create: source[" + std::to_string(o) + "] = " + std::to_string(sp->source[o]) + " is not an input channel (0 .. inputs-1) or -1 (silent)");
+    if (sp->per_instance != 0 && sp->per_instance != 1) return fail(FDSP_EINVAL, "fdsp_resynth_create: per_instance takes 0 or 1");
+    if (sp->processor == FDSP_RESYNTH_BAND && (!sp->lo_hz || !sp->hi_hz)) return fail(FDSP_EINVAL, "fdsp_resynth_create: FDSP_RESYNTH_BAND needs lo_hz and hi_hz");
+    if (sp->processor == FDSP_RESYNTH_GAIN && !sp->gain) return fail(FDSP_EINVAL, "fdsp_resynth_create: FDSP_RESYNTH_GAIN needs gain");
+    if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, "fdsp_resynth_create: flush_denormals takes 0 or 1");
+    return FDSP_OK;
+}
+int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles) {
+    const int N = window_length;
+    if (N < 4 || N > 8192 || (N & (N - 1)) != 0) return fail(FDSP_EINVAL, "fdsp_resynth_tables: window_length takes a power of two from 4 to 8192");
+    fd::rs_tables(N, h_hann, nullptr, h_twiddles);
+    return FDSP_OK;
+}
+int fdsp_resynth_create_on(int device, size_t instances, const fdsp_resynth_spec* sp, fdsp_bank** out) {
+    if (!out) return fail(FDSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = rs_check_spec(instances, sp)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FDSP_EDEVICE, "no HIP device available: the fundsp_hip engine has no CPU fallback");
+    if (device < 0) device = current_device();
+    if (device < 0 || device >= ndev || device >= MAX_DEVICES) return fail(FDSP_EINVAL, "device index out of range");
+    DeviceGuard guard(device);
+    const int N = sp->window_length, H = N / 4, I = sp->inputs, O = sp->outputs, NB = N / 2 + 1;
+    const size_t V = instances;
+    RsBank* r = new RsBank();
+    fd::RsConst& c = r->c;
+    c.N = N;
+    c.logN = 0;
+    while ((1 << c.logN) < N) c.logN++;
+    c.I = I;
+    c.O = O;
+    c.proc = sp->processor;
+    for (int o = 0; o < fd::RS_MAX_CH; o++) c.src[o] = o < O ? sp->source[o] : -1;
+    c.rows = sp->per_instance ? (int)V : 1;
+    c.invN = 1.0f / (float)N;
+    // frame ring: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large
+    const size_t slot = V * (size_t)O * N * sizeof(float);
+    size_t R = ((size_t)256 << 20) / slot;
+    const size_t rmax = 5 + 65536 / (size_t)H;
+    R = R < 8 ? 8 : (R > rmax ? rmax : R);
+    c.R = (int)R;
+    c.Lmax = (c.R - 5) * H;
+    c.Rx = 1;
+    while (c.Rx < c.Lmax + N) c.Rx <<= 1;
+    r->ftz = sp->flush_denormals;
+    r->per_instance = sp->per_instance;
+    const float fstep = (float)FDSP_DEFAULT_SR / (float)N;
+    std::vector<float> hann(N), hz(N), tw(N);
+    fd::rs_tables(N, hann.data(), hz.data(), tw.data());
+    std::vector<float> band, gain;
+    if (c.proc == FDSP_RESYNTH_BAND) {
+        band.resize((size_t)c.rows * O * 2);
+        for (size_t i = 0; i < (size_t)c.rows * O; i++) {
+            band[2 * i] = sp->lo_hz[i];
+            band[2 * i + 1] = sp->hi_hz[i];
+        }
+    }
+    if (c.proc == FDSP_RESYNTH_GAIN) gain.assign(sp->gain, sp->gain + (size_t)c.rows * O * NB);
+    fdsp_bank* b = new fdsp_bank();
+    b->device = device;
+    b->rs = r;
+    b->V = instances;
+    b->stride = instances;
+    b->sr = FDSP_DEFAULT_SR;
+    if (hipStreamCreate(&b->stream) != hipSuccess || hipEventCreate(&b->e0) != hipSuccess || hipEventCreate(&b->e1) != hipSuccess) {
+        fdsp_bank_destroy(b);
+        return fail(FDSP_EDEVICE, "stream/event creation failed");
+    }
+    hipError_t e = hipMalloc((void**)&r->st.frames, R * slot);
+    if (e == hipSuccess) e = hipMalloc((void**)&r->st.xin, V * (size_t)I * c.Rx * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->st.samples, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->st.fstep, sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->tw, (N / 2) * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->hann, N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&r->hz, N * sizeof(float));
+    if (e == hipSuccess && !band.empty()) e = hipMalloc((void**)&r->band, band.size() * sizeof(float));
+    if (e == hipSuccess && !gain.empty()) e = hipMalloc((void**)&r->gain, gain.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(r->tw, tw.data(), (N / 2) * sizeof(float2), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->hann, hann.data(), N * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->hz, hz.data(), N * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && r->band) e = hipMemcpyAsync(r->band, band.data(), band.size() * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && r->gain) e = hipMemcpyAsync(r->gain, gain.data(), gain.size() * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    // reset: the windows start empty (nothing is read before a frame of this run exists, but the rings start defined)
+    if (e == hipSuccess) e = hipMemsetAsync(r->st.samples, 0, sizeof(unsigned long long), b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->st.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->st.frames, 0, R * slot, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->st.xin, 0, V * (size_t)I * c.Rx * sizeof(float), b->stream);
+    if (e == hipSuccess) e = sync_bank_stream(b);
+    if (e != hipSuccess) {
+        fdsp_bank_destroy(b);
+        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("fdsp_resynth_create buffers: ") + hipGetErrorString(e));
+    }
+    c.tw = r->tw;
+    c.hann = r->hann;
+    c.hz = r->hz;
+    c.band = r->band;
+    c.gain = r->gain;
+    *out = b;
+    return FDSP_OK;
+}
+int fdsp_resynth_create(size_t instances, const fdsp_resynth_spec* spec, fdsp_bank** out) { return fdsp_resynth_create_on(-1, instances, spec, out); }
+static int rs_set_table(fdsp_bank* b, const float* h, size_t first, size_t count, bool gain) {
+    if (!b || !h) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: bank or values NULL");
+    if (!b->rs) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: not a resynthesizer bank");
+    RsBank* r = b->rs;
+    if (r->c.proc != (gain ? FDSP_RESYNTH_GAIN : FDSP_RESYNTH_BAND))
+        return fail(FDSP_EINVAL, gain ? "fdsp_resynth_set_gain: the bank's processor is not FDSP_RESYNTH_GAIN" : "fdsp_resynth_set_band: the bank's processor is not FDSP_RESYNTH_BAND");
+    const size_t rows = (size_t)r->c.rows;
+    if (first > rows || count > rows - first) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: rows out of range (one row per instance with per_instance, else the single row 0)");
+    if (count == 0) return FDSP_OK;
+    DeviceGuard guard(b->device);
+    const size_t row = (size_t)r->c.O * (gain ? (size_t)(r->c.N / 2 + 1) : 2);
+    HIPCHK(await_last_render(b));
+    HIPCHK(hipMemcpyAsync((gain ? r->gain : (float*)r->band) + first * row, h, count * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(sync_bank_stream(b));   // (h is borrowed for the call; the bank's stream is idle when a setter returns)
+    return FDSP_OK;
+}
+int fdsp_resynth_set_band(fdsp_bank* b, const float* h_lo_hi, size_t first, size_t count) { return rs_set_table(b, h_lo_hi, first, count, false); }
+int fdsp_resynth_set_gain(fdsp_bank* b, const float* h_gain, size_t first, size_t count) { return rs_set_table(b, h_gain, first, count, true); }
+static int rs_clone(const fdsp_bank* src, fdsp_bank** out) {
+    const RsBank* a = src->rs;
+    fdsp_resynth_spec sp{};
+    sp.window_length = a->c.N;
+    sp.inputs = a->c.I;
+    sp.outputs = a->c.O;
+    sp.processor = a->c.proc;
+    for (int o = 0; o < 8; o++) sp.source[o] = a->c.src[o];
+    sp.flush_denormals = a->ftz;
+    sp.per_instance = a->per_instance;
+    const size_t nt = (size_t)a->c.rows * a->c.O;
+    std::vector<float> lo(nt, 0.0f), hi(nt, 0.0f), g(a->gain ? nt * (a->c.N / 2 + 1) : 0);
+    sp.lo_hz = lo.data();
+    sp.hi_hz = hi.data();
+    sp.gain = g.data();
+    fdsp_bank* b = nullptr;
+    if (int rc = fdsp_resynth_create_on(src->device, src->V, &sp, &b)) return rc;
+    RsBank* d = b->rs;
+    const size_t slot = src->V * (size_t)a->c.O * a->c.N * sizeof(float);
+    hipError_t e = hipMemcpyAsync(d->st.frames, a->st.frames, (size_t)a->c.R * slot, hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->st.xin, a->st.xin, src->V * (size_t)a->c.I * a->c.Rx * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->st.samples, a->st.samples, sizeof(unsigned long long), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->st.fstep, a->st.fstep, sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess && a->band) e = hipMemcpyAsync(d->band, a->band, nt * sizeof(float2), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess && a->gain) e = hipMemcpyAsync(d->gain, a->gain, g.size() * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
+    if (e == hipSuccess) e = sync_bank_stream(b);
+    if (e != hipSuccess) {
+        fdsp_bank_destroy(b);
+        return fail(FDSP_EDEVICE, std::string("fdsp_bank_clone: resynthesizer state: ") + hipGetErrorString(e));
+    }
+    b->sr = src->sr;
+    b->math = src->math;
+    b->opt_timing = src->opt_timing;
+    *out = b;
+    return FDSP_OK;
+}
 static int rv3_create(int device, size_t instances, double time, double diffusion, const fd::Rv3Filter& flt, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (!(time > 0.0) || !(diffusion >= 0.0 && diffusion <= 1.0) || !(flt.cutoff > 0.0f))
@@ -1323,6 +1510,10 @@ void fdsp_bank_destroy(fdsp_bank* b) {
         delete b->fdn;
         b->fdn = nullptr;
     }
+    if (b->rs) {
+        rs_free(b->rs);
+        b->rs = nullptr;
+    }
     if (b->slots) hipFree(b->slots);
     if (b->ring) hipFree(b->ring);
     if (b->ev) hipFree(b->ev);
@@ -1349,6 +1540,7 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     // everything queued on the source's stream (and a render on a caller's stream) lands before the copy reads it
     if (src->ext_pending && src->e1) HIPCHK(hipEventSynchronize(src->e1));
     HIPCHK(hipStreamSynchronize(src->stream));
+    if (src->rs) return rs_clone(src, out);
     fdsp_bank* b = nullptr;
     int rc;
     if (src->fdn)
@@ -1442,6 +1634,7 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
 // `wet * node` / `dry * multipass() & wet * node` around a reverb / network bank (fd_fdn.hpp FdnBus): a host-side setting, read at every launch
 int fdsp_bank_set_bus(fdsp_bank* b, int mode, float wet, float dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: bank NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: resynthesizer banks have no bus (out of scope: render the dry path separately)");
     if (!b->fdn) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: reverb / network banks only (a run-time compiled graph carries its bus in the graph: fdsp_graph_compile)");
     if (mode < FDSP_BUS_NONE || mode > FDSP_BUS_DRY_WET) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: mode takes FDSP_BUS_NONE, FDSP_BUS_WET or FDSP_BUS_DRY_WET");
     if (mode == FDSP_BUS_DRY_WET && b->fdn->c.nin != b->fdn->c.nout)
@@ -1454,6 +1647,7 @@ int fdsp_bank_set_bus(fdsp_bank* b, int mode, float wet, float dry) {
 
 int fdsp_bank_get_bus(const fdsp_bank* b, int* mode, float* wet, float* dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_get_bus: bank NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: resynthesizer banks have no bus");
     if (!b->fdn) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: reverb / network banks only");
     if (mode) *mode = b->fdn->bus.mode;
     if (wet) *wet = b->fdn->bus.wet;
@@ -1461,13 +1655,22 @@ int fdsp_bank_get_bus(const fdsp_bank* b, int* mode, float* wet, float* dry) {
     return FDSP_OK;
 }
 
-int fdsp_bank_inputs(const fdsp_bank* b) { return b ? (b->fdn ? b->fdn->c.nin : b->ops->nin) : FDSP_EINVAL; }
-int fdsp_bank_outputs(const fdsp_bank* b) { return b ? (b->fdn ? b->fdn->c.nout : b->ops->nout) : FDSP_EINVAL; }
+int fdsp_bank_inputs(const fdsp_bank* b) { return b ? (b->rs ? b->rs->c.I : b->fdn ? b->fdn->c.nin : b->ops->nin) : FDSP_EINVAL; }
+int fdsp_bank_outputs(const fdsp_bank* b) { return b ? (b->rs ? b->rs->c.O : b->fdn ? b->fdn->c.nout : b->ops->nout) : FDSP_EINVAL; }
 size_t fdsp_bank_voices(const fdsp_bank* b) { return b ? b->V : 0; }
 
 int fdsp_bank_set_sample_rate(fdsp_bank* b, double sr) {
     if (!b || !(sr > 0.0)) return fail(FDSP_EINVAL, "bad bank or sample rate");
     DeviceGuard guard(b->device);
+    if (b->rs) {  // FftWindow::set_sample_rate: frequency() follows, every other state stays (resynth.rs:170-172, 325-330)
+        // the bin spacing lives in device memory, in stream order behind the last render: a captured launch replays with the new rate
+        const float fstep = (float)sr / (float)b->rs->c.N;
+        HIPCHK(await_last_render(b));
+        HIPCHK(hipMemcpyAsync(b->rs->st.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(sync_bank_stream(b));   // (fstep is a local; the bank's stream is idle when a setter returns)
+        b->sr = sr;
+        return FDSP_OK;
+    }
     if (b->fdn) {
         if (sr == b->sr) return FDSP_OK;  // Delay::set_sample_rate: nothing happens unless the rate changes
         HIPCHK(await_last_render(b));
@@ -1486,6 +1689,12 @@ int fdsp_bank_set_sample_rate(fdsp_bank* b, double sr) {
 int fdsp_bank_reset(fdsp_bank* b) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     DeviceGuard guard(b->device);
+    if (b->rs) {  // Resynth::reset: the sample count and the four windows start over (resynth.rs:332-337)
+        HIPCHK(await_last_render(b));
+        HIPCHK(hipMemsetAsync(b->rs->st.samples, 0, sizeof(unsigned long long), b->stream));
+        HIPCHK(sync_bank_stream(b));
+        return FDSP_OK;
+    }
     if (b->fdn) {
         HIPCHK(await_last_render(b));
         if (b->fdn->kind == 3) fd::rv3_launch_reset(b->fdn->c3, b->fdn->st3, b->V, b->stream);
@@ -1505,7 +1714,7 @@ int fdsp_bank_reset(fdsp_bank* b) {
 int fdsp_bank_set_seed(fdsp_bank* b, const uint64_t* h_seeds, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     DeviceGuard guard(b->device);
-    if (b->fdn) return FDSP_OK;  // no node of reverb_stereo uses its hash (Delay, Fir, Panner: default set_hash)
+    if (b->fdn || b->rs) return FDSP_OK;  // no node of reverb_stereo (nor Resynth) uses its hash (Delay, Fir, Panner: default set_hash)
     if (int rc = check_range(b, first, count)) return rc;
     if (count == 0) return FDSP_OK;
     uint64_t* d = nullptr;
@@ -1669,7 +1878,11 @@ int fdsp_bank_process(fdsp_bank* b, size_t frames, const float* d_in, float* d_o
     const bool timing = timing_on(b);
     if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
     resolve_opts(b);
-    if (b->fdn) {  // Feedback::process is the per-sample tick (feedback.rs:136-146): both modes are the same arithmetic but for the joins (MultiJoin / Join)
+    if (b->rs) {   // Resynth has no process override: FDSP_MODE_PROCESS == FDSP_MODE_TICK
+        RsBank* r = b->rs;
+        if (r->ftz) fd::rs_ftz::rs_launch_render(r->c, r->st, b->V, d_in, d_out, frames, frame_stride, layout, s);
+        else fd::rs_ieee::rs_launch_render(r->c, r->st, b->V, d_in, d_out, frames, frame_stride, layout, s);
+    } else if (b->fdn) {  // Feedback::process is the per-sample tick (feedback.rs:136-146): both modes are the same arithmetic but for the joins (MultiJoin / Join)
         FdnBank* f = b->fdn;
         const int tick = mode == FDSP_MODE_TICK ? 1 : 0, nin = f->c.nin, nout = f->c.nout;
         // voice-minor buffers of banks with at least a tile of instances go through the planar staging copy (the lane = frame kernels read
@@ -1742,6 +1955,7 @@ int mix_reserve(fdsp_bank* b, size_t floats) {
 
 int fdsp_bank_set_pan(fdsp_bank* b, const float* h_pan, size_t first, size_t count) {
     if (!b || !h_pan) return fail(FDSP_EINVAL, "bank or h_pan NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     if (int rc = check_range(b, first, count)) return rc;
     if (count == 0) return FDSP_OK;
@@ -1766,6 +1980,7 @@ int fdsp_bank_set_pan(fdsp_bank* b, const float* h_pan, size_t first, size_t cou
 
 int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     const size_t nm = (size_t)(fdsp_bank_outputs(b) > 2 ? fdsp_bank_outputs(b) : 2);
     if (b->ops && b->ops->prepare_mix) b->ops->prepare_mix(b->math == FDSP_MATH_FAST && (bool)b->ops->render_mix_fast);  // run-time compiled graphs: build the mix kernels NOW
@@ -1774,6 +1989,7 @@ int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
 
 int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float* d_mix, int mix, int mode, void* stream) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
     if (!d_mix) return fail(FDSP_EINVAL, "d_mix is NULL");
@@ -1820,6 +2036,7 @@ int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float*
 
 int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t frames, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     if (b->fdn || !b->ring) return fail(FDSP_EINVAL, "this bank has no ring memory");
     if (!data) return fail(FDSP_EINVAL, "data is NULL");
@@ -1841,6 +2058,7 @@ int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t f
 
 int fdsp_bank_set_events(fdsp_bank* b, const double* events, const int* fade, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     if (b->fdn) return fail(FDSP_EINVAL, "reverb banks have no event scheduler");
     if (!events) return fail(FDSP_EINVAL, "events is NULL");
@@ -1896,6 +2114,7 @@ namespace {
 // Sequencer's output, the sum of the events, to d_mix [outputs][frames]) share everything but the launch
 int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, float* d_mix, int mode, void* stream) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
     const bool mixing = d_out == nullptr;

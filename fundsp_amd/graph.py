@@ -845,3 +845,61 @@ def uses_wavetables(g):
     sets = (("saw", "WaveSynth<0>"), ("square", "WaveSynth<1>"), ("triangle", "WaveSynth<2>"), ("organ", "WaveSynth<4>"),
             ("soft_saw", "WaveSynth<5>"), ("hammond", "WaveSynth<6>"), ("saw", "PulseWave"))
     return sorted({k for k, t in sets if t in g.type})
+
+
+# --- resynth (resynth.rs:216-372): rendered by its own bank family (Bank.resynth, fdsp_resynth_create), never by the run-time compiler.
+# The type below only lets the hash probe (bank.probe_hash) walk a graph that contains the node: Resynth::ID = 80 with the default ping
+# (audionode.rs:156-161), so a front piped into it is seeded as the reference's Pipe seeds it.
+_RESYNTH_SRC = """
+template <int I, int O> struct ResynthPing {
+    static constexpr int IN = I, OUT = O, RINGS = 0;
+    static constexpr uint64_t ID = 80;
+    template <class V> FD_HD void visit(V&) {}
+    FD_HD void bind(Ctx&) {}
+    FD_HD void init() {}
+    FD_HD void update(double) {}
+    FD_HD void reset() {}
+    FD_HD uint64_t ping(bool, uint64_t h) { return atto(h, ID); }
+    FD_HD void begin_block(int) {}
+    FD_HD bool tripped() const { return false; }
+    FD_HD void end_simd() {}
+    template <int PH> FD_HD void step(const float*, float* out) { for (int o = 0; o < O; o++) out[o] = 0.0f; }
+    FD_STEP2_VIA_STEP
+};
+"""
+RESYNTH_PROCESSORS = ("pass", "band", "gain")
+
+
+def resynth(window, inputs=1, outputs=1, processor="pass", source=None, band=None, gain=None):
+    """resynth::<I, O, _>(window, closure) (prelude.rs:2825-2856) with a stock closure: "pass" (fft.set(o, i, fft.at(source[o], i))),
+    "band" (the same where lo <= fft.frequency(i) <= hi; band = (lo, hi) per output) or "gain" (times gain[o][i], window/2 + 1 bins).
+    The arguments are checked here, on the host; Bank.from_graph renders the node alone or as `front >> resynth(..)`."""
+    N, I, O = int(window), int(inputs), int(outputs)
+    if N < 4 or N > 8192 or N & (N - 1):
+        raise ValueError(f"resynth: window {N} is not a power of two from 4 to 8192")
+    if not (1 <= I <= 8 and 1 <= O <= 8):
+        raise ValueError(f"resynth: inputs and outputs take 1 .. 8 (got {I} -> {O})")
+    if processor not in RESYNTH_PROCESSORS:
+        raise ValueError(f"resynth: processor takes one of {RESYNTH_PROCESSORS}, got {processor!r}")
+    src = [o % I for o in range(O)] if source is None else [int(x) for x in source]
+    if len(src) != O or any(x < -1 or x >= I for x in src):
+        raise ValueError(f"resynth: source needs {O} entries, each an input channel 0 .. {I - 1} or -1 (silent): {src}")
+    if processor == "band":
+        if band is None:
+            raise ValueError("resynth: processor 'band' needs band=(lo, hi)")
+        t = np.asarray(band, dtype=np.float32)
+        if t.shape[-1] != 2 or t.ndim > 3 or (t.ndim >= 2 and t.shape[-2] not in (1, O)):
+            raise ValueError(f"resynth: band takes (lo, hi), [outputs, 2] or [instances, outputs, 2]; got shape {t.shape}")
+    if processor == "gain":
+        if gain is None:
+            raise ValueError("resynth: processor 'gain' needs gain")
+        t = np.asarray(gain, dtype=np.float32)
+        if t.shape[-1] != N // 2 + 1 or t.ndim > 3 or (t.ndim >= 2 and t.shape[-2] not in (1, O)):
+            raise ValueError(f"resynth: gain takes [window/2 + 1 = {N // 2 + 1}], [outputs, bins] or [instances, outputs, bins]; got shape {t.shape}")
+    g = Graph(f"ResynthPing<{I},{O}>", I, O, [], 0, _RESYNTH_SRC)
+    g.resynth_plan = dict(window=N, inputs=I, outputs=O, processor=processor, source=src, band=band, gain=gain)
+    return g
+
+
+def has_resynth(graph):
+    return "ResynthPing<" in graph.type

@@ -245,6 +245,46 @@ typedef struct fdsp_fdn_network {
     const float* line_gain;             /* the `* g` behind the filter, NULL = no such node */
 } fdsp_fdn_network;
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out);
+/* Resynthesizer banks: `instances` independent resynth::<I, O, _>(window_length, processor) nodes (src/resynth.rs:216-372, prelude
+ * src/prelude.rs:2825-2856) with one of three stock processing closures (o and i in increasing order, bins i = 0 .. window_length/2):
+ *   FDSP_RESYNTH_PASS  fft.set(o, i, fft.at(source[o], i))                    -- FftWindow::forward, the reference's criterion bench
+ *   FDSP_RESYNTH_BAND  the same where lo_hz[o] <= fft.frequency(i) <= hi_hz[o] -- the prelude's brickwall example
+ *   FDSP_RESYNTH_GAIN  fft.set(o, i, fft.at(source[o], i) * gain[o][i])        -- Complex32 times f32
+ * source[o] = -1 leaves output o silent.  window_length N is a power of two from 4 to 8192; inputs and outputs take 1 .. 8.  Tables are
+ * [outputs] (per_instance = 0) or [instances][outputs] (per_instance = 1); gain has N/2 + 1 entries per output.  flush_denormals = 1 selects the
+ * flush-to-zero build of the kernels: the reference renders the whole graph flushed when a Feedback node was constructed in front of it
+ * (src/denormal.rs); 0 keeps IEEE denormals like a graph without one.
+ * The frames that complete inside a launch are independent given its input: one workgroup unit per (frame, instance, output) does the
+ * source channel's real FFT and the output's inverse in LDS (64 KiB at N = 8192), the real outputs go to a frame ring in HBM, and a second
+ * pass adds the four overlapping windows in the reference's window order.  Parity: bit-exact against the project's restatement of microfft's
+ * rfft_N / inverse FFT (fundsp_amd/csrc/fd_resynth.hpp; microfft's own butterflies are not pinned: its source is not in the reference tree).
+ * Latency N samples; a pass-through returns the input delayed by N from sample 2N on.  No process override (FDSP_MODE_PROCESS ==
+ * FDSP_MODE_TICK).  set_sample_rate moves frequency() only and keeps every state; reset starts the four windows over; clone continues
+ * where the source stands.  Every buffer a launch uses is allocated at creation (the frame ring takes max(256 MiB, 8 x instances x
+ * outputs x N x 4 bytes)), so a launch may be captured on a caller's stream and replayed: the sample counter, the bin spacing of
+ * frequency() and the tables live on the device, so a replay moves on and follows set_sample_rate / set_band / set_gain.
+ * fdsp_bank_set_bus, fdsp_bank_process_mix, slots, rings and events answer FDSP_ENOTSUP; invalid specs FDSP_EINVAL before anything is
+ * allocated or launched. */
+enum { FDSP_RESYNTH_PASS = 0, FDSP_RESYNTH_BAND = 1, FDSP_RESYNTH_GAIN = 2 };
+typedef struct fdsp_resynth_spec {
+    int window_length, inputs, outputs;
+    int processor;                      /* FDSP_RESYNTH_PASS | _BAND | _GAIN */
+    int source[8];                      /* input channel of each output, -1 = silent */
+    int per_instance;                   /* 0: tables [outputs]; 1: [instances][outputs] */
+    int flush_denormals;                /* 1: f32 denormals flushed (a Feedback node in front) */
+    const float *lo_hz, *hi_hz;         /* FDSP_RESYNTH_BAND: [..][outputs] */
+    const float* gain;                  /* FDSP_RESYNTH_GAIN: [..][outputs][window_length / 2 + 1] */
+} fdsp_resynth_spec;
+int fdsp_resynth_create(size_t instances, const fdsp_resynth_spec* spec, fdsp_bank** out);
+int fdsp_resynth_create_on(int device, size_t instances, const fdsp_resynth_spec* spec, fdsp_bank** out);
+/* Replace table rows first .. first+count-1 between launches (rows are instances with per_instance, else the single row 0), with the
+ * ordering of fdsp_bank_set_param: the new values apply from the next launch; the host array is borrowed for the call only.
+ * set_band takes [count][outputs][2] (lo, hi) in Hz, set_gain [count][outputs][window_length / 2 + 1]. */
+int fdsp_resynth_set_band(fdsp_bank* bank, const float* h_lo_hi, size_t first, size_t count);
+int fdsp_resynth_set_gain(fdsp_bank* bank, const float* h_gain, size_t first, size_t count);
+/* Host only, no device: the bank's tables for window_length N -- hann[N] = 0.5 + 0.5 * cosf(((i - N/2) as f32 * TAU) / N as f32) and
+ * twiddles[N/2][2] = (cos, -sin)(2 pi j / N) computed in double and rounded to f32.  Either pointer may be NULL. */
+int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles);
 /* reverb3_stereo(time, diffusion, lowpole_hz(cutoff)) (src/prelude.rs:1858-1871): the allpass-loop reverb Reverb<F> of src/reverb.rs:152-279
  * with the documented loop filter, a one-pole lowpass (src/filter.rs:19-66).  `instances` independent reverbs, 2 inputs / 2 outputs each, all
  * with the same parameters.  One wave per instance, one lane per FRAME of a 64-sample block: all 76 delay lines of the structure (4 input

@@ -579,6 +579,13 @@ class Bank {
         b.kind_ = "fdn_network";
         return b;
     }
+    // resynth::<I, O, _>(window_length, closure) with a stock closure (fdsp_resynth_create, include/fundsp_hip.h): batched FFT frames
+    static Bank resynth(size_t instances, const fdsp_resynth_spec& spec) {
+        Bank b;
+        check(fdsp_resynth_create(instances, &spec, &b.h_));
+        b.kind_ = "resynth";
+        return b;
+    }
     Bank(Bank&& o) noexcept { *this = std::move(o); }
     Bank& operator=(Bank&& o) noexcept {
         if (this != &o) {

@@ -51,6 +51,23 @@ pub mod ffi {
         pub gain: *const f32,
         pub line_gain: *const f32,
     }
+    /// `struct fdsp_resynth_spec` (fdsp_resynth_create): a resynthesizer with a stock processing closure
+    #[repr(C)]
+    pub struct FdspResynthSpec {
+        pub window_length: c_int,
+        pub inputs: c_int,
+        pub outputs: c_int,
+        pub processor: c_int,
+        pub source: [c_int; 8],
+        pub per_instance: c_int,
+        pub flush_denormals: c_int,
+        pub lo_hz: *const f32,
+        pub hi_hz: *const f32,
+        pub gain: *const f32,
+    }
+    pub const FDSP_RESYNTH_PASS: c_int = 0;
+    pub const FDSP_RESYNTH_BAND: c_int = 1;
+    pub const FDSP_RESYNTH_GAIN: c_int = 2;
     pub const FDSP_FDN_FILTER_NONE: c_int = 0;
     pub const FDSP_FDN_FILTER_LOWPOLE: c_int = 1;
     pub const FDSP_FDN_FILTER_SVF: c_int = 2;
@@ -79,6 +96,9 @@ pub mod ffi {
         pub fn fdsp_reverb3_stereo_svf_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, svf_mode: c_int, cutoff_hz: f32, q: f32, gain: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_create_on(device: c_int, instances: usize, lines: c_int, delays: *const f64, taps: c_int, weights: *const f32, inputs: c_int, outputs: c_int, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_network_create_on(device: c_int, instances: usize, net: *const FdspFdnNetwork, sample_rate: f64, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_resynth_create_on(device: c_int, instances: usize, spec: *const FdspResynthSpec, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_resynth_set_band(bank: *mut FdspBank, lo_hi: *const f32, first: usize, count: usize) -> c_int;
+        pub fn fdsp_resynth_set_gain(bank: *mut FdspBank, gain: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_destroy(bank: *mut FdspBank);
         pub fn fdsp_bank_clone(bank: *const FdspBank, out: *mut *mut FdspBank) -> c_int; // Clone: slots, rings, sample rate, options, events
         pub fn fdsp_bank_inputs(bank: *const FdspBank) -> c_int;
@@ -275,6 +295,44 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_fdn_network_create_on(device as c_int, instances, &c, sample_rate, &mut bank) })?;
         Self::adopt(bank, "fdn_network", instances)
+    }
+
+    /// `instances` x `resynth::<I, O, _>(window_length, closure)` (src/resynth.rs) with a stock closure (include/fundsp_hip.h
+    /// `fdsp_resynth_spec`): `processor` = FDSP_RESYNTH_PASS (`fft.set(o, i, fft.at(source[o], i))`), FDSP_RESYNTH_BAND (the same where
+    /// lo_hz[o] <= fft.frequency(i) <= hi_hz[o]) or FDSP_RESYNTH_GAIN (times gain[o][i], window_length / 2 + 1 bins per output).  `source[o]`:
+    /// the input channel of output o, -1 = silent.  Tables hold one row, or with `per_instance` one per instance.  `flush_denormals` when a
+    /// Feedback node was constructed in front of the node (the reference then renders it flushed).  Source only: no Rust toolchain has built it.
+    pub fn resynth(instances: usize, window_length: usize, source: &[i32], processor: i32, per_instance: bool, lo_hi: Option<(&[f32], &[f32])>,
+                   gain: Option<&[f32]>, inputs: usize, flush_denormals: bool, device: i32) -> Result<Self, String> {
+        if source.is_empty() || source.len() > 8 {
+            return Err("HipBank::resynth: one source entry per output, 1 .. 8 outputs".into());
+        }
+        let rows = if per_instance { instances } else { 1 };
+        let outputs = source.len();
+        if lo_hi.map_or(false, |(l, h)| l.len() != rows * outputs || h.len() != rows * outputs)
+            || gain.map_or(false, |g| g.len() != rows * outputs * (window_length / 2 + 1))
+        {
+            return Err("HipBank::resynth: tables need one row (per instance with per_instance) of one entry per output (gain: per bin)".into());
+        }
+        let mut src = [-1 as c_int; 8];
+        for (o, &s) in source.iter().enumerate() {
+            src[o] = s as c_int;
+        }
+        let spec = FdspResynthSpec {
+            window_length: window_length as c_int,
+            inputs: inputs as c_int,
+            outputs: outputs as c_int,
+            processor: processor as c_int,
+            source: src,
+            per_instance: per_instance as c_int,
+            flush_denormals: flush_denormals as c_int,
+            lo_hz: lo_hi.map_or(core::ptr::null(), |(l, _)| l.as_ptr()),
+            hi_hz: lo_hi.map_or(core::ptr::null(), |(_, h)| h.as_ptr()),
+            gain: gain.map_or(core::ptr::null(), |g| g.as_ptr()),
+        };
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_resynth_create_on(device as c_int, instances, &spec, &mut bank) })?;
+        Self::adopt(bank, "resynth", instances)
     }
 
     fn adopt(bank: *mut FdspBank, kind: &str, voices: usize) -> Result<Self, String> {

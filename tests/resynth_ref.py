@@ -1,0 +1,183 @@
+"""numpy restatement of the resynthesizer banks' contract (fundsp_amd/csrc/fd_resynth.hpp), for the tests.
+
+resynth::<I, O, _>(N, closure) (resynth.rs:216-372) in explicit f32 steps, vectorised over instances and frames: the Hann window, the four
+windows a hop H = N/4 apart, the project's restatement of microfft's rfft_N (pack z[m] = x[2m] + i x[2m+1], the N/2-point radix-2 complex
+FFT of cfft_inplace, the split), the stock processors, fix_negative, the inverse FFT (reverse elements 1 .. N-1, forward, / N), and the
+overlap-add in WINDOW order.  Every operation is one f32 rounding in the order the header states; `ftz=True` flushes every operand and result
+below 2^-126 to a zero of the same sign, as a build with f32 denormals flushed does.
+"""
+import math
+
+import numpy as np
+
+f32 = np.float32
+_TINY = f32(2.0 ** -126)
+TAU = f32(6.28318548202514648)   # core::f32::consts::TAU
+PROCESSORS = {"pass": 0, "band": 1, "gain": 2}
+
+
+class _Ops:
+    def __init__(self, ftz):
+        self.ftz = ftz
+
+    def fl(self, x):
+        x = np.asarray(x, dtype=f32)
+        if not self.ftz:
+            return x
+        return np.where(np.abs(x) < _TINY, np.copysign(f32(0.0), x), x).astype(f32)
+
+    def add(self, a, b): return self.fl(self.fl(a) + self.fl(b))
+    def sub(self, a, b): return self.fl(self.fl(a) - self.fl(b))
+    def mul(self, a, b): return self.fl(self.fl(a) * self.fl(b))
+
+
+def tables(N, cosf):
+    """hann[N] and twiddles[N/2, 2] = (cos, -sin)(2 pi j / N) (double, rounded to f32); `cosf` is musl's f32 cosine (the oracle's)."""
+    hann = np.empty(N, dtype=f32)
+    for i in range(N):
+        a = f32(f32(f32(i - N // 2) * TAU) / f32(N))
+        hann[i] = f32(0.5) + f32(0.5) * f32(cosf(a))
+    tw = np.empty((N // 2, 2), dtype=f32)
+    for j in range(N // 2):
+        ang = 6.283185307179586476925286766559 * j / N
+        tw[j, 0] = f32(math.cos(ang))
+        tw[j, 1] = f32(-math.sin(ang))
+    return hann, tw
+
+
+def _bitrev(n):
+    bits = n.bit_length() - 1
+    return np.array([int(format(i, f"0{bits}b")[::-1], 2) if bits else 0 for i in range(n)], dtype=np.int64)
+
+
+def cfft(re, im, tw, N, op):
+    """cfft_inplace over the last axis (n points, n | N): bit-reversed order, radix-2 stages, twiddle k * N / span of the N table."""
+    n = re.shape[-1]
+    p = _bitrev(n)
+    re, im = re[..., p], im[..., p]
+    lead = re.shape[:-1]
+    span = 2
+    while span <= n:
+        half = span // 2
+        k = np.arange(half) * (N // span)
+        wr, wi = tw[k, 0], tw[k, 1]
+        r = re.reshape(lead + (n // span, span))
+        i = im.reshape(lead + (n // span, span))
+        pr, pi, qr, qi = r[..., :half], i[..., :half], r[..., half:], i[..., half:]
+        yr = op.sub(op.mul(wr, qr), op.mul(wi, qi))
+        yi = op.add(op.mul(wr, qi), op.mul(wi, qr))
+        re = np.concatenate([op.add(pr, yr), op.sub(pr, yr)], axis=-1).reshape(lead + (n,))
+        im = np.concatenate([op.add(pi, yi), op.sub(pi, yi)], axis=-1).reshape(lead + (n,))
+        span *= 2
+    return re, im
+
+
+def rfft(xw, tw, op):
+    """real_fft + fix_nyquist of windowed frames [..., N] -> bins 0 .. N/2 as (re, im) [..., N/2 + 1]."""
+    N = xw.shape[-1]
+    NH = N // 2
+    zr, zi = cfft(np.ascontiguousarray(xw[..., 0::2]), np.ascontiguousarray(xw[..., 1::2]), tw, N, op)
+    Xr = np.zeros(xw.shape[:-1] + (NH + 1,), dtype=f32)
+    Xi = np.zeros_like(Xr)
+    Xr[..., 0] = op.add(zr[..., 0], zi[..., 0])
+    Xr[..., NH] = op.sub(zr[..., 0], zi[..., 0])
+    k = np.arange(1, NH)
+    Ar, Ai = zr[..., k], zi[..., k]
+    Br, Bi = zr[..., NH - k], -zi[..., NH - k]
+    h = f32(0.5)
+    Er, Ei = op.mul(h, op.add(Ar, Br)), op.mul(h, op.add(Ai, Bi))
+    Dr, Di = op.mul(h, op.sub(Ar, Br)), op.mul(h, op.sub(Ai, Bi))
+    qr, qi = Di, -Dr
+    wr, wi = tw[k, 0], tw[k, 1]
+    Xr[..., k] = op.add(Er, op.sub(op.mul(wr, qr), op.mul(wi, qi)))
+    Xi[..., k] = op.add(Ei, op.add(op.mul(wr, qi), op.mul(wi, qr)))
+    return Xr, Xi
+
+
+def irfft_re(Yr, Yi, tw, op):
+    """fix_negative + inverse_fft of output bins [..., N/2 + 1]; the real parts / N [..., N]."""
+    NH = Yr.shape[-1] - 1
+    N = 2 * NH
+    Vr = np.empty(Yr.shape[:-1] + (N,), dtype=f32)
+    Vi = np.empty_like(Vr)
+    # after the reversal of elements 1 .. N-1: V[0] = Y[0], V[j] = conj(Y[j]) (1 <= j < N/2), V[j] = Y[N-j] (j >= N/2)
+    Vr[..., 0], Vi[..., 0] = Yr[..., 0], Yi[..., 0]
+    j = np.arange(1, NH)
+    Vr[..., j], Vi[..., j] = Yr[..., j], -Yi[..., j]
+    j = np.arange(NH, N)
+    Vr[..., j], Vi[..., j] = Yr[..., N - j], Yi[..., N - j]
+    r, _ = cfft(Vr, Vi, tw, N, op)
+    return op.fl(r / f32(N))
+
+
+def render(x, N, outputs=1, processor="pass", source=None, band=None, gain=None, sample_rate=44100.0, changes=(), ftz=False, cosf=None,
+           tabs=None):
+    """y [V, O, T] of V fresh resynthesizers fed x [V, I, T].
+
+    band: (lo, hi) | [O, 2] | [V, O, 2]; gain: [bins] | [O, bins] | [V, O, bins].  `changes`: [(S, dict(sample_rate=.., band=.., gain=..))]
+    -- a setter called before sample S: it applies to the frames transformed at sample counts kH > S (the launches from S on)."""
+    x = np.asarray(x, dtype=f32)
+    V, I, T = x.shape
+    O, H, NH = int(outputs), N // 4, N // 2
+    src = [o % I for o in range(O)] if source is None else list(source)
+    op = _Ops(ftz)
+    hann, tw = tabs if tabs is not None else tables(N, cosf)
+    hz = (hann * f32(f32(2.0) / f32(3.0))).astype(f32)
+    proc = PROCESSORS[processor]
+
+    def params(p):
+        sr = f32(p["sample_rate"])
+        b = None if p.get("band") is None else np.broadcast_to(np.asarray(p["band"], dtype=f32), (V, O, 2))
+        g = None if p.get("gain") is None else np.broadcast_to(np.asarray(p["gain"], dtype=f32), (V, O, NH + 1))
+        return f32(sr / f32(N)), b, g
+
+    segs = [(-1, dict(sample_rate=sample_rate, band=band, gain=gain))]
+    for S, upd in sorted(changes, key=lambda c: c[0]):
+        p = dict(segs[-1][1])
+        p.update(upd)
+        segs.append((S, p))
+    ks = np.arange(4, T // H + 1)          # frames transformed at sample counts kH <= T that some output sample reads (kH < T), k >= 4
+    ks = ks[ks * H < T]
+    frames = np.zeros((V, len(ks), O, N), dtype=f32)
+    xfr = {}
+    for si, (S, p) in enumerate(segs):
+        S_next = segs[si + 1][0] if si + 1 < len(segs) else None
+        sel = np.nonzero((ks * H > S) & ((ks * H <= S_next) if S_next is not None else True))[0]
+        if len(sel) == 0:
+            continue
+        fstep, b, g = params(p)
+        idx = (ks[sel] * H - N)[:, None] + np.arange(N)[None, :]      # [K, N]
+        for o in range(O):
+            s = src[o]
+            if s < 0:
+                Yr = np.zeros((V, len(sel), NH + 1), dtype=f32)
+                Yi = np.zeros_like(Yr)
+            else:
+                key = (si, s)
+                if key not in xfr:
+                    xfr[key] = rfft(op.mul(x[:, s, :][:, idx], hann), tw, op)
+                Xr, Xi = xfr[key]
+                if proc == 0:
+                    Yr, Yi = Xr, Xi
+                elif proc == 1:
+                    fr = (fstep * np.arange(NH + 1).astype(f32)).astype(f32)
+                    lo, hi = b[:, o, 0][:, None, None], b[:, o, 1][:, None, None]
+                    m = (lo <= fr[None, None, :]) & (fr[None, None, :] <= hi)
+                    Yr, Yi = np.where(m, Xr, f32(0.0)), np.where(m, Xi, f32(0.0))
+                else:
+                    gg = g[:, o, :][:, None, :]
+                    Yr, Yi = op.mul(Xr, gg), op.mul(Xi, gg)
+            frames[:, sel, o, :] = irfft_re(Yr.astype(f32), Yi.astype(f32), tw, op)
+    # overlap-add: y[t] = (((0 + a_w0) + a_w1) + a_w2) + a_w3, frame k in window (-k) mod 4, read at p = t - kH
+    y = np.zeros((V, O, T), dtype=f32)
+    t = np.arange(T)
+    m = t // H
+    for w in range(4):
+        k = m - ((m + w) % 4)
+        live = k >= 4
+        kk, tt = k[live], t[live]
+        pos = tt - kk * H
+        fi = kk - 4
+        a = op.mul(frames[:, fi, :, pos], hz[pos][:, None, None])   # [n, V, O] (the two index arrays go first)
+        y[:, :, live] = op.add(y[:, :, live], np.transpose(a, (1, 2, 0)))
+    return y

@@ -1,0 +1,298 @@
+"""GPU parity of the resynthesizer banks (fdsp_resynth_create, Bank.resynth, resynth(..) in Bank.from_graph): every output bit-exact against
+the numpy restatement tests/resynth_ref.py -- window lengths 4 .. 8192, 1->1 / 2->2 / 1->2 / 2->1, the three stock processors, shared and
+per-instance tables, 1 / 3 / 2048 instances, ragged launches, both layouts and executors, reset, clone, set_sample_rate, set_gain, a captured
+launch replayed, subnormal inputs through the IEEE and flush-to-zero builds, the criterion chain noise() >> resynth(1024), and invalid specs."""
+import functools
+
+import numpy as np
+import pytest
+
+import oracle as O
+import resynth_ref as R
+from fundsp_amd import LAYOUT_PLANAR, LAYOUT_VOICE_MINOR, MODE_PROCESS, MODE_TICK
+from fundsp_amd import graph as GR
+from test_gpu_parity import assert_bit_equal, oracle_render, run_bank
+
+pytestmark = pytest.mark.gpu
+
+
+@functools.lru_cache(maxsize=None)
+def tabs(N):
+    return R.tables(N, O.lib().o_math_cosf)
+
+
+def signal(V, I, T, seed):
+    return np.random.default_rng(seed).uniform(-1.0, 1.0, (V, I, T)).astype(np.float32)
+
+
+def tables_for(proc, N, O_, V=None, seed=0):
+    rng = np.random.default_rng(seed + 100)
+    nb = N // 2 + 1
+    if proc == "band":
+        lo = rng.uniform(0.0, 8000.0, (O_,) if V is None else (V, O_)).astype(np.float32)
+        return dict(band=np.stack([lo, lo + np.float32(6000.0)], axis=-1).astype(np.float32))
+    if proc == "gain":
+        return dict(gain=rng.uniform(-1.5, 1.5, (O_, nb) if V is None else (V, O_, nb)).astype(np.float32))
+    return {}
+
+
+def check(bank, x, want, what, layout=LAYOUT_VOICE_MINOR, mode=MODE_PROCESS):
+    got = run_bank(bank, x, x.shape[2], layout, mode)
+    for v in range(got.shape[0]):
+        assert_bit_equal(got[v], want[v], f"{what}, instance {v}")
+    return got
+
+
+IO = [(1, 1), (2, 2), (1, 2), (2, 1)]
+SOURCES = {(1, 1): [0], (2, 2): [1, 0], (1, 2): [0, 0], (2, 1): [1]}
+
+
+@pytest.mark.parametrize("N", [4, 32, 256, 1024, 4096, 8192])
+@pytest.mark.parametrize("io", IO)
+@pytest.mark.parametrize("proc", ["pass", "band", "gain"])
+def test_matrix_bit_exact(gpu, N, io, proc):
+    import fundsp_amd as F
+
+    I, O_ = io
+    V, T = 3, 3 * N + 7
+    x = signal(V, I, T, seed=N + 10 * I + O_)
+    t = tables_for(proc, N, O_)
+    b = F.Bank.resynth(V, N, I, O_, processor=proc, source=SOURCES[io], **t)
+    want = R.render(x, N, O_, proc, SOURCES[io], tabs=tabs(N), **t)
+    check(b, x, want, f"N={N} {I}->{O_} {proc}")
+
+
+def test_per_instance_tables_many_instances(gpu):
+    import fundsp_amd as F
+
+    N, V, T = 256, 2048, 1000
+    for proc in ("band", "gain"):
+        x = signal(V, 2, T, seed=5)
+        t = tables_for(proc, N, 2, V=V, seed=7)
+        b = F.Bank.resynth(V, N, 2, 2, processor=proc, source=[1, -1] if proc == "band" else [0, 1], **t)
+        want = R.render(x, N, 2, proc, [1, -1] if proc == "band" else [0, 1], tabs=tabs(N), **t)
+        got = run_bank(b, x, T, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{proc}: {np.argwhere(got != want)[:4]}"
+        if proc == "band":
+            assert not got[:, 1].any(), "source -1: a silent output"
+
+
+@pytest.mark.parametrize("layout", [LAYOUT_VOICE_MINOR, LAYOUT_PLANAR])
+def test_ragged_launches_layouts_and_executors(gpu, layout):
+    import fundsp_amd as F
+
+    N = 32
+    H = N // 4
+    lens = [1, 63, 64, H - 1, N + 5, 3 * N + 7]
+    T = sum(lens)
+    V = 3
+    x = signal(V, 2, T, seed=9)
+    want = R.render(x, N, 2, "gain", [0, 1], tabs=tabs(N), **tables_for("gain", N, 2))
+    for mode in (MODE_PROCESS, MODE_TICK):
+        b = F.Bank.resynth(V, N, 2, 2, processor="gain", source=[0, 1], **tables_for("gain", N, 2))
+        parts, t0 = [], 0
+        for n in lens:
+            parts.append(run_bank(b, np.ascontiguousarray(x[:, :, t0:t0 + n]), n, layout, mode))
+            t0 += n
+        got = np.concatenate(parts, axis=2)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"mode {mode}: ragged launches differ from the restatement"
+
+
+def test_long_launch_spans_several_chunks(gpu):
+    """2048 instances of N = 1024 take a frame ring of 32 slots (256 MiB), so 20 000 frames are rendered in 3 chunks: the same bits as the restatement"""
+    import fundsp_amd as F
+
+    N, V, T = 1024, 2048, 20000
+    x = signal(V, 1, T, seed=3)
+    b = F.Bank.resynth(V, N)
+    got = run_bank(b, x, T, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    for v in (0, 777, 2047):
+        want = R.render(x[v:v + 1], N, tabs=tabs(N))
+        assert_bit_equal(got[v], want[0], f"instance {v}")
+
+
+def test_lifecycle_reset_clone_sample_rate_set_gain(gpu):
+    import fundsp_amd as F
+
+    N, V = 64, 3
+    T1, T2 = 300, 400
+    x = signal(V, 1, T1 + T2, seed=11)
+    x1, x2 = np.ascontiguousarray(x[:, :, :T1]), np.ascontiguousarray(x[:, :, T1:])
+    # reset: a second run from the start renders the first run's samples
+    b = F.Bank.resynth(V, N, processor="band", band=(1000.0, 9000.0))
+    a = run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    b.reset()
+    a2 = run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    assert np.array_equal(a.view(np.uint32), a2.view(np.uint32))
+    # set_sample_rate mid-stream: the BAND bins move, the windows keep their state; clone mid-stream continues the same
+    b.reset()
+    run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    c = b.clone()
+    b.set_sample_rate(22050.0)
+    c.set_sample_rate(22050.0)
+    want = R.render(x, N, processor="band", band=(1000.0, 9000.0), changes=[(T1, dict(sample_rate=22050.0))], tabs=tabs(N))
+    for bank, what in ((b, "set_sample_rate"), (c, "clone, then set_sample_rate")):
+        got = run_bank(bank, x2, T2, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+        assert np.array_equal(got.view(np.uint32), want[:, :, T1:].view(np.uint32)), what
+    # set_gain between launches
+    g1, g2 = tables_for("gain", N, 1, seed=1)["gain"], tables_for("gain", N, 1, seed=2)["gain"]
+    b = F.Bank.resynth(V, N, processor="gain", gain=g1)
+    run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    b.set_gain(g2)
+    got = run_bank(b, x2, T2, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    want = R.render(x, N, processor="gain", gain=g1, changes=[(T1, dict(gain=g2))], tabs=tabs(N))
+    assert np.array_equal(got.view(np.uint32), want[:, :, T1:].view(np.uint32)), "set_gain between launches"
+
+
+def test_one_row_setters_on_a_two_output_bank(gpu):
+    """set_gain with one [bins] row and set_band with one (lo, hi) pair on a 2 -> 2 bank: broadcast over both outputs, as the constructor does"""
+    import fundsp_amd as F
+
+    N, V, T1, T2 = 64, 3, 300, 400
+    x = signal(V, 2, T1 + T2, seed=23)
+    x1, x2 = np.ascontiguousarray(x[:, :, :T1]), np.ascontiguousarray(x[:, :, T1:])
+    g1 = tables_for("gain", N, 2, seed=3)["gain"]
+    g2 = tables_for("gain", N, 1, seed=4)["gain"][0]   # [bins]
+    b = F.Bank.resynth(V, N, 2, 2, processor="gain", source=[1, 0], gain=g1)
+    run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    b.set_gain(g2)
+    got = run_bank(b, x2, T2, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    want = R.render(x, N, 2, "gain", [1, 0], gain=g1, changes=[(T1, dict(gain=g2))], tabs=tabs(N))
+    assert np.array_equal(got.view(np.uint32), want[:, :, T1:].view(np.uint32)), "set_gain([bins]) on 2 outputs"
+    with pytest.raises(ValueError):
+        b.set_gain(np.ones(N // 2, np.float32))
+    with pytest.raises(ValueError):
+        b.set_gain(np.ones((3, N // 2 + 1), np.float32))
+    b = F.Bank.resynth(V, N, 2, 2, processor="band", source=[0, 1], band=[(0.0, 5000.0), (3000.0, 20000.0)])
+    run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    b.set_band((1500.0, 7000.0))
+    got = run_bank(b, x2, T2, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    want = R.render(x, N, 2, "band", [0, 1], band=[(0.0, 5000.0), (3000.0, 20000.0)], changes=[(T1, dict(band=(1500.0, 7000.0)))], tabs=tabs(N))
+    assert np.array_equal(got.view(np.uint32), want[:, :, T1:].view(np.uint32)), "set_band((lo, hi)) on 2 outputs"
+
+
+def test_captured_launch_follows_set_sample_rate(gpu):
+    """The bin spacing of frequency() lives in device memory: a captured BAND launch replayed after set_sample_rate uses the new rate"""
+    import torch
+
+    import fundsp_amd as F
+
+    N, V, T = 32, 3, 48
+    x = signal(V, 1, 3 * T, seed=29)
+    b = F.Bank.resynth(V, N, processor="band", band=(2000.0, 9000.0))
+    inp = torch.zeros((1, T, V), dtype=torch.float32, device="cuda")
+    out = torch.zeros((1, T, V), dtype=torch.float32, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        b.process(T, inp, out)
+    parts = []
+    for r in range(3):
+        if r == 2:
+            b.set_sample_rate(22050.0)
+        inp.copy_(torch.from_numpy(np.ascontiguousarray(x[:, :, T * r:T * (r + 1)].transpose(1, 2, 0))))
+        g.replay()
+        torch.cuda.synchronize()
+        parts.append(out.cpu().numpy().transpose(2, 0, 1).copy())
+    got = np.concatenate(parts, axis=2)
+    want = R.render(x, N, processor="band", band=(2000.0, 9000.0), changes=[(2 * T, dict(sample_rate=22050.0))], tabs=tabs(N))
+    old = R.render(x, N, processor="band", band=(2000.0, 9000.0), tabs=tabs(N))
+    assert not np.array_equal(want, old), "the change of rate moves bins in or out of the band"
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "replay after set_sample_rate"
+
+
+def test_captured_launch_replays(gpu):
+    """A launch captured on a caller's stream replays with the state moving on (the sample counter lives on the device)"""
+    import torch
+
+    import fundsp_amd as F
+
+    N, V, T = 32, 5, 40
+    reps = 4
+    x = signal(V, 1, T * (reps + 1), seed=13)
+    b = F.Bank.resynth(V, N)
+    head = run_bank(b, np.ascontiguousarray(x[:, :, :T]), T, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    inp = torch.zeros((1, T, V), dtype=torch.float32, device="cuda")
+    out = torch.zeros((1, T, V), dtype=torch.float32, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        b.process(T, inp, out)
+    parts = [head]
+    for r in range(reps):
+        inp.copy_(torch.from_numpy(np.ascontiguousarray(x[:, :, T * (r + 1):T * (r + 2)].transpose(1, 2, 0))))
+        g.replay()
+        torch.cuda.synchronize()
+        parts.append(out.cpu().numpy().transpose(2, 0, 1).copy())
+    got = np.concatenate(parts, axis=2)
+    want = R.render(x, N, tabs=tabs(N))
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "captured launch, replayed"
+
+
+def test_subnormal_inputs_ieee_and_flushed(gpu):
+    import fundsp_amd as F
+
+    N, V, T = 32, 2, 200
+    x = signal(V, 1, T, seed=17)
+    x[0] *= np.float32(2.0 ** -130)   # instance 0: subnormal input samples
+    x[1] *= np.float32(2.0 ** -118)   # instance 1: normal samples whose window products and frames / N fall into the denormal range
+    assert np.any((np.abs(x) < np.float32(2.0 ** -126)) & (x != 0))
+    for ftz in (False, True):
+        b = F.Bank.resynth(V, N, flush_denormals=ftz)
+        want = R.render(x, N, tabs=tabs(N), ftz=ftz)
+        got = run_bank(b, x, T, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"ftz={ftz}"
+        if not ftz:
+            assert np.any(got != 0), "IEEE build: the denormal input comes through"
+        else:
+            assert not np.any(got[0]), "flushed build: a denormal input reads as zero"
+
+
+def test_criterion_chain_noise_into_resynth(gpu):
+    """noise() >> resynth::<U1, U1, _>(1024, pass) at 44.1 kHz for 44 100 frames (benches/benchmark.rs:12-23): a Chain whose front is seeded
+    from the Pipe's construction hash, into which Resynth::ID = 80 enters; and the 2 -> 2 form (noise() | noise()) >> resynth"""
+    import torch
+
+    import fundsp_amd as F
+    from fundsp_amd.bank import PIPE_ID, atto, probe_hash
+
+    T = 44100
+    g = GR.noise() >> GR.resynth(1024)
+    h0 = atto(atto(np.uint64(PIPE_ID), PIPE_ID), 20)   # Pipe::new: ping(true, AttoHash::new(Pipe::ID)); Noise::ID = 20, Resynth::ID = 80
+    assert probe_hash(g) == int(atto(h0, 80))
+    g2 = (GR.noise() | GR.noise()) >> GR.resynth(1024, 2, 2)
+    for graph, I, mk in ((g, 1, lambda: O.noise()), (g2, 2, lambda: O.noise() | O.noise())):
+        ch = F.Bank.from_graph(graph, 2)
+        assert isinstance(ch, F.Chain) and ch.effect.kind == "resynth"
+        out = ch.process(T)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy().transpose(2, 0, 1)
+        n = mk()
+        n.set_seed(int(atto(np.uint64(probe_hash(graph)), PIPE_ID)))
+        x = oracle_render(n, None, T, MODE_PROCESS)
+        want = R.render(x[None], 1024, I, tabs=tabs(1024))[0]
+        for v in range(2):
+            assert_bit_equal(got[v], want, f"{I}->{I} chain, instance {v}")
+
+
+def test_invalid_specs_and_unsupported_calls(gpu):
+    import ctypes as C
+
+    import fundsp_amd as F
+    from fundsp_amd import _lib
+
+    L = _lib.lib()
+    for kw, msg in ((dict(window_length=1000), b"power of two"), (dict(inputs=9), b"inputs and outputs"), (dict(source0=3), b"source[0]"),
+                    (dict(processor=7), b"processor")):
+        s = _lib.ResynthSpec()
+        s.window_length, s.inputs, s.outputs, s.processor = kw.get("window_length", 64), kw.get("inputs", 1), 1, kw.get("processor", 0)
+        s.source[0] = kw.get("source0", 0)
+        h = C.c_void_p()
+        assert L.fdsp_resynth_create(4, C.byref(s), C.byref(h)) == _lib.EINVAL and not h.value
+        assert msg in L.fdsp_last_error(), L.fdsp_last_error()
+    b = F.Bank.resynth(2, 64)
+    assert L.fdsp_bank_set_bus(b._h, _lib.BUS_WET, 0.5, 1.0) == _lib.ENOTSUP
+    out = C.c_void_p()
+    assert L.fdsp_bank_process_mix(b._h, 64, None, out, _lib.MIX_SUM, 0, None) == _lib.ENOTSUP
