@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -13,10 +15,7 @@
 
 #include "../../include/fundsp_hip.h"
 #include "fd_engine.hpp"
-#include "fd_fdn.hpp"
-#include "fd_reverb3.hpp"
-#include "fd_resynth.hpp"
-#include "fd_fdnx.hpp"
+#include "fd_fxbank.hpp"
 #include "fd_opts.hpp"
 
 namespace {
@@ -389,41 +388,8 @@ int build_default_table_set(int set) {
 
 }  // namespace
 
-struct FdnBank {  // reverb_stereo / reverb4_stereo banks (fd_fdn.hip): rings + per-line state instead of the slot SoA
-    int kind = 0;  // 0 = reverb_stereo(room, time, damping), 1 = reverb4_stereo(room, time), 2 = the generic network (fdsp_fdn_create: desc),
-                   // 3 = reverb3_stereo(time, diffusion = `damping`, lowpole_hz(cutoff)): the allpass loop of fd_reverb3.hip (c3 / st3; `c` only carries nin / nout),
-                   // 4 = a filtered / per-instance network (fdsp_fdn_network_create: xdesc, cx / sx / xtab of fd_fdnx.hip; `c` only carries nin / nout)
-    double room = 0.0, time = 0.0, damping = 0.0;
-    fd::Rv3Filter flt;      // kind 3: the loop filter
-    fd::Rv3Const c3;
-    fd::Rv3State st3{};
-    fd::FdnDesc desc;
-    fd::FdnConst c;
-    fd::FdnState st;
-    fd::FdnxDesc xdesc;
-    fd::FdnxConst cx{};
-    fd::FdnxState sx{};
-    fd::FdnxInst* xtab = nullptr;   // kind 4: the parameter table at the bank's rate (one entry, or one per instance)
-    fd::FdnBus bus;           // fdsp_bank_set_bus: wet * node [& dry * multipass()] folded into the render kernels' epilogue
-    float* stage = nullptr;   // planar staging of voice-minor launches: [V][inputs][frames] | [V][outputs][frames] (fd_fdn.hip "voice-minor I/O")
-    size_t stage_n = 0;
-};
-
-struct RsBank {  // resynthesizer banks (fdsp_resynth_create, fd_resynth.hpp): tables, frame ring, input ring, device sample counter
-    fd::RsConst c{};
-    fd::RsState st{};
-    int ftz = 0;              // 1: the flush-to-zero instantiation (a Feedback node in front)
-    int per_instance = 0;
-    float2* tw = nullptr;
-    float* hann = nullptr;
-    float* hz = nullptr;
-    float2* band = nullptr;   // [rows][O] (lo, hi)
-    float* gain = nullptr;    // [rows][O][N/2 + 1]
-};
-
 struct fdsp_bank {
-    FdnBank* fdn = nullptr;
-    RsBank* rs = nullptr;
+    std::unique_ptr<fd::FxBank> fx;  // an effect bank (fd_fxbank.hpp): reverb, network or resynthesizer instead of a voice graph of slots
     float* ring = nullptr;       // delay-ring memory [ring node][position][voice] for kinds with Delay / Tap nodes
     uint32_t ring_cap = 0;       // positions per ring node
     const fd::KindOps* ops = nullptr;
@@ -901,6 +867,27 @@ int fdsp_device_count(void) {
 
 int fdsp_bank_device(const fdsp_bank* b) { return b ? b->device : FDSP_EINVAL; }
 
+// The part of every bank constructor that is not the bank's content: the device (-1: the current one), the handle with one instance per
+// voice, its stream and event pair
+static int new_bank(int device, size_t voices, fdsp_bank** out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(FDSP_EDEVICE, "no HIP device available: the fundsp_hip engine has no CPU fallback");
+    if (device < 0) device = current_device();
+    if (device < 0 || device >= ndev || device >= MAX_DEVICES) return fail(FDSP_EINVAL, "device index out of range");
+    DeviceGuard guard(device);
+    fdsp_bank* b = new fdsp_bank();
+    b->device = device;
+    b->V = b->stride = voices;
+    b->sr = FDSP_DEFAULT_SR;
+    if (hipStreamCreate(&b->stream) != hipSuccess || hipEventCreate(&b->e0) != hipSuccess || hipEventCreate(&b->e1) != hipSuccess) {
+        fdsp_bank_destroy(b);  // frees whatever of {stream, e0, e1} exists
+        return fail(FDSP_EDEVICE, "stream/event creation failed");
+    }
+    *out = b;
+    return FDSP_OK;
+}
+
 int fdsp_bank_create(const char* kind, size_t voices, fdsp_bank** out) {
     return fdsp_bank_create_on(-1, kind, voices, 0, out);
 }
@@ -915,37 +902,24 @@ int fdsp_bank_create_on(int device, const char* kind, size_t voices, size_t ring
     int k = fdsp_kind_by_name(kind);
     if (k < 0) return fail(FDSP_EINVAL, std::string("unknown voice-graph kind: ") + (kind ? kind : "(null)"));
     if (voices == 0) return fail(FDSP_EINVAL, "voices must be > 0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FDSP_EDEVICE, "no HIP device available: the fundsp_hip engine has no CPU fallback");
-    if (device < 0) device = current_device();
-    if (device < 0 || device >= ndev || device >= MAX_DEVICES) return fail(FDSP_EINVAL, "device index out of range");
-    DeviceGuard guard(device);
-    const void* aux = device_aux(device);
-    if (!aux) return fail(FDSP_EDEVICE, "cannot set up the shared-data block on the device");
-    fdsp_bank* b = new fdsp_bank();
-    b->device = device;
-    b->aux = aux;
+    fdsp_bank* b = nullptr;
+    if (int rc = new_bank(device, voices, &b)) return rc;
+    DeviceGuard guard(b->device);
+    b->aux = device_aux(b->device);
+    if (!b->aux) {
+        fdsp_bank_destroy(b);
+        return fail(FDSP_EDEVICE, "cannot set up the shared-data block on the device");
+    }
     b->ops = kind_at(k);
-    b->V = voices;
     b->stride = (voices + 63) / 64 * 64;
     b->nslots = (int)b->ops->slots.size();
-    b->slots = nullptr;
-    b->stream = nullptr;
-    b->timed = false;
-    b->sr = FDSP_DEFAULT_SR;
     b->math = fd::g_math.load();
     for (int i = 0; i < b->nslots; i++) b->index[b->ops->slots[i].name] = i;
     size_t bytes = (size_t)(b->nslots > 0 ? b->nslots : 1) * b->stride * sizeof(float);
     hipError_t e = hipMalloc((void**)&b->slots, bytes);
     if (e != hipSuccess) {
-        delete b;
+        fdsp_bank_destroy(b);
         return fail(FDSP_ENOMEM, std::string("hipMalloc(slots): ") + hipGetErrorString(e));
-    }
-    if (hipStreamCreate(&b->stream) != hipSuccess ||
-        hipEventCreate(&b->e0) != hipSuccess || hipEventCreate(&b->e1) != hipSuccess) {
-        fdsp_bank_destroy(b);  // frees whatever of {slots, stream, e0, e1} exists
-        return fail(FDSP_EDEVICE, "stream/event creation failed");
     }
     if (b->ops->prepare_render) b->ops->prepare_render(voices, b->math == FDSP_MATH_FAST);  // (run-time compiled kinds: whatever a bank of this size and arithmetic still has to compile)
     if (b->ops->nrings > 0) {
@@ -1000,186 +974,43 @@ int fdsp_bank_create_on(int device, const char* kind, size_t voices, size_t ring
     return FDSP_OK;
 }
 
-static void fdn_free(FdnBank* f) {
-    if (!f) return;
-    if (f->st.rings) hipFree(f->st.rings);
-    if (f->st.wpos) hipFree(f->st.wpos);
-    if (f->st.v1) hipFree(f->st.v1);
-    if (f->st.v2) hipFree(f->st.v2);
-    if (f->st.fb) hipFree(f->st.fb);
-    f->st = fd::FdnState{};
-    if (f->st3.rings) hipFree(f->st3.rings);
-    if (f->st3.wpos) hipFree(f->st3.wpos);
-    f->st3.rings = nullptr;   // (pre, wpre, fval outlive a re-configuration: rv3_free_persistent)
-    f->st3.wpos = nullptr;
-    for (void* p : {(void*)f->sx.rings, (void*)f->sx.wpos, (void*)f->sx.v1, (void*)f->sx.v2, (void*)f->sx.fb, (void*)f->sx.s1, (void*)f->sx.s2, (void*)f->xtab})
-        if (p) hipFree(p);
-    f->sx = fd::FdnxState{};
-    f->xtab = nullptr;
-}
-static void rv3_free_persistent(FdnBank* f) {
-    if (f->st3.pre) hipFree(f->st3.pre);
-    if (f->st3.wpre) hipFree(f->st3.wpre);
-    if (f->st3.fval) hipFree(f->st3.fval);
-    f->st3.pre = nullptr; f->st3.wpre = nullptr; f->st3.fval = nullptr;
-}
-// reverb3_stereo banks: (re)allocate the loop's lines for a sample rate.  Transactional like fdn_configure.  What the reference's
-// Reverb::set_sample_rate leaves alone survives the move (the `pre` diffusers entirely; every allpass's z, the feedback sample and the
-// filters' values: fd_reverb3.hpp rv3_launch_migrate); the first configuration zeroes everything.
-static int rv3_configure(fdsp_bank* b, double sr) {
-    FdnBank* f = b->fdn;
-    fd::Rv3Const c;
-    if (!fd::rv3_make_const(f->time, f->damping, f->flt, sr, &c))
-        return fail(FDSP_EINVAL, "reverb3_stereo: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule; >= 14.2 kHz)");
-    const size_t n = b->V;
-    const bool first = f->st3.pre == nullptr;
-    fd::Rv3State st = f->st3;
-    st.rings = nullptr;
-    st.wpos = nullptr;
-    hipError_t e = hipMalloc((void**)&st.rings, n * c.ring_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.wpos, n * sizeof(int));
-    if (e == hipSuccess && first) e = hipMalloc((void**)&st.pre, n * 4 * (fd::RV3_PRE_CAP + 64) * sizeof(float));
-    if (e == hipSuccess && first) e = hipMalloc((void**)&st.wpre, n * sizeof(int));
-    if (e == hipSuccess && first) e = hipMalloc((void**)&st.fval, n * 32 * sizeof(float));
-    if (e != hipSuccess) {
-        if (st.rings) hipFree(st.rings);
-        if (st.wpos) hipFree(st.wpos);
-        if (first) { if (st.pre) hipFree(st.pre); if (st.wpre) hipFree(st.wpre); if (st.fval) hipFree(st.fval); }
-        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("reverb3_stereo buffers: ") + hipGetErrorString(e));
+// ---- effect banks (fd_fxbank.hpp): the public constructors check their arguments, the module builds the family on the bank's stream ----
+// The shell around what `make` builds.  It makes the networks' last argument checks first: the out pointer, the instances, the reverbs'
+// room size and time.
+using FxPtr = std::unique_ptr<fd::FxBank>;
+static int fx_bank_create(int device, size_t instances, double sample_rate, fdsp_bank** out, const std::function<int(hipStream_t, FxPtr*)>& make,
+                          double room_size = 1.0, double time = 1.0) {
+    if (!out) return fail(FDSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (instances == 0 || !(room_size > 0.0) || !(time > 0.0)) return fail(FDSP_EINVAL, "bad reverb_stereo / reverb4_stereo arguments");
+    fdsp_bank* b = nullptr;
+    if (int rc = new_bank(device, instances, &b)) return rc;
+    DeviceGuard guard(b->device);
+    int rc = make(b->stream, &b->fx);
+    if (rc == FDSP_OK) {
+        const hipError_t e = sync_bank_stream(b);
+        if (e != hipSuccess) rc = fail(FDSP_EDEVICE, hipGetErrorString(e));
     }
-    if (first) fd::rv3_launch_init(c, st, n, b->stream);
-    else {
-        // the new lines start empty; pre / filter values stay where they are; z and the feedback sample move over
-        fd::Rv3State fresh = st;
-        hipMemsetAsync(st.rings, 0, n * c.ring_stride * sizeof(float), b->stream);
-        hipMemsetAsync(st.wpos, 0, n * sizeof(int), b->stream);
-        fd::rv3_launch_migrate(f->c3, f->st3, c, fresh, n, b->stream);
-        hipStreamSynchronize(b->stream);
-        hipFree(f->st3.rings);
-        hipFree(f->st3.wpos);
+    if (rc != FDSP_OK) {
+        fdsp_bank_destroy(b);
+        return rc;
     }
-    f->c3 = c;
-    f->st3 = st;
-    f->c.nin = f->c.nout = 2;
-    b->sr = sr;
-    HIPCHK(hipGetLastError());
-    return FDSP_OK;
-}
-// filtered / per-instance networks: the table and the lines for a sample rate.  Transactional like fdn_configure: the new rings start empty
-// (Delay::set_sample_rate, delay.rs:105-113), the coefficients follow the rate (filter.rs:58-61, svf.rs:989-992), and the Fir carry, the
-// filter states and the feedback value stay (fir.rs:52-54, feedback.rs:125-127, 254-257)
-static int fdnx_configure(fdsp_bank* b, double sr) {
-    FdnBank* f = b->fdn;
-    std::vector<fd::FdnxInst> tab;
-    fd::FdnxConst c;
-    const int shortest = fd::fdnx_make_table(f->xdesc, b->V, sr, tab, &c);
-    if (shortest < 0) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
-    if (shortest < 128)
-        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
-    const size_t n = b->V;
-    fd::FdnxState st{};
-    fd::FdnxInst* dtab = nullptr;
-    hipError_t e = hipMalloc((void**)&st.rings, n * c.ring_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.wpos, n * sizeof(int));
-    for (float** p : {&st.v1, &st.v2, &st.fb, &st.s1, &st.s2})
-        if (e == hipSuccess) e = hipMalloc((void**)p, n * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&dtab, tab.size() * sizeof(fd::FdnxInst));
-    if (e == hipSuccess) e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(fd::FdnxInst), hipMemcpyHostToDevice, b->stream);
-    if (e != hipSuccess) {
-        FdnBank tmp;
-        tmp.sx = st;
-        tmp.xtab = dtab;
-        fdn_free(&tmp);
-        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("fdsp_fdn_network_create buffers: ") + hipGetErrorString(e));
-    }
-    c.tab = dtab;
-    fd::fdnx_launch_reset(c, st, n, b->stream);
-    if (f->sx.v1) {
-        hipMemcpyAsync(st.v1, f->sx.v1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.v2, f->sx.v2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.fb, f->sx.fb, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.s1, f->sx.s1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.s2, f->sx.s2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-    }
-    hipStreamSynchronize(b->stream);
-    fdn_free(f);  // the old buffers
-    f->cx = c;
-    f->sx = st;
-    f->xtab = dtab;
-    f->c.nin = f->xdesc.nin;
-    f->c.nout = f->xdesc.nout;
-    b->sr = sr;
-    HIPCHK(hipGetLastError());
-    return FDSP_OK;
-}
-static void fdn_free_stage(FdnBank* f) {
-    if (f && f->stage) hipFree(f->stage);
-    if (f) { f->stage = nullptr; f->stage_n = 0; }
-}
-
-// (re)allocate rings for the current sample rate and zero everything: Delay::set_sample_rate resizes + resets
-// when the rate changes (delay.rs:105-113)
-// Transactional: the new constants are validated and the new buffers allocated BEFORE anything of the bank changes; on
-// any failure the bank keeps its old constants, rings and rate.
-static int fdn_configure(fdsp_bank* b, double sr) {
-    FdnBank* f = b->fdn;
-    if (f->kind == 3) return rv3_configure(b, sr);
-    if (f->kind == 4) return fdnx_configure(b, sr);
-    fd::FdnConst c;
-    if (f->kind == 2) fd::fdn_make_const_generic(f->desc, sr, &c);
-    else if (f->kind == 1) fd::fdn_make_const_reverb4(f->room, f->time, sr, &c);
-    else fd::fdn_make_const(f->room, f->time, f->damping, sr, &c);
-    for (int i = 0; i < c.lines; i++)
-        if (c.len[i] <= 128)
-            return fail(FDSP_EINVAL, f->kind == 2 ? "fdsp_fdn_create: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)"
-                                                  : "reverb_stereo / reverb4_stereo: every delay must exceed 128 samples (room_size * sample_rate too small)");
-    if (f->kind != 0 && c.cap > (1 << 18))
-        return fail(FDSP_EINVAL, "reverb4_stereo / fdsp_fdn_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
-    const size_t n = b->V;
-    fd::FdnState st{};
-    hipError_t e = hipMalloc((void**)&st.rings, n * c.ring_stride * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.wpos, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.v1, n * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.v2, n * 32 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&st.fb, n * 32 * sizeof(float));
-    if (e != hipSuccess) {
-        FdnBank tmp;
-        tmp.st = st;
-        fdn_free(&tmp);
-        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("reverb_stereo buffers: ") + hipGetErrorString(e));
-    }
-    // The new lines start empty (Delay::set_sample_rate resizes and resets, delay.rs:105-113) -- but a change of rate resets nothing else: the
-    // FIRs keep their two samples of history (Fir::set_sample_rate, fir.rs:52-54) and Feedback its value (feedback.rs:125-127), so a tail that
-    // is sounding when the rate changes goes on from those, exactly like the reference's
-    fd::fdn_launch_reset(c, st, n, b->stream);
-    if (f->st.v1) {
-        hipMemcpyAsync(st.v1, f->st.v1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.v2, f->st.v2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipMemcpyAsync(st.fb, f->st.fb, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        hipStreamSynchronize(b->stream);
-    }
-    fdn_free(f);  // the old buffers
-    f->c = c;
-    f->st = st;
-    b->sr = sr;
-    HIPCHK(hipGetLastError());
+    b->sr = sample_rate;
+    *out = b;
     return FDSP_OK;
 }
 
 int fdsp_reverb_stereo_create(size_t instances, double room_size, double time, double damping, fdsp_bank** out) {
     return fdsp_reverb_stereo_create_on(-1, instances, room_size, time, damping, out);
 }
-
-static int fdn_bank_create_on(int kind, int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out, const fd::FdnDesc* desc = nullptr,
-                              const fd::Rv3Filter* flt = nullptr, const fd::FdnxDesc* xdesc = nullptr, double sample_rate = FDSP_DEFAULT_SR);
 int fdsp_reverb_stereo_create_on(int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out) {
-    return fdn_bank_create_on(0, device, instances, room_size, time, damping, out);
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_reverb_stereo(instances, 1, room_size, time, damping, s, fx); }, room_size, time);
 }
 int fdsp_reverb4_stereo_create(size_t instances, double room_size, double time, fdsp_bank** out) {
-    return fdn_bank_create_on(1, -1, instances, room_size, time, 0.0, out);
+    return fdsp_reverb4_stereo_create_on(-1, instances, room_size, time, out);
 }
 int fdsp_reverb4_stereo_create_on(int device, size_t instances, double room_size, double time, fdsp_bank** out) {
-    return fdn_bank_create_on(1, device, instances, room_size, time, 0.0, out);
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_reverb_stereo(instances, 2, room_size, time, 0.0, s, fx); }, room_size, time);
 }
 
 int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out) {
@@ -1188,17 +1019,9 @@ int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* de
     if (taps < 1 || taps > 3) return fail(FDSP_EINVAL, "fdsp_fdn_create: taps takes 1..3 (Fir<U1> .. Fir<U3>)");
     if ((inputs != 1 && inputs != 2) || (outputs != 1 && outputs != 2)) return fail(FDSP_EINVAL, "fdsp_fdn_create: inputs / outputs take 1 (split / join) or 2 (multisplit::<U2, _> / multijoin::<U2, _>)");
     if (!delays || !weights) return fail(FDSP_EINVAL, "fdsp_fdn_create: delays or weights NULL");
-    fd::FdnDesc d;
-    d.lines = lines;
-    d.taps = taps;
-    d.nin = inputs;
-    d.nout = outputs;
-    for (int i = 0; i < lines; i++) {
+    for (int i = 0; i < lines; i++)
         if (!(delays[i] >= 0.0) || !(delays[i] < 1e6)) return fail(FDSP_EINVAL, "fdsp_fdn_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
-        d.delay[i] = delays[i];
-    }
-    for (int j = 0; j < taps; j++) d.w[j] = weights[j];
-    return fdn_bank_create_on(2, device, instances, 1.0, 1.0, 0.0, out, &d);
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_fdn(instances, lines, delays, taps, weights, inputs, outputs, s, fx); });
 }
 int fdsp_fdn_create(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out) {
     return fdsp_fdn_create_on(-1, instances, lines, delays, taps, weights, inputs, outputs, out);
@@ -1224,38 +1047,16 @@ int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_netw
     if (shelf && !net->gain) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: bell / lowshelf / highshelf need a gain");
     if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: sample_rate must be positive");
     if (instances == 0) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: no instances");
-    fd::FdnxDesc d;
-    d.lines = N;
-    d.taps = net->taps;
-    d.nin = net->inputs;
-    d.nout = net->outputs;
-    d.filter = net->filter;
-    d.svf_mode = net->svf_mode;
-    d.place = net->place;
-    d.per_instance = net->per_instance ? 1 : 0;
-    d.has_gain = net->line_gain ? 1 : 0;
-    const size_t P = d.per_instance ? instances : 1, M = P * (size_t)N;
-    d.delay.assign(net->delays, net->delays + M);
-    for (double t : d.delay)
-        if (!(t >= 0.0) || !(t < 1e6)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
-    if (net->taps > 0) d.w.assign(net->weights, net->weights + M * net->taps);
-    if (net->filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net->cutoff, net->cutoff + M);
-    if (net->filter == FDSP_FDN_FILTER_SVF) d.q.assign(net->q, net->q + M);
-    if (shelf) d.gain.assign(net->gain, net->gain + M);
-    if (d.has_gain) d.line_gain.assign(net->line_gain, net->line_gain + M);
-    return fdn_bank_create_on(4, device, instances, 1.0, 1.0, 0.0, out, nullptr, nullptr, &d, sample_rate);
+    const size_t M = (net->per_instance ? instances : 1) * (size_t)N;
+    for (size_t i = 0; i < M; i++)
+        if (!(net->delays[i] >= 0.0) || !(net->delays[i] < 1e6)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+    return fx_bank_create(device, instances, sample_rate, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_fdn_network(instances, *net, sample_rate, s, fx); });
 }
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
     return fdsp_fdn_network_create_on(-1, instances, net, sample_rate, out);
 }
 
-// ---- resynthesizer banks (fd_resynth.hpp) ----------------------------------------------------------------------------------------------
-static void rs_free(RsBank* r) {
-    if (!r) return;
-    for (void* p : {(void*)r->st.frames, (void*)r->st.xin, (void*)r->st.samples, (void*)r->st.fstep, (void*)r->tw, (void*)r->hann, (void*)r->hz, (void*)r->band, (void*)r->gain})
-        if (p) hipFree(p);
-    delete r;
-}
+// ---- resynthesizer banks (fd_fxbank.hpp fx_resynth) --------------------------------------------------------------------------------------
 static int rs_check_spec(size_t instances, const fdsp_resynth_spec* sp) {
     if (!sp) return fail(FDSP_EINVAL, "fdsp_resynth_create: spec NULL");
     if (instances == 0) return fail(FDSP_EINVAL, "fdsp_resynth_create: no instances");
@@ -1273,165 +1074,34 @@ static int rs_check_spec(size_t instances, const fdsp_resynth_spec* sp) {
     if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, "fdsp_resynth_create: flush_denormals takes 0 or 1");
     return FDSP_OK;
 }
-int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles) {
-    const int N = window_length;
-    if (N < 4 || N > 8192 || (N & (N - 1)) != 0) return fail(FDSP_EINVAL, "fdsp_resynth_tables: window_length takes a power of two from 4 to 8192");
-    fd::rs_tables(N, h_hann, nullptr, h_twiddles);
-    return FDSP_OK;
-}
 int fdsp_resynth_create_on(int device, size_t instances, const fdsp_resynth_spec* sp, fdsp_bank** out) {
     if (!out) return fail(FDSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (int rc = rs_check_spec(instances, sp)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(FDSP_EDEVICE, "no HIP device available: the fundsp_hip engine has no CPU fallback");
-    if (device < 0) device = current_device();
-    if (device < 0 || device >= ndev || device >= MAX_DEVICES) return fail(FDSP_EINVAL, "device index out of range");
-    DeviceGuard guard(device);
-    const int N = sp->window_length, H = N / 4, I = sp->inputs, O = sp->outputs, NB = N / 2 + 1;
-    const size_t V = instances;
-    RsBank* r = new RsBank();
-    fd::RsConst& c = r->c;
-    c.N = N;
-    c.logN = 0;
-    while ((1 << c.logN) < N) c.logN++;
-    c.I = I;
-    c.O = O;
-    c.proc = sp->processor;
-    for (int o = 0; o < fd::RS_MAX_CH; o++) c.src[o] = o < O ? sp->source[o] : -1;
-    c.rows = sp->per_instance ? (int)V : 1;
-    c.invN = 1.0f / (float)N;
-    // frame ring: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large
-    const size_t slot = V * (size_t)O * N * sizeof(float);
-    size_t R = ((size_t)256 << 20) / slot;
-    const size_t rmax = 5 + 65536 / (size_t)H;
-    R = R < 8 ? 8 : (R > rmax ? rmax : R);
-    c.R = (int)R;
-    c.Lmax = (c.R - 5) * H;
-    c.Rx = 1;
-    while (c.Rx < c.Lmax + N) c.Rx <<= 1;
-    r->ftz = sp->flush_denormals;
-    r->per_instance = sp->per_instance;
-    const float fstep = (float)FDSP_DEFAULT_SR / (float)N;
-    std::vector<float> hann(N), hz(N), tw(N);
-    fd::rs_tables(N, hann.data(), hz.data(), tw.data());
-    std::vector<float> band, gain;
-    if (c.proc == FDSP_RESYNTH_BAND) {
-        band.resize((size_t)c.rows * O * 2);
-        for (size_t i = 0; i < (size_t)c.rows * O; i++) {
-            band[2 * i] = sp->lo_hz[i];
-            band[2 * i + 1] = sp->hi_hz[i];
-        }
-    }
-    if (c.proc == FDSP_RESYNTH_GAIN) gain.assign(sp->gain, sp->gain + (size_t)c.rows * O * NB);
-    fdsp_bank* b = new fdsp_bank();
-    b->device = device;
-    b->rs = r;
-    b->V = instances;
-    b->stride = instances;
-    b->sr = FDSP_DEFAULT_SR;
-    if (hipStreamCreate(&b->stream) != hipSuccess || hipEventCreate(&b->e0) != hipSuccess || hipEventCreate(&b->e1) != hipSuccess) {
-        fdsp_bank_destroy(b);
-        return fail(FDSP_EDEVICE, "stream/event creation failed");
-    }
-    hipError_t e = hipMalloc((void**)&r->st.frames, R * slot);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->st.xin, V * (size_t)I * c.Rx * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->st.samples, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->st.fstep, sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->tw, (N / 2) * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->hann, N * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->hz, N * sizeof(float));
-    if (e == hipSuccess && !band.empty()) e = hipMalloc((void**)&r->band, band.size() * sizeof(float));
-    if (e == hipSuccess && !gain.empty()) e = hipMalloc((void**)&r->gain, gain.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(r->tw, tw.data(), (N / 2) * sizeof(float2), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->hann, hann.data(), N * sizeof(float), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->hz, hz.data(), N * sizeof(float), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess && r->band) e = hipMemcpyAsync(r->band, band.data(), band.size() * sizeof(float), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess && r->gain) e = hipMemcpyAsync(r->gain, gain.data(), gain.size() * sizeof(float), hipMemcpyHostToDevice, b->stream);
-    // reset: the windows start empty (nothing is read before a frame of this run exists, but the rings start defined)
-    if (e == hipSuccess) e = hipMemsetAsync(r->st.samples, 0, sizeof(unsigned long long), b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->st.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->st.frames, 0, R * slot, b->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->st.xin, 0, V * (size_t)I * c.Rx * sizeof(float), b->stream);
-    if (e == hipSuccess) e = sync_bank_stream(b);
-    if (e != hipSuccess) {
-        fdsp_bank_destroy(b);
-        return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("fdsp_resynth_create buffers: ") + hipGetErrorString(e));
-    }
-    c.tw = r->tw;
-    c.hann = r->hann;
-    c.hz = r->hz;
-    c.band = r->band;
-    c.gain = r->gain;
-    *out = b;
-    return FDSP_OK;
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_resynth(instances, *sp, s, fx); });
 }
 int fdsp_resynth_create(size_t instances, const fdsp_resynth_spec* spec, fdsp_bank** out) { return fdsp_resynth_create_on(-1, instances, spec, out); }
 static int rs_set_table(fdsp_bank* b, const float* h, size_t first, size_t count, bool gain) {
     if (!b || !h) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: bank or values NULL");
-    if (!b->rs) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: not a resynthesizer bank");
-    RsBank* r = b->rs;
-    if (r->c.proc != (gain ? FDSP_RESYNTH_GAIN : FDSP_RESYNTH_BAND))
-        return fail(FDSP_EINVAL, gain ? "fdsp_resynth_set_gain: the bank's processor is not FDSP_RESYNTH_GAIN" : "fdsp_resynth_set_band: the bank's processor is not FDSP_RESYNTH_BAND");
-    const size_t rows = (size_t)r->c.rows;
-    if (first > rows || count > rows - first) return fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: rows out of range (one row per instance with per_instance, else the single row 0)");
+    float* row0 = nullptr; size_t row = 0;
+    if (int rc = fd::fx_resynth_table(b->fx.get(), gain, first, count, &row0, &row)) return rc;
     if (count == 0) return FDSP_OK;
     DeviceGuard guard(b->device);
-    const size_t row = (size_t)r->c.O * (gain ? (size_t)(r->c.N / 2 + 1) : 2);
     HIPCHK(await_last_render(b));
-    HIPCHK(hipMemcpyAsync((gain ? r->gain : (float*)r->band) + first * row, h, count * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(row0, h, count * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
     HIPCHK(sync_bank_stream(b));   // (h is borrowed for the call; the bank's stream is idle when a setter returns)
     return FDSP_OK;
 }
 int fdsp_resynth_set_band(fdsp_bank* b, const float* h_lo_hi, size_t first, size_t count) { return rs_set_table(b, h_lo_hi, first, count, false); }
 int fdsp_resynth_set_gain(fdsp_bank* b, const float* h_gain, size_t first, size_t count) { return rs_set_table(b, h_gain, first, count, true); }
-static int rs_clone(const fdsp_bank* src, fdsp_bank** out) {
-    const RsBank* a = src->rs;
-    fdsp_resynth_spec sp{};
-    sp.window_length = a->c.N;
-    sp.inputs = a->c.I;
-    sp.outputs = a->c.O;
-    sp.processor = a->c.proc;
-    for (int o = 0; o < 8; o++) sp.source[o] = a->c.src[o];
-    sp.flush_denormals = a->ftz;
-    sp.per_instance = a->per_instance;
-    const size_t nt = (size_t)a->c.rows * a->c.O;
-    std::vector<float> lo(nt, 0.0f), hi(nt, 0.0f), g(a->gain ? nt * (a->c.N / 2 + 1) : 0);
-    sp.lo_hz = lo.data();
-    sp.hi_hz = hi.data();
-    sp.gain = g.data();
-    fdsp_bank* b = nullptr;
-    if (int rc = fdsp_resynth_create_on(src->device, src->V, &sp, &b)) return rc;
-    RsBank* d = b->rs;
-    const size_t slot = src->V * (size_t)a->c.O * a->c.N * sizeof(float);
-    hipError_t e = hipMemcpyAsync(d->st.frames, a->st.frames, (size_t)a->c.R * slot, hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->st.xin, a->st.xin, src->V * (size_t)a->c.I * a->c.Rx * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->st.samples, a->st.samples, sizeof(unsigned long long), hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->st.fstep, a->st.fstep, sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess && a->band) e = hipMemcpyAsync(d->band, a->band, nt * sizeof(float2), hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess && a->gain) e = hipMemcpyAsync(d->gain, a->gain, g.size() * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-    if (e == hipSuccess) e = sync_bank_stream(b);
-    if (e != hipSuccess) {
-        fdsp_bank_destroy(b);
-        return fail(FDSP_EDEVICE, std::string("fdsp_bank_clone: resynthesizer state: ") + hipGetErrorString(e));
-    }
-    b->sr = src->sr;
-    b->math = src->math;
-    b->opt_timing = src->opt_timing;
-    *out = b;
-    return FDSP_OK;
-}
-static int rv3_create(int device, size_t instances, double time, double diffusion, const fd::Rv3Filter& flt, fdsp_bank** out) {
+static int rv3_create(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, fdsp_bank** out) {
     if (out) *out = nullptr;
-    if (!(time > 0.0) || !(diffusion >= 0.0 && diffusion <= 1.0) || !(flt.cutoff > 0.0f))
+    if (!(time > 0.0) || !(diffusion >= 0.0 && diffusion <= 1.0) || !(cutoff > 0.0f))
         return fail(FDSP_EINVAL, "fdsp_reverb3_stereo_create: time > 0, diffusion in 0..1, the loop filter's cutoff > 0 Hz");
-    return fdn_bank_create_on(3, device, instances, 1.0, time, diffusion, out, nullptr, &flt);
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_reverb3_stereo(instances, time, diffusion, svf_mode, cutoff, q, gain, s, fx); }, 1.0, time);
 }
 int fdsp_reverb3_stereo_create_on(int device, size_t instances, double time, double diffusion, float lowpole_cutoff, fdsp_bank** out) {
-    fd::Rv3Filter f;
-    f.kind = 0;
-    f.cutoff = lowpole_cutoff;
-    return rv3_create(device, instances, time, diffusion, f, out);
+    return rv3_create(device, instances, time, diffusion, -1, lowpole_cutoff, 1.0f, 1.0f, out);
 }
 int fdsp_reverb3_stereo_create(size_t instances, double time, double diffusion, float lowpole_cutoff, fdsp_bank** out) {
     return fdsp_reverb3_stereo_create_on(-1, instances, time, diffusion, lowpole_cutoff, out);
@@ -1439,62 +1109,10 @@ int fdsp_reverb3_stereo_create(size_t instances, double time, double diffusion, 
 int fdsp_reverb3_stereo_svf_create_on(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (svf_mode < 0 || svf_mode > 8 || !(q > 0.0f) || !(gain > 0.0f)) return fail(FDSP_EINVAL, "fdsp_reverb3_stereo_svf_create: svf_mode 0..8 (FDSP_SVF_*), q > 0, gain > 0 (an amplitude, used by bell / lowshelf / highshelf)");
-    fd::Rv3Filter f;
-    f.kind = 1;
-    f.mode = svf_mode;
-    f.cutoff = cutoff; f.q = q; f.gain = gain;
-    return rv3_create(device, instances, time, diffusion, f, out);
+    return rv3_create(device, instances, time, diffusion, svf_mode, cutoff, q, gain, out);
 }
 int fdsp_reverb3_stereo_svf_create(size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, fdsp_bank** out) {
     return fdsp_reverb3_stereo_svf_create_on(-1, instances, time, diffusion, svf_mode, cutoff, q, gain, out);
-}
-
-static int fdn_bank_create_on(int kind, int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out, const fd::FdnDesc* desc,
-                              const fd::Rv3Filter* flt, const fd::FdnxDesc* xdesc, double sample_rate) {
-    if (!out) return fail(FDSP_EINVAL, "out is NULL");
-    *out = nullptr;
-    if (instances == 0 || !(room_size > 0.0) || !(time > 0.0)) return fail(FDSP_EINVAL, "bad reverb_stereo / reverb4_stereo arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FDSP_EDEVICE, "no HIP device available: the fundsp_hip engine has no CPU fallback");
-    if (device < 0) device = current_device();
-    if (device < 0 || device >= ndev || device >= MAX_DEVICES) return fail(FDSP_EINVAL, "device index out of range");
-    DeviceGuard guard(device);
-    fdsp_bank* b = new fdsp_bank();
-    b->device = device;
-    b->fdn = new FdnBank();
-    b->fdn->kind = kind;
-    b->fdn->room = room_size;
-    b->fdn->time = time;
-    b->fdn->damping = damping;
-    if (desc) b->fdn->desc = *desc;
-    if (flt) b->fdn->flt = *flt;
-    if (xdesc) b->fdn->xdesc = *xdesc;
-    b->fdn->st = fd::FdnState{};
-    b->ops = nullptr;
-    b->V = instances;
-    b->stride = instances;
-    b->nslots = 0;
-    b->slots = nullptr;
-    b->timed = false;
-    b->sr = FDSP_DEFAULT_SR;
-    if (hipStreamCreate(&b->stream) != hipSuccess || hipEventCreate(&b->e0) != hipSuccess ||
-        hipEventCreate(&b->e1) != hipSuccess) {
-        fdsp_bank_destroy(b);
-        return fail(FDSP_EDEVICE, "stream/event creation failed");
-    }
-    int rc = fdn_configure(b, sample_rate);
-    if (rc != FDSP_OK) {
-        fdsp_bank_destroy(b);
-        return rc;
-    }
-    hipError_t e = sync_bank_stream(b);
-    if (e != hipSuccess) {
-        fdsp_bank_destroy(b);
-        return fail(FDSP_EDEVICE, hipGetErrorString(e));
-    }
-    *out = b;
-    return FDSP_OK;
 }
 
 void fdsp_bank_destroy(fdsp_bank* b) {
@@ -1503,17 +1121,7 @@ void fdsp_bank_destroy(fdsp_bank* b) {
     // a render that ran on a caller's stream may still be reading the slots: wait for its completion event first
     if (b->ext_pending && b->e1) hipEventSynchronize(b->e1);
     if (b->stream) sync_bank_stream(b);
-    if (b->fdn) {
-        fdn_free(b->fdn);
-        rv3_free_persistent(b->fdn);
-        fdn_free_stage(b->fdn);
-        delete b->fdn;
-        b->fdn = nullptr;
-    }
-    if (b->rs) {
-        rs_free(b->rs);
-        b->rs = nullptr;
-    }
+    b->fx.reset();
     if (b->slots) hipFree(b->slots);
     if (b->ring) hipFree(b->ring);
     if (b->ev) hipFree(b->ev);
@@ -1540,57 +1148,21 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     // everything queued on the source's stream (and a render on a caller's stream) lands before the copy reads it
     if (src->ext_pending && src->e1) HIPCHK(hipEventSynchronize(src->e1));
     HIPCHK(hipStreamSynchronize(src->stream));
-    if (src->rs) return rs_clone(src, out);
     fdsp_bank* b = nullptr;
-    int rc;
-    if (src->fdn)
-        rc = fdn_bank_create_on(src->fdn->kind, src->device, src->V, src->fdn->room, src->fdn->time, src->fdn->damping, &b, &src->fdn->desc, &src->fdn->flt,
-                                &src->fdn->xdesc, src->fdn->kind == 4 ? src->sr : FDSP_DEFAULT_SR);
-    else
-        rc = fdsp_bank_create_on(src->device, src->ops->name.c_str(), src->V, src->ring_frames, &b);
+    int rc = src->fx ? new_bank(src->device, src->V, &b) : fdsp_bank_create_on(src->device, src->ops->name.c_str(), src->V, src->ring_frames, &b);
     if (rc != FDSP_OK) return rc;
     auto bail = [&](hipError_t e, const char* what) {
         fdsp_bank_destroy(b);
         return fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, std::string("fdsp_bank_clone: ") + what + ": " + hipGetErrorString(e));
     };
     hipError_t e = hipSuccess;
-    if (src->fdn) {
-        if (src->sr != b->sr) {  // the rings' capacity and lengths follow the sample rate
-            e = sync_bank_stream(b);
-            if (e != hipSuccess) return bail(e, "sync");
-            rc = fdn_configure(b, src->sr);
-            if (rc != FDSP_OK) {
-                fdsp_bank_destroy(b);
-                return rc;
-            }
-        }
-        const size_t n = src->V;
-        if (src->fdn->kind == 3) {
-            const fd::Rv3State &a3 = src->fdn->st3, &d3 = b->fdn->st3;
-            e = hipMemcpyAsync(d3.rings, a3.rings, n * src->fdn->c3.ring_stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d3.pre, a3.pre, n * 4 * (fd::RV3_PRE_CAP + 64) * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d3.wpos, a3.wpos, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d3.wpre, a3.wpre, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d3.fval, a3.fval, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-            if (e != hipSuccess) return bail(e, "reverb3 state");
-        } else if (src->fdn->kind == 4) {
-            const fd::FdnxState &a = src->fdn->sx, &d = b->fdn->sx;
-            e = hipMemcpyAsync(d.rings, a.rings, n * src->fdn->cx.ring_stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d.wpos, a.wpos, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
-            for (auto m : {&fd::FdnxState::v1, &fd::FdnxState::v2, &fd::FdnxState::fb, &fd::FdnxState::s1, &fd::FdnxState::s2})
-                if (e == hipSuccess) e = hipMemcpyAsync(d.*m, a.*m, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-            if (e != hipSuccess) return bail(e, "network state");
-        } else {
-        const fd::FdnState &a = src->fdn->st, &d = b->fdn->st;
-        e = hipMemcpyAsync(d.rings, a.rings, n * src->fdn->c.ring_stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d.wpos, a.wpos, n * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d.v1, a.v1, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d.v2, a.v2, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d.fb, a.fb, n * 32 * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
-        if (e != hipSuccess) return bail(e, "reverb state");
+    b->sr = src->sr;
+    if (src->fx) {
+        if ((rc = src->fx->clone(b->stream, &b->fx)) != FDSP_OK) {
+            fdsp_bank_destroy(b);
+            return rc;
         }
     } else {
-        b->sr = src->sr;
         e = hipMemcpyAsync(b->slots, src->slots, (size_t)(src->nslots > 0 ? src->nslots : 1) * src->stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
         if (e != hipSuccess) return bail(e, "slots");
         if (src->ring) {
@@ -1619,7 +1191,6 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
         if (e == hipSuccess) e = hipMemcpyAsync(b->panw, src->panw, 2 * src->stride * sizeof(float), hipMemcpyDeviceToDevice, b->stream);
         if (e != hipSuccess) return bail(e, "pan weights");
     }
-    if (src->fdn) b->fdn->bus = src->fdn->bus;
     b->math = src->math;
     b->opt_pipe_split = src->opt_pipe_split;
     b->opt_time_split = src->opt_time_split;
@@ -1634,48 +1205,41 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
 // `wet * node` / `dry * multipass() & wet * node` around a reverb / network bank (fd_fdn.hpp FdnBus): a host-side setting, read at every launch
 int fdsp_bank_set_bus(fdsp_bank* b, int mode, float wet, float dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: bank NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: resynthesizer banks have no bus (out of scope: render the dry path separately)");
-    if (!b->fdn) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: reverb / network banks only (a run-time compiled graph carries its bus in the graph: fdsp_graph_compile)");
+    fd::FdnBus* bus = b->fx ? b->fx->bus() : nullptr;
+    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: resynthesizer banks have no bus (out of scope: render the dry path separately)");
+    if (!bus) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: reverb / network banks only (a run-time compiled graph carries its bus in the graph: fdsp_graph_compile)");
     if (mode < FDSP_BUS_NONE || mode > FDSP_BUS_DRY_WET) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: mode takes FDSP_BUS_NONE, FDSP_BUS_WET or FDSP_BUS_DRY_WET");
-    if (mode == FDSP_BUS_DRY_WET && b->fdn->c.nin != b->fdn->c.nout)
+    if (mode == FDSP_BUS_DRY_WET && b->fx->inputs() != b->fx->outputs())
         return fail(FDSP_EINVAL, "fdsp_bank_set_bus: a Bus needs as many outputs as inputs (Bus<X, Y>: Y::Inputs = X::Inputs, Y::Outputs = X::Outputs; multipass::<N>() is N -> N)");
-    b->fdn->bus.mode = mode;
-    b->fdn->bus.wet = wet;
-    b->fdn->bus.dry = dry;
+    bus->mode = mode;
+    bus->wet = wet;
+    bus->dry = dry;
     return FDSP_OK;
 }
 
 int fdsp_bank_get_bus(const fdsp_bank* b, int* mode, float* wet, float* dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_get_bus: bank NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: resynthesizer banks have no bus");
-    if (!b->fdn) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: reverb / network banks only");
-    if (mode) *mode = b->fdn->bus.mode;
-    if (wet) *wet = b->fdn->bus.wet;
-    if (dry) *dry = b->fdn->bus.dry;
+    const fd::FdnBus* bus = b->fx ? b->fx->bus() : nullptr;
+    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: resynthesizer banks have no bus");
+    if (!bus) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: reverb / network banks only");
+    if (mode) *mode = bus->mode;
+    if (wet) *wet = bus->wet;
+    if (dry) *dry = bus->dry;
     return FDSP_OK;
 }
 
-int fdsp_bank_inputs(const fdsp_bank* b) { return b ? (b->rs ? b->rs->c.I : b->fdn ? b->fdn->c.nin : b->ops->nin) : FDSP_EINVAL; }
-int fdsp_bank_outputs(const fdsp_bank* b) { return b ? (b->rs ? b->rs->c.O : b->fdn ? b->fdn->c.nout : b->ops->nout) : FDSP_EINVAL; }
+int fdsp_bank_inputs(const fdsp_bank* b) { return b ? (b->fx ? b->fx->inputs() : b->ops->nin) : FDSP_EINVAL; }
+int fdsp_bank_outputs(const fdsp_bank* b) { return b ? (b->fx ? b->fx->outputs() : b->ops->nout) : FDSP_EINVAL; }
 size_t fdsp_bank_voices(const fdsp_bank* b) { return b ? b->V : 0; }
 
 int fdsp_bank_set_sample_rate(fdsp_bank* b, double sr) {
     if (!b || !(sr > 0.0)) return fail(FDSP_EINVAL, "bad bank or sample rate");
     DeviceGuard guard(b->device);
-    if (b->rs) {  // FftWindow::set_sample_rate: frequency() follows, every other state stays (resynth.rs:170-172, 325-330)
-        // the bin spacing lives in device memory, in stream order behind the last render: a captured launch replays with the new rate
-        const float fstep = (float)sr / (float)b->rs->c.N;
+    if (b->fx) {  // (a network changes nothing unless the rate changes, and sets nothing when its new configuration fails)
         HIPCHK(await_last_render(b));
-        HIPCHK(hipMemcpyAsync(b->rs->st.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(sync_bank_stream(b));   // (fstep is a local; the bank's stream is idle when a setter returns)
+        if (int rc = b->fx->set_sample_rate(sr, b->stream)) return rc;
         b->sr = sr;
         return FDSP_OK;
-    }
-    if (b->fdn) {
-        if (sr == b->sr) return FDSP_OK;  // Delay::set_sample_rate: nothing happens unless the rate changes
-        HIPCHK(await_last_render(b));
-        HIPCHK(sync_bank_stream(b));
-        return fdn_configure(b, sr);  // sets b->sr on success only
     }
     b->sr = sr;
     HIPCHK(await_last_render(b));
@@ -1689,24 +1253,12 @@ int fdsp_bank_set_sample_rate(fdsp_bank* b, double sr) {
 int fdsp_bank_reset(fdsp_bank* b) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     DeviceGuard guard(b->device);
-    if (b->rs) {  // Resynth::reset: the sample count and the four windows start over (resynth.rs:332-337)
-        HIPCHK(await_last_render(b));
-        HIPCHK(hipMemsetAsync(b->rs->st.samples, 0, sizeof(unsigned long long), b->stream));
-        HIPCHK(sync_bank_stream(b));
-        return FDSP_OK;
-    }
-    if (b->fdn) {
-        HIPCHK(await_last_render(b));
-        if (b->fdn->kind == 3) fd::rv3_launch_reset(b->fdn->c3, b->fdn->st3, b->V, b->stream);
-        else if (b->fdn->kind == 4) fd::fdnx_launch_reset(b->fdn->cx, b->fdn->sx, b->V, b->stream);
-        else fd::fdn_launch_reset(b->fdn->c, b->fdn->st, b->V, b->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(sync_bank_stream(b));
-        return FDSP_OK;
-    }
     HIPCHK(await_last_render(b));
-    b->ops->lifecycle(b->slots, b->stride, 0, b->stride, 2, b->sr, nullptr, b->aux, b->ring, b->ring_cap, b->stream);
-    HIPCHK(hipGetLastError());
+    if (b->fx) HIPCHK(b->fx->reset(b->stream));
+    else {
+        b->ops->lifecycle(b->slots, b->stride, 0, b->stride, 2, b->sr, nullptr, b->aux, b->ring, b->ring_cap, b->stream);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(sync_bank_stream(b));
     return FDSP_OK;
 }
@@ -1714,7 +1266,7 @@ int fdsp_bank_reset(fdsp_bank* b) {
 int fdsp_bank_set_seed(fdsp_bank* b, const uint64_t* h_seeds, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     DeviceGuard guard(b->device);
-    if (b->fdn || b->rs) return FDSP_OK;  // no node of reverb_stereo (nor Resynth) uses its hash (Delay, Fir, Panner: default set_hash)
+    if (b->fx) return FDSP_OK;  // no node of reverb_stereo (nor Resynth) uses its hash (Delay, Fir, Panner: default set_hash)
     if (int rc = check_range(b, first, count)) return rc;
     if (count == 0) return FDSP_OK;
     uint64_t* d = nullptr;
@@ -1747,6 +1299,16 @@ __global__ void k_fill_slot(float* __restrict__ row, float value, size_t V) {
     if (v < V) row[v] = value;
 }
 
+// reverb / network banks (the effect banks with a bus) have no named slots: the slot entry points refuse them before any other check
+static int no_named_slots(const fdsp_bank* b) {
+    return b && b->fx && b->fx->bus() ? fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)") : FDSP_OK;
+}
+// resynthesizer banks (the effect bank without a bus) take fdsp_bank_process and nothing of the mix-down, pan, ring or event entry points
+static int render_only(const fdsp_bank* b) {
+    return b->fx && !b->fx->bus() ? fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)")
+                                   : FDSP_OK;
+}
+
 static int set_words(fdsp_bank* b, int slot, const void* h_words, size_t first, size_t count) {
     HIPCHK(await_last_render(b));
     HIPCHK(hipMemcpyAsync(b->slots + (size_t)slot * b->stride + first, h_words, count * sizeof(float),
@@ -1756,7 +1318,7 @@ static int set_words(fdsp_bank* b, int slot, const void* h_words, size_t first, 
 }
 
 int fdsp_bank_set_param(fdsp_bank* b, const char* name, const float* h_values, size_t first, size_t count) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b || !h_values) return fail(FDSP_EINVAL, "bank or values NULL");
     DeviceGuard guard(b->device);
     int s = find_slot(b, name);
@@ -1774,7 +1336,7 @@ int fdsp_bank_set_param(fdsp_bank* b, const char* name, const float* h_values, s
 }
 
 int fdsp_bank_set_param_all(fdsp_bank* b, const char* name, float value) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     // One value for every voice -- Shared::set_value of a control all voices watch (shared.rs:98-101), e.g. the gate of config 4's
     // `var(gate) >> adsr_live` between two launches: filled on the device, in stream order behind the last render, no host copy and
@@ -1793,7 +1355,7 @@ int fdsp_bank_set_param_all(fdsp_bank* b, const char* name, float value) {
 }
 
 int fdsp_bank_set_param_u64(fdsp_bank* b, const char* name, const uint64_t* h_values, size_t first, size_t count) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b || !h_values || !name) return fail(FDSP_EINVAL, "bank, name or values NULL");
     DeviceGuard guard(b->device);
     int lo = find_slot(b, (std::string(name) + ".lo").c_str());
@@ -1817,7 +1379,7 @@ int fdsp_bank_set_param_u64(fdsp_bank* b, const char* name, const uint64_t* h_va
 }
 
 int fdsp_bank_get_slot(fdsp_bank* b, const char* name, float* h_values, size_t first, size_t count) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b || !h_values) return fail(FDSP_EINVAL, "bank or values NULL");
     DeviceGuard guard(b->device);
     int s = find_slot(b, name);
@@ -1830,7 +1392,7 @@ int fdsp_bank_get_slot(fdsp_bank* b, const char* name, float* h_values, size_t f
 }
 
 int fdsp_bank_get_state(fdsp_bank* b, float* h_slots) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b || !h_slots) return fail(FDSP_EINVAL, "bank or buffer NULL");
     DeviceGuard guard(b->device);
     HIPCHK(await_last_render(b));
@@ -1842,7 +1404,7 @@ int fdsp_bank_get_state(fdsp_bank* b, float* h_slots) {
 }
 
 int fdsp_bank_set_state(fdsp_bank* b, const float* h_slots) {
-    if (b && b->fdn) return fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)");
+    if (int rc = no_named_slots(b)) return rc;
     if (!b || !h_slots) return fail(FDSP_EINVAL, "bank or buffer NULL");
     DeviceGuard guard(b->device);
     HIPCHK(await_last_render(b));
@@ -1878,40 +1440,9 @@ int fdsp_bank_process(fdsp_bank* b, size_t frames, const float* d_in, float* d_o
     const bool timing = timing_on(b);
     if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
     resolve_opts(b);
-    if (b->rs) {   // Resynth has no process override: FDSP_MODE_PROCESS == FDSP_MODE_TICK
-        RsBank* r = b->rs;
-        if (r->ftz) fd::rs_ftz::rs_launch_render(r->c, r->st, b->V, d_in, d_out, frames, frame_stride, layout, s);
-        else fd::rs_ieee::rs_launch_render(r->c, r->st, b->V, d_in, d_out, frames, frame_stride, layout, s);
-    } else if (b->fdn) {  // Feedback::process is the per-sample tick (feedback.rs:136-146): both modes are the same arithmetic but for the joins (MultiJoin / Join)
-        FdnBank* f = b->fdn;
-        const int tick = mode == FDSP_MODE_TICK ? 1 : 0, nin = f->c.nin, nout = f->c.nout;
-        // voice-minor buffers of banks with at least a tile of instances go through the planar staging copy (the lane = frame kernels read
-        // 256-byte runs of it instead of gathering a line per frame); the staging buffer grows outside captures only, like the partial mixes
-        bool staged = layout == FDSP_LAYOUT_VOICE_MINOR && b->V >= 64 && (f->kind >= 3 || f->c.generic || fd::tl_opts.fdn_kernel == 0 || f->c.sections == 2);
-        auto render = [&](const float* pi, float* po, size_t fs, int lay) {
-            if (f->kind == 3) fd::rv3_launch_render(f->c3, f->st3, b->V, pi, po, frames, fs, lay, s, f->bus);   // (Reverb has no process override: one arithmetic)
-            else if (f->kind == 4) fd::fdnx_launch_render(f->cx, f->sx, b->V, pi, po, frames, fs, lay, tick, s, f->bus);
-            else fd::fdn_launch_render(f->c, f->st, b->V, pi, po, frames, fs, lay, tick, s, f->bus);
-        };
-        const size_t need = b->V * (size_t)(nin + nout) * frames;
-        if (staged && need > f->stage_n) {
-            if (capturing) staged = false;
-            else {
-                fdn_free_stage(f);  // (hipFree waits for launches that still use the old buffer)
-                if (hipMalloc((void**)&f->stage, need * sizeof(float)) == hipSuccess) f->stage_n = need;
-                else { (void)hipGetLastError(); f->stage = nullptr; staged = false; }   // no room: the kernels' own voice-minor path
-            }
-        }
-        if (staged) {
-            float* pin = f->stage;
-            float* pout = f->stage + b->V * (size_t)nin * frames;
-            fd::fdn_launch_transpose(d_in, pin, b->V, frames, nin, true, s);
-            render(pin, pout, frames, FDSP_LAYOUT_PLANAR);
-            fd::fdn_launch_transpose(pout, d_out, b->V, frames, nout, false, s);
-        } else {
-            render(d_in, d_out, frame_stride, layout);
-        }
-    } else if (b->math == FDSP_MATH_FAST && b->ops->render_fast)
+    if (b->fx)
+        b->fx->render(d_in, d_out, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, capturing, s);
+    else if (b->math == FDSP_MATH_FAST && b->ops->render_fast)
         b->ops->render_fast(b->slots, b->stride, b->V, d_in, d_out, frames, frame_stride, layout, mode, b->aux, b->ring, b->ring_cap, s);
     else
         b->ops->render(b->slots, b->stride, b->V, d_in, d_out, frames, frame_stride, layout, mode, b->aux, b->ring, b->ring_cap, s);
@@ -1955,7 +1486,7 @@ int mix_reserve(fdsp_bank* b, size_t floats) {
 
 int fdsp_bank_set_pan(fdsp_bank* b, const float* h_pan, size_t first, size_t count) {
     if (!b || !h_pan) return fail(FDSP_EINVAL, "bank or h_pan NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
     if (int rc = check_range(b, first, count)) return rc;
     if (count == 0) return FDSP_OK;
@@ -1980,7 +1511,7 @@ int fdsp_bank_set_pan(fdsp_bank* b, const float* h_pan, size_t first, size_t cou
 
 int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
     const size_t nm = (size_t)(fdsp_bank_outputs(b) > 2 ? fdsp_bank_outputs(b) : 2);
     if (b->ops && b->ops->prepare_mix) b->ops->prepare_mix(b->math == FDSP_MATH_FAST && (bool)b->ops->render_mix_fast);  // run-time compiled graphs: build the mix kernels NOW
@@ -1989,7 +1520,7 @@ int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
 
 int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float* d_mix, int mix, int mode, void* stream) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
     if (!d_mix) return fail(FDSP_EINVAL, "d_mix is NULL");
@@ -1997,7 +1528,7 @@ int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float*
     if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
     if (mix != FDSP_MIX_SUM && mix != FDSP_MIX_PAN) return fail(FDSP_EINVAL, "mix takes FDSP_MIX_SUM or FDSP_MIX_PAN");
     if (mix == FDSP_MIX_PAN && fdsp_bank_outputs(b) != 1) return fail(FDSP_EINVAL, "FDSP_MIX_PAN pans a mono graph; this one has " + std::to_string(fdsp_bank_outputs(b)) + " outputs (use FDSP_MIX_SUM)");
-    if (b->fdn) return fail(FDSP_ENOTSUP, "reverb_stereo banks have no fused mix-down: render the instances and call fdsp_sum_voices");
+    if (b->fx) return fail(FDSP_ENOTSUP, "reverb_stereo banks have no fused mix-down: render the instances and call fdsp_sum_voices");
     const bool fast = b->math == FDSP_MATH_FAST && b->ops->render_mix_fast;
     const auto& launch = fast ? b->ops->render_mix_fast : b->ops->render_mix;
     if (!launch) return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' was built without a fused mix-down kernel: render voice-out and call fdsp_sum_voices / fdsp_mix_stereo");
@@ -2036,9 +1567,9 @@ int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float*
 
 int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t frames, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
-    if (b->fdn || !b->ring) return fail(FDSP_EINVAL, "this bank has no ring memory");
+    if (b->fx || !b->ring) return fail(FDSP_EINVAL, "this bank has no ring memory");
     if (!data) return fail(FDSP_EINVAL, "data is NULL");
     if (ring_index < 0 || ring_index >= b->ops->nrings) return fail(FDSP_EINVAL, "ring index out of range");
     if (frames > b->ring_cap) return fail(FDSP_EINVAL, "more frames than the ring capacity given to fdsp_bank_create_ring");
@@ -2058,9 +1589,9 @@ int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t f
 
 int fdsp_bank_set_events(fdsp_bank* b, const double* events, const int* fade, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
-    if (b->fdn) return fail(FDSP_EINVAL, "reverb banks have no event scheduler");
+    if (b->fx) return fail(FDSP_EINVAL, "reverb banks have no event scheduler");
     if (!events) return fail(FDSP_EINVAL, "events is NULL");
     if (int rc = check_range(b, first, count)) return rc;
     for (size_t i = 0; i < count; i++) {  // Sequencer::push asserts (sequencer.rs:366-367)
@@ -2114,7 +1645,7 @@ namespace {
 // Sequencer's output, the sum of the events, to d_mix [outputs][frames]) share everything but the launch
 int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, float* d_mix, int mode, void* stream) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (b->rs) return fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)");
+    if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
     const bool mixing = d_out == nullptr;

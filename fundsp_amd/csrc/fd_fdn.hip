@@ -774,7 +774,7 @@ void fdn_launch_render(const FdnConst& c, const FdnState& s, size_t instances, c
             FD_FDN_CASE(8) FD_FDN_CASE(9) FD_FDN_CASE(10) FD_FDN_CASE(11) FD_FDN_CASE(12) FD_FDN_CASE(13) FD_FDN_CASE(14)
             FD_FDN_CASE(15) FD_FDN_CASE(16) FD_FDN_CASE(17) FD_FDN_CASE(18)
 #undef FD_FDN_CASE
-        default:  // longer than 2^18 slots (5.4 s at 48 kHz): the lane = line kernel takes any capacity (reverb_stereo; fdn_configure
+        default:  // longer than 2^18 slots (5.4 s at 48 kHz): the lane = line kernel takes any capacity (reverb_stereo; HadamardFx::configure
                   // refuses such a reverb4_stereo)
             hipLaunchKernelGGL(k_fdn_render<1>, grid, block, 0, stream, c, s, instances, in, out, T, fstride, layout, bus);
         }

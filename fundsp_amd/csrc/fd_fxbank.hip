@@ -1,0 +1,410 @@
+// fd_fxbank.hip -- the effect banks of fd_fxbank.hpp: buffers, configuration, clone and launch of each family (host code; the kernels are in
+// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip and fd_resynth.hip).
+#include <vector>
+
+#include "fd_fxbank.hpp"
+#include "fd_fdnx.hpp"
+#include "fd_opts.hpp"
+#include "fd_resynth.hpp"
+#include "fd_reverb3.hpp"
+
+namespace fd {
+namespace {
+
+int hip_fail(hipError_t e, const std::string& what) {
+    return api_fail(e == hipErrorOutOfMemory ? FDSP_ENOMEM : FDSP_EDEVICE, what + ": " + hipGetErrorString(e));
+}
+int launch_error() { const hipError_t e = hipGetLastError(); return e == hipSuccess ? FDSP_OK : hip_fail(e, "hipGetLastError()"); }
+
+// A family's device buffers as one list of (pointer, bytes): allocated all or none, freed, and copied (a clone, or what outlives a rate
+// change) by walking it.  An entry of 0 bytes is a buffer the instance does not have: it stays NULL.
+struct Buf { void** p; size_t bytes; };
+using Bufs = std::vector<Buf>;
+
+void free_bufs(const Bufs& l) {
+    for (const Buf& b : l) {
+        if (*b.p) hipFree(*b.p);
+        *b.p = nullptr;
+    }
+}
+hipError_t alloc_bufs(const Bufs& l) {
+    for (const Buf& b : l) *b.p = nullptr;
+    hipError_t e = hipSuccess;
+    for (const Buf& b : l)
+        if (e == hipSuccess && b.bytes) e = hipMalloc(b.p, b.bytes);
+    if (e != hipSuccess) free_bufs(l);
+    return e;
+}
+// entries [first, ..) of `from` into `to` (lists of the same shape) in stream order; entries `from` does not have are skipped
+hipError_t copy_bufs(const Bufs& to, const Bufs& from, hipStream_t s, size_t first = 0) {
+    hipError_t e = hipSuccess;
+    for (size_t i = first; i < to.size() && e == hipSuccess; i++)
+        if (*from[i].p) e = hipMemcpyAsync(*to[i].p, *from[i].p, to[i].bytes, hipMemcpyDeviceToDevice, s);
+    return e;
+}
+// the end of a transactional configuration: entries [first, ..) of the old buffers move into the new ones, the stream drains, the old
+// buffers go (on the first configuration the old list is all NULL: nothing to carry or free)
+void carry_and_free(const Bufs& to, const Bufs& from, size_t first, hipStream_t s) {
+    copy_bufs(to, from, s, first);
+    hipStreamSynchronize(s);
+    free_bufs(from);
+}
+
+// ---- the lane-per-frame networks: rate, bus and the planar staging copy of voice-minor launches ------------------------------------------------
+class NetFx : public FxBank {
+  public:
+    ~NetFx() override { free_stage(); }
+    int inputs() const override { return nin_; }
+    int outputs() const override { return nout_; }
+    FdnBus* bus() override { return &bus_; }
+    int set_sample_rate(double sr, hipStream_t s) override {
+        if (sr == sr_) return FDSP_OK;  // Delay::set_sample_rate: nothing happens unless the rate changes
+        if (hipError_t e = hipStreamSynchronize(s)) return hip_fail(e, "hipStreamSynchronize");
+        return configure(sr, s);
+    }
+    // built the way this instance was (at its creation rate, where it passed validation) and moved to its rate, then every state buffer
+    // is copied (the tables configure computed are already equal)
+    int clone(hipStream_t s, std::unique_ptr<FxBank>* out) override {
+        std::unique_ptr<NetFx> d = fresh();
+        int rc = d->create(sr0_, s);
+        if (rc == FDSP_OK) rc = d->set_sample_rate(sr_, s);
+        if (rc != FDSP_OK) return rc;
+        if (hipError_t e = copy_bufs(d->bufs(), bufs(), s, tables_)) return hip_fail(e, std::string("fdsp_bank_clone: ") + what_ + " state");
+        d->bus_ = bus_;
+        *out = std::move(d);
+        return FDSP_OK;
+    }
+    // Feedback::process is the per-sample tick (feedback.rs:136-146): both modes are the same arithmetic but for the joins (MultiJoin / Join)
+    void render(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, bool capturing, hipStream_t s) override {
+        // voice-minor buffers of banks with at least a tile of instances go through the planar staging copy (the lane = frame kernels read
+        // 256-byte runs of it instead of gathering a line per frame); the staging buffer grows outside captures only, like the partial mixes
+        bool staged = layout == FDSP_LAYOUT_VOICE_MINOR && V_ >= 64 && frames_kernel();
+        const size_t need = V_ * (size_t)(nin_ + nout_) * T;
+        if (staged && need > stage_n_) {
+            if (capturing) staged = false;
+            else {
+                free_stage();  // (hipFree waits for launches that still use the old buffer)
+                if (hipMalloc((void**)&stage_, need * sizeof(float)) == hipSuccess) stage_n_ = need;
+                else { (void)hipGetLastError(); stage_ = nullptr; staged = false; }   // no room: the kernels' own voice-minor path
+            }
+        }
+        if (staged) {
+            float *pin = stage_, *pout = stage_ + V_ * (size_t)nin_ * T;
+            fdn_launch_transpose(in, pin, V_, T, nin_, true, s);
+            launch(pin, pout, T, T, FDSP_LAYOUT_PLANAR, tick, s);
+            fdn_launch_transpose(pout, out, V_, T, nout_, false, s);
+        } else {
+            launch(in, out, T, fstride, layout, tick, s);
+        }
+    }
+    int create(double sr, hipStream_t s) { sr0_ = sr; return configure(sr, s); }   // the first configuration
+
+  protected:
+    NetFx(size_t V, const char* what) : V_(V), what_(what) {}
+    // (re)allocate the lines for a sample rate.  Transactional: the constants are validated and the new buffers allocated BEFORE anything of
+    // the instance changes; on any failure it keeps its old constants, buffers and rate
+    virtual int configure(double sr, hipStream_t s) = 0;
+    virtual std::unique_ptr<NetFx> fresh() const = 0;    // the same network, no buffers yet
+    virtual Bufs bufs() = 0;                             // every state buffer of the current configuration
+    virtual bool frames_kernel() const { return true; }  // the launch takes a lane = frame kernel (the staging copy pays)
+    virtual void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) = 0;
+    void free_stage() { if (stage_) hipFree(stage_); stage_ = nullptr; stage_n_ = 0; }
+
+    size_t V_, tables_ = 0;         // instances; leading entries of bufs() that configure computes from the description
+    double sr0_ = 0.0, sr_ = 0.0;   // the creation rate, the current one
+    int nin_ = 2, nout_ = 2;
+    FdnBus bus_;
+    const char* what_;
+    float* stage_ = nullptr;   // planar staging of voice-minor launches: [V][inputs][frames] | [V][outputs][frames] (fd_fdn.hip "voice-minor I/O")
+    size_t stage_n_ = 0;
+};
+
+// reverb_stereo, reverb4_stereo and the generic network (fd_fdn.hpp): one kernel family, three ways to make its constants
+class HadamardFx final : public NetFx {
+  public:
+    enum Kind { REVERB, REVERB4, GENERIC };
+    HadamardFx(Kind kind, double room, double time, double damping, const FdnDesc& desc, size_t V)
+        : NetFx(V, "reverb"), kind_(kind), room_(room), time_(time), damping_(damping), desc_(desc) {}
+    ~HadamardFx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { fdn_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+
+  private:
+    int configure(double sr, hipStream_t s) override {
+        FdnConst c;
+        if (kind_ == GENERIC) fdn_make_const_generic(desc_, sr, &c);
+        else if (kind_ == REVERB4) fdn_make_const_reverb4(room_, time_, sr, &c);
+        else fdn_make_const(room_, time_, damping_, sr, &c);
+        for (int i = 0; i < c.lines; i++)
+            if (c.len[i] <= 128)
+                return api_fail(FDSP_EINVAL, kind_ == GENERIC ? "fdsp_fdn_create: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)"
+                                                               : "reverb_stereo / reverb4_stereo: every delay must exceed 128 samples (room_size * sample_rate too small)");
+        if (kind_ != REVERB && c.cap > (1 << 18))
+            return api_fail(FDSP_EINVAL, "reverb4_stereo / fdsp_fdn_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
+        FdnState st{};
+        if (hipError_t e = alloc_bufs(bufs(c, st))) return hip_fail(e, "reverb_stereo buffers");
+        // The new lines start empty (Delay::set_sample_rate resizes and resets, delay.rs:105-113) -- but a change of rate resets nothing else: the
+        // FIRs keep their two samples of history (Fir::set_sample_rate, fir.rs:52-54) and Feedback its value (feedback.rs:125-127), so a tail that
+        // is sounding when the rate changes goes on from those, exactly like the reference's
+        fdn_launch_reset(c, st, V_, s);
+        carry_and_free(bufs(c, st), bufs(c_, st_), 2, s);   // v1, v2, fb
+        c_ = c; st_ = st; sr_ = sr;
+        nin_ = c.nin; nout_ = c.nout;
+        return launch_error();
+    }
+    Bufs bufs(const FdnConst& c, FdnState& st) const {
+        const size_t n = V_;
+        return {{(void**)&st.rings, n * c.ring_stride * sizeof(float)}, {(void**)&st.wpos, n * sizeof(int)}, {(void**)&st.v1, n * 32 * sizeof(float)},
+                {(void**)&st.v2, n * 32 * sizeof(float)}, {(void**)&st.fb, n * 32 * sizeof(float)}};
+    }
+    Bufs bufs() override { return bufs(c_, st_); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<HadamardFx>(kind_, room_, time_, damping_, desc_, V_); }
+    bool frames_kernel() const override { return c_.generic || tl_opts.fdn_kernel == 0 || c_.sections == 2; }
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) override { fdn_launch_render(c_, st_, V_, in, out, T, fstride, layout, tick, s, bus_); }
+
+    Kind kind_;
+    double room_, time_, damping_;
+    FdnDesc desc_;
+    FdnConst c_{};
+    FdnState st_{};
+};
+
+// reverb3_stereo (fd_reverb3.hpp): what the reference's Reverb::set_sample_rate leaves alone survives a new rate (the `pre` diffusers
+// entirely; every allpass's z, the feedback sample and the filters' values: rv3_launch_migrate); the first configuration zeroes everything
+class Reverb3Fx final : public NetFx {
+  public:
+    Reverb3Fx(double time, double diffusion, const Rv3Filter& flt, size_t V) : NetFx(V, "reverb3"), time_(time), diffusion_(diffusion), flt_(flt) {}
+    ~Reverb3Fx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { rv3_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+
+  private:
+    int configure(double sr, hipStream_t s) override {
+        Rv3Const c;
+        if (!rv3_make_const(time_, diffusion_, flt_, sr, &c))
+            return api_fail(FDSP_EINVAL, "reverb3_stereo: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule; >= 14.2 kHz)");
+        const bool first = st_.pre == nullptr;
+        Rv3State st = st_;   // (pre, wpre and fval are allocated once)
+        if (hipError_t e = alloc_bufs(bufs(c, st, first))) return hip_fail(e, "reverb3_stereo buffers");
+        if (first) rv3_launch_init(c, st, V_, s);
+        else {
+            // the new lines start empty; pre / filter values stay where they are; z and the feedback sample move over
+            hipMemsetAsync(st.rings, 0, V_ * c.ring_stride * sizeof(float), s);
+            hipMemsetAsync(st.wpos, 0, V_ * sizeof(int), s);
+            rv3_launch_migrate(c_, st_, c, st, V_, s);
+        }
+        carry_and_free(bufs(c, st, false), bufs(c_, st_, false), 2, s);   // (the old lines go, nothing to carry)
+        c_ = c; st_ = st; sr_ = sr;
+        return launch_error();
+    }
+    // the lines of a rate (rings, write positions), with `all` also what outlives a rate change
+    Bufs bufs(const Rv3Const& c, Rv3State& st, bool all) const {
+        const size_t n = V_;
+        Bufs l = {{(void**)&st.rings, n * c.ring_stride * sizeof(float)}, {(void**)&st.wpos, n * sizeof(int)}};
+        if (all) l.insert(l.end(), {{(void**)&st.pre, n * 4 * (RV3_PRE_CAP + 64) * sizeof(float)}, {(void**)&st.wpre, n * sizeof(int)}, {(void**)&st.fval, n * 32 * sizeof(float)}});
+        return l;
+    }
+    Bufs bufs() override { return bufs(c_, st_, true); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<Reverb3Fx>(time_, diffusion_, flt_, V_); }
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int, hipStream_t s) override {
+        rv3_launch_render(c_, st_, V_, in, out, T, fstride, layout, s, bus_);   // (Reverb has no process override: one arithmetic)
+    }
+
+    double time_, diffusion_;
+    Rv3Filter flt_;
+    Rv3Const c_{};
+    Rv3State st_{};
+};
+
+// filtered / per-instance networks (fd_fdnx.hpp): the table and the lines for a sample rate.  The new rings start empty (Delay::set_sample_rate,
+// delay.rs:105-113), the coefficients follow the rate (filter.rs:58-61, svf.rs:989-992), and the Fir carry, the filter states and the feedback
+// value stay (fir.rs:52-54, feedback.rs:125-127, 254-257)
+class FdnxFx final : public NetFx {
+  public:
+    FdnxFx(const FdnxDesc& d, size_t V) : NetFx(V, "network"), d_(d) { tables_ = 1; }
+    ~FdnxFx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { fdnx_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+
+  private:
+    int configure(double sr, hipStream_t s) override {
+        std::vector<FdnxInst> tab;
+        FdnxConst c;
+        const int shortest = fdnx_make_table(d_, V_, sr, tab, &c);
+        if (shortest < 0) return api_fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
+        if (shortest < 128)
+            return api_fail(FDSP_EINVAL, "fdsp_fdn_network_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+        FdnxState st{};
+        hipError_t e = alloc_bufs(bufs(c, st));
+        if (e == hipSuccess && (e = hipMemcpyAsync((void*)c.tab, tab.data(), tab.size() * sizeof(FdnxInst), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st));
+        if (e != hipSuccess) return hip_fail(e, "fdsp_fdn_network_create buffers");
+        fdnx_launch_reset(c, st, V_, s);
+        carry_and_free(bufs(c, st), bufs(c_, st_), 3, s);   // v1, v2, fb, s1, s2 (and the stream drains before `tab` goes)
+        c_ = c; st_ = st; sr_ = sr;
+        nin_ = c.nin; nout_ = c.nout;
+        return launch_error();
+    }
+    Bufs bufs(FdnxConst& c, FdnxState& st) const {
+        const size_t n = V_;
+        return {{(void**)&c.tab, (c.tab_stride ? n : 1) * sizeof(FdnxInst)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)},
+                {(void**)&st.wpos, n * sizeof(int)}, {(void**)&st.v1, n * 32 * sizeof(float)}, {(void**)&st.v2, n * 32 * sizeof(float)},
+                {(void**)&st.fb, n * 32 * sizeof(float)}, {(void**)&st.s1, n * 32 * sizeof(float)}, {(void**)&st.s2, n * 32 * sizeof(float)}};
+    }
+    Bufs bufs() override { return bufs(c_, st_); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<FdnxFx>(d_, V_); }
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) override { fdnx_launch_render(c_, st_, V_, in, out, T, fstride, layout, tick, s, bus_); }
+
+    FdnxDesc d_;
+    FdnxConst c_{};
+    FdnxState st_{};
+};
+
+int make_net(std::unique_ptr<NetFx> f, double sr, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    if (int rc = f->create(sr, s)) return rc;
+    *out = std::move(f);
+    return FDSP_OK;
+}
+
+// ---- resynthesizer banks (fd_resynth.hpp): tables, frame ring, input ring, device sample counter -------------------------------------------
+class ResynthFx final : public FxBank {
+  public:
+    // (the table pointers of `c` are another instance's)
+    ResynthFx(const RsConst& c, int ftz, size_t V) : c_(c), ftz_(ftz), V_(V) { for (const Buf& b : bufs()) *b.p = nullptr; }
+    ~ResynthFx() override { free_bufs(bufs()); }
+    int inputs() const override { return c_.I; }
+    int outputs() const override { return c_.O; }
+    // FftWindow::set_sample_rate: frequency() follows, every other state stays (resynth.rs:170-172, 325-330).  The bin spacing lives in device
+    // memory, in stream order behind the last render: a captured launch replays with the new rate
+    int set_sample_rate(double sr, hipStream_t s) override {
+        const float fstep = (float)sr / (float)c_.N;
+        hipError_t e = hipMemcpyAsync(st_.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (fstep is a local)
+        return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_bank_set_sample_rate");
+    }
+    // Resynth::reset: the sample count and the four windows start over (resynth.rs:332-337)
+    hipError_t reset(hipStream_t s) override { return hipMemsetAsync(st_.samples, 0, sizeof(unsigned long long), s); }
+    // a new bank with zero band / gain tables, then everything but the window and twiddle tables copied over
+    int clone(hipStream_t s, std::unique_ptr<FxBank>* out) override {
+        auto d = std::make_unique<ResynthFx>(c_, ftz_, V_);
+        const Bufs l = bufs();
+        const std::vector<float> band(l[7].bytes / sizeof(float)), gain(l[8].bytes / sizeof(float));
+        if (int rc = d->init(band.data(), gain.data(), s)) return rc;
+        if (hipError_t e = copy_bufs(d->bufs(), l, s, 3)) return hip_fail(e, "fdsp_bank_clone: resynthesizer state");
+        *out = std::move(d);
+        return FDSP_OK;
+    }
+    // Resynth has no process override: FDSP_MODE_PROCESS == FDSP_MODE_TICK
+    void render(const float* in, float* out, size_t T, size_t fstride, int layout, int, bool, hipStream_t s) override {
+        (ftz_ ? rs_ftz::rs_launch_render : rs_ieee::rs_launch_render)(c_, st_, V_, in, out, T, fstride, layout, s);
+    }
+    // the buffers, the tables uploaded (band [rows][O][2] and gain [rows][O][N/2 + 1] where the processor has them), empty windows at 44.1 kHz
+    int init(const float* band, const float* gain, hipStream_t s) {
+        const Bufs l = bufs();
+        const float fstep = (float)FDSP_DEFAULT_SR / (float)c_.N;
+        std::vector<float> tw(c_.N), hann(c_.N), hz(c_.N);
+        rs_tables(c_.N, hann.data(), hz.data(), tw.data());
+        hipError_t e = alloc_bufs(l);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.tw, tw.data(), l[0].bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.hann, hann.data(), l[1].bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.hz, hz.data(), l[2].bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && c_.band) e = hipMemcpyAsync((void*)c_.band, band, l[7].bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && c_.gain) e = hipMemcpyAsync((void*)c_.gain, gain, l[8].bytes, hipMemcpyHostToDevice, s);
+        // reset: the windows start empty (nothing is read before a frame of this run exists, but the rings start defined)
+        if (e == hipSuccess) e = hipMemsetAsync(st_.samples, 0, sizeof(unsigned long long), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(st_.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(st_.frames, 0, l[3].bytes, s);
+        if (e == hipSuccess) e = hipMemsetAsync(st_.xin, 0, l[4].bytes, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_resynth_create buffers");
+    }
+    Bufs bufs() {   // the constant tables first
+        const size_t N = (size_t)c_.N, rows = (size_t)c_.rows * c_.O;
+        return {{(void**)&c_.tw, N / 2 * sizeof(float2)}, {(void**)&c_.hann, N * sizeof(float)}, {(void**)&c_.hz, N * sizeof(float)},
+                {(void**)&st_.frames, (size_t)c_.R * V_ * c_.O * N * sizeof(float)}, {(void**)&st_.xin, V_ * (size_t)c_.I * c_.Rx * sizeof(float)},
+                {(void**)&st_.samples, sizeof(unsigned long long)}, {(void**)&st_.fstep, sizeof(float)},
+                {(void**)&c_.band, c_.proc == RS_BAND ? rows * sizeof(float2) : 0}, {(void**)&c_.gain, c_.proc == RS_GAIN ? rows * (N / 2 + 1) * sizeof(float) : 0}};
+    }
+
+    RsConst c_;
+    RsState st_{};
+    int ftz_;   // 1: the flush-to-zero instantiation (a Feedback node in front)
+    size_t V_;
+};
+
+}  // namespace
+
+int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    const HadamardFx::Kind kind = sections == 2 ? HadamardFx::REVERB4 : HadamardFx::REVERB;
+    return make_net(std::make_unique<HadamardFx>(kind, room_size, time, damping, FdnDesc(), instances), FDSP_DEFAULT_SR, s, out);
+}
+int fx_fdn(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, hipStream_t s,
+           std::unique_ptr<FxBank>* out) {
+    FdnDesc d{lines, taps, inputs, outputs};
+    for (int i = 0; i < lines; i++) d.delay[i] = delays[i];
+    for (int j = 0; j < taps; j++) d.w[j] = weights[j];
+    return make_net(std::make_unique<HadamardFx>(HadamardFx::GENERIC, 1.0, 1.0, 0.0, d, instances), FDSP_DEFAULT_SR, s, out);
+}
+int fx_reverb3_stereo(size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, hipStream_t s,
+                      std::unique_ptr<FxBank>* out) {
+    const Rv3Filter f{svf_mode < 0 ? 0 : 1, svf_mode < 0 ? 0 : svf_mode, cutoff, q, gain};
+    return make_net(std::make_unique<Reverb3Fx>(time, diffusion, f, instances), FDSP_DEFAULT_SR, s, out);
+}
+int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    FdnxDesc d{net.lines, net.taps, net.inputs, net.outputs, net.filter, net.svf_mode, net.place, net.per_instance ? 1 : 0, net.line_gain ? 1 : 0};
+    const size_t M = (d.per_instance ? instances : 1) * (size_t)net.lines;
+    d.delay.assign(net.delays, net.delays + M);
+    if (net.taps > 0) d.w.assign(net.weights, net.weights + M * net.taps);
+    if (net.filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net.cutoff, net.cutoff + M);
+    if (net.filter == FDSP_FDN_FILTER_SVF) d.q.assign(net.q, net.q + M);
+    if (net.filter == FDSP_FDN_FILTER_SVF && net.svf_mode >= FDSP_SVF_BELL) d.gain.assign(net.gain, net.gain + M);
+    if (d.has_gain) d.line_gain.assign(net.line_gain, net.line_gain + M);
+    return make_net(std::make_unique<FdnxFx>(d, instances), sample_rate, s, out);
+}
+
+int fx_resynth(size_t instances, const fdsp_resynth_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    const int N = sp.window_length, H = N / 4, O = sp.outputs;
+    const size_t V = instances;
+    RsConst c{};
+    c.N = N;
+    while ((1 << c.logN) < N) c.logN++;
+    c.I = sp.inputs;
+    c.O = O;
+    c.proc = sp.processor;
+    for (int o = 0; o < RS_MAX_CH; o++) c.src[o] = o < O ? sp.source[o] : -1;
+    c.rows = sp.per_instance ? (int)V : 1;
+    c.invN = 1.0f / (float)N;
+    // frame ring: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large
+    size_t R = ((size_t)256 << 20) / (V * (size_t)O * N * sizeof(float));
+    const size_t rmax = 5 + 65536 / (size_t)H;
+    R = R < 8 ? 8 : (R > rmax ? rmax : R);
+    c.R = (int)R;
+    c.Lmax = (c.R - 5) * H;
+    c.Rx = 1;
+    while (c.Rx < c.Lmax + N) c.Rx <<= 1;
+    std::vector<float> band;
+    if (c.proc == FDSP_RESYNTH_BAND)
+        for (size_t i = 0; i < (size_t)c.rows * O; i++) band.insert(band.end(), {sp.lo_hz[i], sp.hi_hz[i]});
+    auto r = std::make_unique<ResynthFx>(c, sp.flush_denormals, V);
+    if (int rc = r->init(band.data(), sp.gain, s)) return rc;
+    *out = std::move(r);
+    return FDSP_OK;
+}
+
+int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats) {
+    auto* r = dynamic_cast<ResynthFx*>(fx);
+    if (!r) return api_fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: not a resynthesizer bank");
+    const RsConst& c = r->c_;
+    if (c.proc != (gain ? FDSP_RESYNTH_GAIN : FDSP_RESYNTH_BAND))
+        return api_fail(FDSP_EINVAL, gain ? "fdsp_resynth_set_gain: the bank's processor is not FDSP_RESYNTH_GAIN" : "fdsp_resynth_set_band: the bank's processor is not FDSP_RESYNTH_BAND");
+    const size_t rows = (size_t)c.rows;
+    if (first > rows || count > rows - first) return api_fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: rows out of range (one row per instance with per_instance, else the single row 0)");
+    *row_floats = (size_t)c.O * (gain ? (size_t)(c.N / 2 + 1) : 2);
+    *row0 = (gain ? (float*)c.gain : (float*)c.band) + first * *row_floats;
+    return FDSP_OK;
+}
+
+}  // namespace fd
+
+extern "C" int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles) {
+    const int N = window_length;
+    if (N < 4 || N > 8192 || (N & (N - 1)) != 0) return fd::api_fail(FDSP_EINVAL, "fdsp_resynth_tables: window_length takes a power of two from 4 to 8192");
+    fd::rs_tables(N, h_hann, nullptr, h_twiddles);
+    return FDSP_OK;
+}

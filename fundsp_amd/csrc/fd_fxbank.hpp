@@ -1,0 +1,48 @@
+// fd_fxbank.hpp -- the effect banks: banks of one stock node per instance instead of a voice graph of slots -- the Hadamard networks
+// (reverb_stereo, reverb4_stereo, the generic `fdn`: fd_fdn.hpp), reverb3_stereo (fd_reverb3.hpp), the filtered / per-instance networks
+// (fd_fdnx.hpp) and the resynthesizer (fd_resynth.hpp).  fd_capi.hip keeps the bank handle (stream, events, pan weights, launch options)
+// and the public constructors' argument checks; what a family allocates, configures, copies and launches is behind FxBank (fd_fxbank.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include <memory>
+#include <string>
+
+#include "../../include/fundsp_hip.h"
+#include "fd_fdn.hpp"   // FdnBus
+
+namespace fd {
+
+int api_fail(int code, const std::string& msg);  // fd_capi.hip: records fdsp_last_error() for this thread
+
+// Work goes to the stream given; the caller owns the waits around it.  int results are FDSP_* codes with fdsp_last_error() set.
+struct FxBank {
+    virtual ~FxBank() = default;   // frees every device buffer the instance allocated
+    virtual int inputs() const = 0;
+    virtual int outputs() const = 0;
+    virtual FdnBus* bus() { return nullptr; }   // nullptr: the resynthesizer, which renders through fdsp_bank_process only
+    // a network changes nothing unless the rate changes and reconfigures transactionally: on failure it keeps its rate and state
+    virtual int set_sample_rate(double sr, hipStream_t stream) = 0;
+    virtual hipError_t reset(hipStream_t stream) = 0;
+    // a new instance that continues exactly where this one stands (state copied on `stream`, bus included)
+    virtual int clone(hipStream_t stream, std::unique_ptr<FxBank>* out) = 0;
+    virtual void render(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, bool capturing, hipStream_t stream) = 0;
+};
+
+// The factories build and initialise an instance on `stream`.  The arguments are checked by the caller; what can still fail is the
+// kernels' delay rule at the creation rate (44.1 kHz but for fx_fdn_network) and the allocation.
+// sections 1: reverb_stereo(room_size, time, damping), 2: reverb4_stereo(room_size, time)
+int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t stream, std::unique_ptr<FxBank>* out);
+int fx_fdn(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, hipStream_t stream,
+           std::unique_ptr<FxBank>* out);
+// svf_mode < 0: lowpole_hz(cutoff) in the loop, else FixedSvf(svf_mode, cutoff, q, gain)
+int fx_reverb3_stereo(size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, hipStream_t stream,
+                      std::unique_ptr<FxBank>* out);
+int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t stream, std::unique_ptr<FxBank>* out);
+int fx_resynth(size_t instances, const fdsp_resynth_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// fdsp_resynth_set_band / _gain: checks the bank (`fx` may be NULL) and the rows; the device address of row `first` and the floats per row
+int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats);
+
+}  // namespace fd

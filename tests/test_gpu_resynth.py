@@ -127,7 +127,11 @@ def test_lifecycle_reset_clone_sample_rate_set_gain(gpu):
     # set_sample_rate mid-stream: the BAND bins move, the windows keep their state; clone mid-stream continues the same
     b.reset()
     run_bank(b, x1, T1, LAYOUT_VOICE_MINOR, MODE_PROCESS)
+    opts = {"math": F.MATH_FAST, "pipe_split": 0, "time_split": 2, "fdn_kernel": 1, "timing": 0}
+    for name, value in opts.items():
+        b.set_option(name, value)
     c = b.clone()
+    assert {name: c.get_option(name) for name in opts} == opts, "a clone carries the arithmetic mode and every launch option"
     b.set_sample_rate(22050.0)
     c.set_sample_rate(22050.0)
     want = R.render(x, N, processor="band", band=(1000.0, 9000.0), changes=[(T1, dict(sample_rate=22050.0))], tabs=tabs(N))
