@@ -9,13 +9,17 @@ One step = one pass of the hot path: render FRAMES samples of every voice of the
 
 Multi-GPU (`--gpus N`, one process per GPU): the headline is STRONG scaling -- the metric's 65 536 voices in total,
 sharded as contiguous ranges of 65 536 / N voices per GPU, no data-path collective.  `--scaling weak` keeps 65 536 voices
-per GPU instead; at N > 1 the weak figure is also measured (outside the timed region) and reported as
+per GPU instead; at N > 1 a `--full` run also measures the weak figure (outside the timed region) and reports it as
 `config.scaling_alt`.  `--mix` adds the on-device stereo mix-down + one RCCL all-reduce of [2][frames] per step.
 
-Prints ONE JSON line on rank 0 (contract in the round brief) with `ms_per_step`, `roofline` and `cpu_baseline`.  At N = 1 the
-`secondary` list, measured after the timed region (the tolerance mode of the same workload, BASELINE configs 2, 4, 5, the
-reference's criterion benches), goes to stderr as a JSON line of its own.  `--dump-outputs DIR` writes what the last timed
-step computed; the timed steps start from the bank's initial state, so runs with the same arguments compute the same samples.
+Prints ONE JSON line on rank 0 with `ms_per_step` and `roofline` (the timed steps' own kernel times and socket power).  A plain run
+does only what that line needs: set up, spin up, warm up, time the K steps, write `--dump-outputs`, print.  `--full` adds what is
+measured or checked beside the headline, all after the timed region: `cpu_baseline` (the CPU restatement of the same workload on
+this host), `roofline.measured_streaming` (copy / fill kernels), the committed PMC / VALU records quoted in `roofline` when they
+match this kernel, `config.scaling_alt` at N > 1, and at N = 1 the `secondary` list (the tolerance mode of the same workload,
+BASELINE configs 2, 4, 5, the reference's criterion benches), which goes to stderr as a JSON line of its own.  `--dump-outputs
+DIR` writes what the last timed step computed; the timed steps start from the bank's initial state, so runs with the same
+arguments compute the same samples.
 """
 import argparse
 import atexit
@@ -984,9 +988,12 @@ def parse_args(argv=None):
                          "launches of one note with the Var slot set on the device in between (default); stream = the gate as an audio-rate HBM input [frames][voices]")
     ap.add_argument("--reverb", choices=["stereo", "4", "3"], default="stereo",
                     help="--config 5: stereo = reverb_stereo(10, 2, 0.5), BASELINE config 5 (default); 4 = reverb4_stereo(20, 2), two 16-line networks in series; 3 = reverb3_stereo(2, 0.5, lowpole_hz(8000)), the allpass-loop reverb (624 B per instance-frame)")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="wall-time budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: cpu_baseline, the streaming "
+                         "copy / fill, the committed PMC / VALU records, scaling_alt at N > 1, the secondary list at N = 1 (off: a plain run)")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="--full: wall-time budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--criterion", action="store_true", help="only the reference's own criterion benches (benches/benchmark.rs) as banks: one JSON line {\"criterion\": ..}")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs 2 / 4 / 5, tolerance mode)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (configs 2 / 4 / 5, tolerance mode)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32; at most 64 MB in all: a fixed, seeded "
                          "sample of whole voices when an output is larger) -- out = the voice-out buffer, mix = the stereo mix-down of --mix; "
@@ -1123,8 +1130,13 @@ def headline_kernel_source_hash():
 
 
 def cpu_baseline_wanted(args, rank, world):
-    """The headline's cpu_baseline leg runs on rank 0 of EVERY run of the headline config, whatever the number of GPUs."""
-    return rank == 0 and world >= 1 and args.cpu_seconds > 0 and args.config == 3
+    """The headline's cpu_baseline leg runs on rank 0 of every --full run of the headline config, whatever the number of GPUs."""
+    return args.full and rank == 0 and world >= 1 and args.cpu_seconds > 0 and args.config == 3
+
+
+def secondary_wanted(args, world):
+    """The secondary list: --full runs of the headline config in exact arithmetic on one GPU."""
+    return args.full and world == 1 and not args.no_secondary and args.config == 3 and args.math == "exact"
 
 
 def fused_mix(args, F, layout):
@@ -1390,7 +1402,7 @@ def run_rank(args, torch, F, peers, device):
             np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if distributed else "") + ".npy"), x.float().cpu().numpy())
     total_voices = base_voices if args.scaling == "strong" else base_voices * world
     scaling_alt = None
-    if distributed and args.config == 3:   # the other scaling law, outside the timed region, a few steps
+    if args.full and distributed and args.config == 3:   # the other scaling law, outside the timed region, a few steps
         other = "weak" if args.scaling == "strong" else "strong"
         kernel_label, shard_bps, shard_slots, power = wl["kernel"], wl["bps"], wl["slot_bytes"], wl.get("power")
         del wl
@@ -1406,10 +1418,10 @@ def run_rank(args, torch, F, peers, device):
     if rank != 0:
         return None
 
-    # also relate the kernel to what this box's HBM delivers to plain streaming kernels (a 2 GiB
+    # SURVEY.md 8(d), --full: also relate the kernel to what this box's HBM delivers to plain streaming kernels (a 2 GiB
     # device-to-device copy = read + write, and a fill = write only, the kernel's own traffic shape), outside the timed region
     measured = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         n = 1 << 29
         a = torch.empty(n, dtype=torch.float32, device="cuda")
         b2 = torch.empty(n, dtype=torch.float32, device="cuda")
@@ -1437,10 +1449,10 @@ def run_rank(args, torch, F, peers, device):
         algo_bytes = V * T * shard_bps + V * shard_slots
         achieved = algo_bytes / (avg_ms * 1e-3) / 1e9
         # HBM traffic comes from separate rocprofv3 --pmc passes of this same command (it cannot be collected inside this
-        # process): the committed summary is quoted, with its source, when it was taken on this very shard shape
+        # process): --full quotes the committed summary, with its source, when it was taken on this very shard shape
         traffic, traffic_source = None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc):
+        if args.full and os.path.exists(pmc):
             try:
                 rec = json.load(open(pmc))
                 if rec.get("voices") == V and rec.get("frames") == T and rec.get("config", 3) == args.config and rec.get("math", "exact") == args.math:
@@ -1454,11 +1466,11 @@ def run_rank(args, torch, F, peers, device):
                                           "not quoted -- rerun tools/pmc_hbm_pass.sh + tools/pmc_latest.py")
             except Exception:
                 traffic = None
-        # the VALU view (the kernel is issue-bound, so the HBM fraction alone says little): instruction counts
+        # --full, the VALU view (the kernel is issue-bound, so the HBM fraction alone says little): instruction counts
         # and cycles from the committed SQ pass + ISA listing (tools/valu_view.py), the flop rate from THIS run's kernel time
         valu = None
         vpath = os.path.join(ROOT, "profiles", "valu_latest.json")
-        if os.path.exists(vpath):
+        if args.full and os.path.exists(vpath):
             try:
                 rec = json.load(open(vpath))
                 if rec.get("voices") == V and rec.get("frames") == T and rec.get("config", 3) == args.config and rec.get("math", "exact") == args.math:
@@ -1530,13 +1542,13 @@ def run_rank(args, torch, F, peers, device):
                 "power": power,
             },
         }
-        # the CPU path "in the same run" (north_star): on rank 0, after the timed region -- at N > 1 too (the other ranks wait at the
+        # --full: the CPU path "in the same run" (north_star): on rank 0, after the timed region -- at N > 1 too (the other ranks wait at the
         # run's last barrier)
         if cpu_baseline_wanted(args, peers.rank, world):
             res["cpu_baseline"] = cpu_baseline(total_voices, T, sr, args.cpu_seconds)
         else:
             res["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary and args.config == 3 and args.math == "exact":
+        if secondary_wanted(args, world):
             try:
                 res["secondary"] = secondary(F, W, torch, sr, mode)
                 if measured:  # the HBM-side entries next to what this box's memory system streams (the fill / copy kernels timed above)

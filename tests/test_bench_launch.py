@@ -100,11 +100,23 @@ def test_cpu_baseline_counts_the_cpus_the_process_may_use(tmp_path):
 
 
 def test_cpu_baseline_runs_on_rank_0_of_multi_gpu_runs_too():
-    """north_star: the CPU path is timed "in the same run" next to the 1/2/4/8-GPU numbers (it used to be null at N > 1)."""
-    a = bench.parse_args(["--gpus", "2"])
+    """north_star: a --full run times the CPU path "in the same run" next to the 1/2/4/8-GPU numbers (it used to be null at N > 1)."""
+    a = bench.parse_args(["--gpus", "2", "--full"])
     assert bench.cpu_baseline_wanted(a, 0, 2) and bench.cpu_baseline_wanted(a, 0, 8) and bench.cpu_baseline_wanted(a, 0, 1)
     assert not bench.cpu_baseline_wanted(a, 1, 2)
-    assert not bench.cpu_baseline_wanted(bench.parse_args(["--gpus", "2", "--cpu-seconds", "0"]), 0, 2)
+    assert not bench.cpu_baseline_wanted(bench.parse_args(["--gpus", "2", "--full", "--cpu-seconds", "0"]), 0, 2)
+    assert not bench.cpu_baseline_wanted(bench.parse_args(["--gpus", "2"]), 0, 2)   # a plain run: the headline alone
+
+
+def test_only_full_runs_measure_beside_the_headline():
+    """A plain run sets up, warms up, times its steps and prints; the CPU legs and the secondary list belong to --full."""
+    plain, full = bench.parse_args([]), bench.parse_args(["--full"])
+    assert not plain.full and full.full
+    assert not bench.cpu_baseline_wanted(plain, 0, 1) and not bench.secondary_wanted(plain, 1)
+    assert bench.cpu_baseline_wanted(full, 0, 1) and bench.secondary_wanted(full, 1)
+    assert not bench.secondary_wanted(full, 2)
+    for argv in (["--no-secondary"], ["--math", "fast"], ["--config", "2"]):
+        assert not bench.secondary_wanted(bench.parse_args(["--full"] + argv), 1)
 
 
 def test_secondary_cpu_baselines_are_the_native_monomorphised_legs():
