@@ -41,6 +41,11 @@ class ResynthSpec(C.Structure):
                 ("flush_denormals", _i), ("lo_hz", _fp), ("hi_hz", _fp), ("gain", _fp)]
 
 
+class ConvolveSpec(C.Structure):
+    """struct fdsp_convolve_spec (include/fundsp_hip.h)"""
+    _fields_ = [("channels", _i), ("max_len", _sz), ("len", _sz), ("per_instance", _i), ("flush_denormals", _i), ("response", _fp)]
+
+
 SYMBOLS = {
     "fdsp_last_error": (_cs, []),
     "fdsp_kind_count": (_i, []),
@@ -77,6 +82,10 @@ SYMBOLS = {
     "fdsp_resynth_set_band": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_resynth_set_gain": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_resynth_tables": (_i, [_i, _fp, _fp]),
+    "fdsp_convolve_create": (_i, [_sz, C.POINTER(ConvolveSpec), C.POINTER(_P)]),
+    "fdsp_convolve_create_on": (_i, [_i, _sz, C.POINTER(ConvolveSpec), C.POINTER(_P)]),
+    "fdsp_convolve_set_response": (_i, [_P, _fp, _sz, _sz, _sz]),
+    "fdsp_convolve_block_length": (_i, [_sz]),
     "fdsp_bank_set_bus": (_i, [_P, _i, _f, _f]),
     "fdsp_bank_get_bus": (_i, [_P, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f)]),
     "fdsp_jit_compiler": (C.c_char_p, []),

@@ -67,7 +67,27 @@ class Bank:
             if sample_rate is not None:
                 b.set_sample_rate(sample_rate)
             return b
+        cv = G.convolve_plan(graph)
+        if cv is not None:   # convolve(..) or a stack convolve(..) | convolve(..) | ..: one convolver bank, one channel each (fdsp_convolve_create)
+            b = cls.convolve(voices, cv, flush_denormals=flush_denormals)
+            if sample_rate is not None:
+                b.set_sample_rate(sample_rate)
+            return b
         parts = getattr(graph, "pipe_parts", None)
+        cv = G.convolve_plan(parts[1]) if parts is not None else None
+        if cv is not None and not G.has_convolve(parts[0]) and not G.has_resynth(parts[0]):
+            # `front >> convolve(..)` / `front >> (convolve(..) | convolve(..))`: the path of `front >> resynth(..)` below -- the front keeps its
+            # fused kernel and is seeded from the whole graph's construction hash (Convolver::ID = 100 enters it through the probe's ConvolvePing)
+            ftz = flush_denormals or "Feedback" in parts[0].type
+            eff = cls.convolve(voices, cv, flush_denormals=ftz)
+            if sample_rate is not None:
+                eff.set_sample_rate(sample_rate)
+            src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, fdn_kernel=fdn_kernel, flush_denormals=ftz)
+            return Chain(src, eff, construction_hash=probe_hash(graph))
+        if G.has_convolve(graph):
+            raise ValueError("convolve(..) renders as a whole graph, as a stack of convolvers `convolve(..) | convolve(..)`, or as the last node "
+                             "of a pipe, `front >> convolve(..)` / `front >> (convolve(..) | convolve(..))` (a Chain); inside any other stack, a "
+                             "sum, bus or feedback, or followed by more nodes, it is not supported")
         if parts is not None and getattr(parts[1], "resynth_plan", None) is not None and not G.has_resynth(parts[0]):
             # `front >> resynth(..)` -- the reference's criterion bench noise() >> resynth::<U1, U1, _>(1024, ..): the front keeps its fused kernel,
             # the resynthesizer its FFT kernels; the front is seeded from the whole graph's construction hash (Resynth::ID = 80 enters it through the
@@ -310,6 +330,39 @@ class Bank:
         b.window = N
         return b
 
+    @classmethod
+    def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None):
+        """Bank of `instances` x `channels` convolvers, convolve(&wave, channel) (convolve.rs) per channel, through the partitioned FFT
+        convolution kernels (fdsp_convolve_create): y[n] = sum h[k] x[n - k], no latency, every split into launches the same bits.
+        `response`: [len] or [channels, len], with per_instance=True [instances, channels, len].  `channels` defaults to the response's
+        (a [len] response is given to every channel when `channels` says more than one); `max_len` is the capacity set_response can
+        fill later (default: len)."""
+        V = int(instances)
+        h = convolve_response_rows(response, channels, V if per_instance else None)
+        spec = _lib.ConvolveSpec()
+        spec.channels, spec.len = h.shape[-2], h.shape[-1]
+        spec.max_len = int(max_len) if max_len is not None else h.shape[-1]
+        spec.per_instance = 1 if per_instance else 0
+        spec.flush_denormals = 1 if flush_denormals else 0
+        spec.response = _fptr(h)
+        hd = C.c_void_p()
+        check(lib().fdsp_convolve_create_on(-1 if device is None else int(device), V, C.byref(spec), C.byref(hd)))
+        b = cls("convolve", V, _handle=hd)
+        b.max_len, b.block_length = int(spec.max_len), lib().fdsp_convolve_block_length(int(spec.max_len))
+        b.per_instance = bool(per_instance)
+        return b
+
+    def set_response(self, response, first=0):
+        """Convolver::set_response for rows from `first` (fdsp_convolve_set_response): [len] or [channels, len] for one row, [rows, channels,
+        len] for several (rows are instances with per-instance responses, else the single row 0).  The history of the whole bank is cleared."""
+        if self.kind != "convolve":
+            raise ValueError("set_response: not a convolver bank")
+        t = np.asarray(response, dtype=np.float32)
+        h = convolve_response_rows(t, self.outputs(), t.shape[0] if t.ndim == 3 else None)
+        if h.ndim == 2:
+            h = h[None]
+        check(lib().fdsp_convolve_set_response(self._h, _fptr(h), h.shape[-1], int(first), h.shape[0]))
+
     def set_band(self, band, first=0):
         """Replace (lo, hi) table rows from `first` (fdsp_resynth_set_band).  `band` takes the constructor's shapes: one (lo, hi) pair or
         [outputs, 2] for one row (broadcast over the outputs), [rows, outputs | 1, 2] for several."""
@@ -331,8 +384,9 @@ class Bank:
         check(lib().fdsp_bank_clone(self._h, C.byref(h)))
         b = Bank(self.kind, self.voices, _handle=h)
         b.sample_rate = self.sample_rate
-        if hasattr(self, "window"):
-            b.window = self.window
+        for k in ("window", "max_len", "block_length", "per_instance"):
+            if hasattr(self, k):
+                setattr(b, k, getattr(self, k))
         return b
 
     def device(self):
@@ -597,6 +651,25 @@ class Bank:
         ms = C.c_float()
         check(lib().fdsp_bank_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+def convolve_response_rows(response, channels, rows):
+    """A convolver's response as the C ABI reads it: contiguous f32 [channels, len], or [rows, channels, len] when `rows` is given.  A [len]
+    response goes to every channel; a [1, len] one too."""
+    t = np.asarray(response, dtype=np.float32)
+    if t.ndim < 1 or t.ndim > (2 if rows is None else 3) or t.shape[-1] < 1:
+        raise ValueError(f"convolve: response takes [len], [channels, len]{'' if rows is None else ' or [instances, channels, len]'} with len >= 1; got shape {t.shape}")
+    if rows is not None and t.ndim == 3 and t.shape[0] != rows:
+        raise ValueError(f"convolve: a per-instance response needs {rows} rows, got {t.shape[0]}")
+    Cn = int(channels) if channels is not None else (t.shape[-2] if t.ndim >= 2 else 1)
+    if not 1 <= Cn <= 8:
+        raise ValueError(f"convolve: channels takes 1 .. 8, got {Cn}")
+    if t.ndim == 1:
+        t = t[None]
+    if t.shape[-2] not in (1, Cn):
+        raise ValueError(f"convolve: the response has {t.shape[-2]} channels for a bank of {Cn}")
+    shape = (Cn, t.shape[-1]) if rows is None else (rows, Cn, t.shape[-1])
+    return np.ascontiguousarray(np.broadcast_to(t, shape))
 
 
 def resynth_table_rows(values, width, outputs, what):

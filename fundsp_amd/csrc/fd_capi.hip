@@ -389,7 +389,7 @@ int build_default_table_set(int set) {
 }  // namespace
 
 struct fdsp_bank {
-    std::unique_ptr<fd::FxBank> fx;  // an effect bank (fd_fxbank.hpp): reverb, network or resynthesizer instead of a voice graph of slots
+    std::unique_ptr<fd::FxBank> fx;  // an effect bank (fd_fxbank.hpp): reverb, network, resynthesizer or convolver instead of a voice graph of slots
     float* ring = nullptr;       // delay-ring memory [ring node][position][voice] for kinds with Delay / Tap nodes
     uint32_t ring_cap = 0;       // positions per ring node
     const fd::KindOps* ops = nullptr;
@@ -1094,6 +1094,37 @@ static int rs_set_table(fdsp_bank* b, const float* h, size_t first, size_t count
 }
 int fdsp_resynth_set_band(fdsp_bank* b, const float* h_lo_hi, size_t first, size_t count) { return rs_set_table(b, h_lo_hi, first, count, false); }
 int fdsp_resynth_set_gain(fdsp_bank* b, const float* h_gain, size_t first, size_t count) { return rs_set_table(b, h_gain, first, count, true); }
+// ---- convolver banks (fd_fxbank.hpp fx_convolve) -------------------------------------------------------------------------------------------
+static int cv_check_spec(size_t instances, const fdsp_convolve_spec* sp) {
+    if (!sp) return fail(FDSP_EINVAL, "fdsp_convolve_create: spec NULL");
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_convolve_create: no instances");
+    if (sp->channels < 1 || sp->channels > 8) return fail(FDSP_EINVAL, "fdsp_convolve_create: channels takes 1 .. 8");
+    if (sp->max_len < 1 || sp->max_len > ((size_t)1 << 24)) return fail(FDSP_EINVAL, "fdsp_convolve_create: max_len (the response capacity) takes 1 .. 2^24 taps");
+    if (sp->len < 1 || sp->len > sp->max_len)
+        return fail(FDSP_EINVAL, "fdsp_convolve_create: len = " + std::to_string(sp->len) + " takes 1 .. max_len = " + std::to_string(sp->max_len));
+    if (sp->per_instance != 0 && sp->per_instance != 1) return fail(FDSP_EINVAL, "fdsp_convolve_create: per_instance takes 0 or 1");
+    if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, "fdsp_convolve_create: flush_denormals takes 0 or 1");
+    if (!sp->response) return fail(FDSP_EINVAL, "fdsp_convolve_create: response NULL");
+    return FDSP_OK;
+}
+int fdsp_convolve_create_on(int device, size_t instances, const fdsp_convolve_spec* sp, fdsp_bank** out) {
+    if (!out) return fail(FDSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = cv_check_spec(instances, sp)) return rc;
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_convolve(instances, *sp, s, fx); });
+}
+int fdsp_convolve_create(size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out) { return fdsp_convolve_create_on(-1, instances, spec, out); }
+int fdsp_convolve_set_response(fdsp_bank* b, const float* h_response, size_t len, size_t first, size_t count) {
+    if (!b || !h_response) return fail(FDSP_EINVAL, "fdsp_convolve_set_response: bank or response NULL");
+    if (int rc = fd::fx_convolve_check(b->fx.get(), len, first, count)) return rc;
+    if (count == 0) return FDSP_OK;
+    DeviceGuard guard(b->device);
+    HIPCHK(await_last_render(b));
+    if (int rc = fd::fx_convolve_response(b->fx.get(), h_response, len, first, count, b->stream)) return rc;
+    HIPCHK(sync_bank_stream(b));   // (h_response is borrowed for the call)
+    return FDSP_OK;
+}
+int fdsp_convolve_block_length(size_t max_len) { return fd::fx_convolve_block_length(max_len); }
 static int rv3_create(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (!(time > 0.0) || !(diffusion >= 0.0 && diffusion <= 1.0) || !(cutoff > 0.0f))
@@ -1206,7 +1237,7 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
 int fdsp_bank_set_bus(fdsp_bank* b, int mode, float wet, float dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: bank NULL");
     fd::FdnBus* bus = b->fx ? b->fx->bus() : nullptr;
-    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: resynthesizer banks have no bus (out of scope: render the dry path separately)");
+    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: resynthesizer and convolver banks have no bus (out of scope: render the dry path separately)");
     if (!bus) return fail(FDSP_ENOTSUP, "fdsp_bank_set_bus: reverb / network banks only (a run-time compiled graph carries its bus in the graph: fdsp_graph_compile)");
     if (mode < FDSP_BUS_NONE || mode > FDSP_BUS_DRY_WET) return fail(FDSP_EINVAL, "fdsp_bank_set_bus: mode takes FDSP_BUS_NONE, FDSP_BUS_WET or FDSP_BUS_DRY_WET");
     if (mode == FDSP_BUS_DRY_WET && b->fx->inputs() != b->fx->outputs())
@@ -1220,7 +1251,7 @@ int fdsp_bank_set_bus(fdsp_bank* b, int mode, float wet, float dry) {
 int fdsp_bank_get_bus(const fdsp_bank* b, int* mode, float* wet, float* dry) {
     if (!b) return fail(FDSP_EINVAL, "fdsp_bank_get_bus: bank NULL");
     const fd::FdnBus* bus = b->fx ? b->fx->bus() : nullptr;
-    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: resynthesizer banks have no bus");
+    if (b->fx && !bus) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: resynthesizer and convolver banks have no bus");
     if (!bus) return fail(FDSP_ENOTSUP, "fdsp_bank_get_bus: reverb / network banks only");
     if (mode) *mode = bus->mode;
     if (wet) *wet = bus->wet;
@@ -1266,7 +1297,7 @@ int fdsp_bank_reset(fdsp_bank* b) {
 int fdsp_bank_set_seed(fdsp_bank* b, const uint64_t* h_seeds, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     DeviceGuard guard(b->device);
-    if (b->fx) return FDSP_OK;  // no node of reverb_stereo (nor Resynth) uses its hash (Delay, Fir, Panner: default set_hash)
+    if (b->fx) return FDSP_OK;  // no node of reverb_stereo (nor Resynth, nor Convolver) uses its hash (Delay, Fir, Panner: default set_hash)
     if (int rc = check_range(b, first, count)) return rc;
     if (count == 0) return FDSP_OK;
     uint64_t* d = nullptr;
@@ -1303,9 +1334,9 @@ __global__ void k_fill_slot(float* __restrict__ row, float value, size_t V) {
 static int no_named_slots(const fdsp_bank* b) {
     return b && b->fx && b->fx->bus() ? fail(FDSP_EINVAL, "reverb_stereo banks have no named slots (parameters are fixed at creation)") : FDSP_OK;
 }
-// resynthesizer banks (the effect bank without a bus) take fdsp_bank_process and nothing of the mix-down, pan, ring or event entry points
+// resynthesizer and convolver banks (the effect banks without a bus) take fdsp_bank_process and nothing of the mix-down, pan, ring or event entry points
 static int render_only(const fdsp_bank* b) {
-    return b->fx && !b->fx->bus() ? fail(FDSP_ENOTSUP, "resynthesizer banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)")
+    return b->fx && !b->fx->bus() ? fail(FDSP_ENOTSUP, "resynthesizer and convolver banks render through fdsp_bank_process / fdsp_bank_process_host only (no mix-down, pan, ring or event scheduler)")
                                    : FDSP_OK;
 }
 

@@ -1,0 +1,97 @@
+// fd_convolve.hpp -- banks of the reference's Convolver (convolve.rs, prelude.rs:3154-3160: `convolve(&wave, channel)`, 1 -> 1, ID = 100),
+// rendered as uniformly partitioned FFT convolution.
+//
+// What the reference pins: y[n] = sum over k < M of h[k] * x[n - k], x[n < 0] = 0, NO latency (test_basic.rs:698-711), tick and process
+// within 1e-4 (test_basic.rs:329-330), reset() clears the history, set_response re-initialises the node, no set_sample_rate override.  It
+// wraps fft_convolver::FFTConvolver<f32>, whose source is not in the reference tree: that crate's butterflies, its partition scheme and any
+// trimming of trailing near-zero taps are NOT pinned.  The algorithm below is this project's own statement, and the kernels, the numpy
+// restatement (tests/convolve_ref.py) and every split of an input into launches give its bits exactly.
+//
+// The contract (B = block length, a power of two; N = 2B; M = response length; P = ceil(M / B); n = samples since reset; every operation
+// one f32 rounding in the order written, no FMA; Complex32 a * b = (a.re*b.re - a.im*b.im, a.re*b.im + a.im*b.re)):
+//   * B is chosen at creation from the response CAPACITY max_len: the power of two at or above sqrt(8 * max_len), clamped to 64 .. 4096
+//     (cv_block_length; tail about 8 M / B and head about B operations per output sample).
+//   * rfft_N(g) of N real values is fd_resynth.hpp's forward: z[m] = g[2m] + i g[2m+1], the B-point cfft, then the split into bins 0 .. B
+//     (bins 0 and B have .im = +0.0).  irfft_N(Z) of bins 0 .. B is its inverse: fix_negative, the reversal of elements 1 .. N-1, the N-point
+//     cfft, .re * (1/N).  One twiddle table (cos, -sin)(2 pi j / N), j < B, computed in double and rounded to f32.
+//   * Response spectra, p = 0 .. P-1:  G_p = rfft_N(g_p),  g_p[i] = h[(p+1)B + i] for i < B,  g_p[B] = 0,  g_p[i] = h[pB + i - B] for i > B
+//     (h[k] = 0 for k >= M; the first B values of the product never read g_p[B], so it carries no tap and adds no rounding noise).  The
+//     circular convolution of a zero-padded block with g_p has, in its first B values, exactly the block's contribution to the B outputs
+//     that start (p + 1) blocks later: taps pB + 1 .. (p + 2)B - 1, no aliasing.
+//   * Block spectra: when the count reaches (j + 1)B, X_j = rfft_N(x[jB .. jB + B - 1] followed by B zeros).  Only complete blocks are ever
+//     transformed, so no rounding depends on where a launch ended.
+//   * Tail: at the same moment, with j' = j + 1:  Z = (0, 0);  for p = 0, 1, .. min(P, j') - 1 in this order:  Z[k] = Z[k] + X_{j'-1-p}[k] *
+//     G_p[k]  (k = 0 .. B; terms of blocks before the reset are skipped, not added as zeros);  pend_{j'}[r] = irfft_N(Z)[r], r = 0 .. B-1.
+//     pend_0[r] = +0.0.  One forward and ONE inverse transform per block: folding the overlap-add's two halves into g_p is what overlap-save
+//     does, with the zero-padded window the head makes possible.
+//   * Head and output, n = jB + r:  a = h[0] * x[n];  for i = 1 .. min(r, M - 1):  a = a + h[i] * x[n - i];  y[n] = pend_j[r] + a.
+//   * reset(): n = 0 (nothing before it is read again).  set_response: new h, M, P and G, then reset.  Channel c of a bank is its own 1 -> 1
+//     convolver with response row c; instances run in lock-step (one sample counter).
+//
+// Device layout.  Nothing is allocated after creation.  A launch is cut into chunks of at most Lmax = KB * B samples, and a chunk runs, on
+// the bank's stream (S = the count at its start, read from device memory, so a captured launch replays with the state moving on):
+//   k_cv_input    the chunk's samples -> input ring xin [V][C][Rx], Rx a power of two >= Lmax + B,
+//   k_cv_forward  one unit per (block completing in the chunk, instance, channel): X_j in LDS -> spectrum ring spec [V][C][R][B + 1] (re, im),
+//                 slot j mod R, R = Pcap + KB (Pcap = ceil(max_len / B)): the frequency-domain delay line,
+//   k_cv_tail     the hot kernel.  Per bin the tail is a 1-D convolution along the block index, so a lane owns one bin of one (instance,
+//                 channel) for CV_J consecutive block boundaries: it walks the blocks from the newest down ONCE, keeps the CV_J sums in
+//                 registers and a window of the last CV_J response bins in registers, and uses each X loaded for up to CV_J sums (p still
+//                 increases from zero in every sum).  Z -> zbuf [V][C][KB][B + 1],
+//   k_cv_inverse  one unit per (boundary, instance, channel): irfft_N in LDS -> pend ring pend [V][C][KB + 1][B], slot j' mod (KB + 1),
+//   k_cv_output   one workgroup per (instance, channel, tile of min(B, 256) samples aligned to the absolute count): the block's inputs up to
+//                 the tile's end and the taps they meet are staged in LDS, one lane per sample adds pend + head,
+//   k_cv_advance  one lane: n += L.
+// M and P live on the device too (dims), so a replayed capture follows set_response.  KB = clamp(256 MiB / (V * C * (B + 1) * 8 B), 8, 64).
+// Memory: V*C * (Rx*4 + (R + KB)*(B + 1)*8 + (KB + 1)*B*4) + rows*C * ((Pcap + 1)*B*4 + Pcap*(B + 1)*8) bytes, rows = V with per-instance
+// responses, else 1.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace fd {
+
+constexpr int CV_MAX_CH = 8;
+constexpr int CV_MIN_LOGB = 6, CV_MAX_LOGB = 12;   // B = 64 .. 4096
+constexpr int CV_J = 8;                            // block boundaries per lane of the tail kernel
+
+struct CvConst {
+    int B, logB, C;
+    int rows;                 // 1: one response per channel for every instance, V: per instance
+    int Pcap;                 // partitions the capacity holds: ceil(max_len / B)
+    size_t Hcap;              // taps per row and channel as stored: (Pcap + 1) * B, zero beyond M
+    int KB;                   // blocks per chunk; Lmax = KB * B
+    int R;                    // spectrum ring slots: Pcap + KB
+    int Rx;                   // input ring length (power of two >= Lmax + B)
+    float invN;               // 1 / (2B) (exact)
+    const float2* tw;         // [B] (cos, -sin)(2 pi j / 2B)
+    const float* h;           // [rows][C][Hcap]
+    const float2* G;          // [rows][C][Pcap][B + 1]
+};
+
+struct CvState {
+    float* xin;               // [V][C][Rx]
+    float2* spec;             // [V][C][R][B + 1]
+    float2* zbuf;             // [V][C][KB][B + 1]
+    float* pend;              // [V][C][KB + 1][B]
+    unsigned long long* samples;   // [1] samples since reset
+    int* dims;                // [2] M, P
+};
+
+// host: B for a response capacity; the largest capacity a bank takes
+int cv_block_length(size_t max_len);
+constexpr size_t CV_MAX_LEN = (size_t)1 << 24;
+
+namespace cv_ieee {
+void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout,
+                      hipStream_t stream);
+void cv_launch_response(const CvConst& c, size_t row0, size_t nrows, hipStream_t stream);   // G of rows [row0, row0 + nrows) from h
+}
+namespace cv_ftz {   // the same kernels compiled with f32 denormals flushed (a Feedback node in front of the convolver)
+void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout,
+                      hipStream_t stream);
+void cv_launch_response(const CvConst& c, size_t row0, size_t nrows, hipStream_t stream);
+}
+
+}  // namespace fd

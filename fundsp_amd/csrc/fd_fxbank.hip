@@ -1,8 +1,9 @@
 // fd_fxbank.hip -- the effect banks of fd_fxbank.hpp: buffers, configuration, clone and launch of each family (host code; the kernels are in
-// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip and fd_resynth.hip).
+// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_resynth.hip and fd_convolve.hip).
 #include <vector>
 
 #include "fd_fxbank.hpp"
+#include "fd_convolve.hpp"
 #include "fd_fdnx.hpp"
 #include "fd_opts.hpp"
 #include "fd_resynth.hpp"
@@ -328,6 +329,87 @@ class ResynthFx final : public FxBank {
     size_t V_;
 };
 
+// ---- convolver banks (fd_convolve.hpp): twiddles, taps, response spectra, input / spectrum / pending rings, device counter and lengths ------
+class ConvolveFx final : public FxBank {
+  public:
+    // (the pointers of `c` are another instance's)
+    ConvolveFx(const CvConst& c, int ftz, size_t V, size_t max_len) : c_(c), ftz_(ftz), V_(V), max_len_(max_len) { for (const Buf& b : bufs()) *b.p = nullptr; }
+    ~ConvolveFx() override { free_bufs(bufs()); }
+    int inputs() const override { return c_.C; }
+    int outputs() const override { return c_.C; }
+    // Convolver has no set_sample_rate override: the response's own rate is ignored and nothing depends on the bank's
+    int set_sample_rate(double, hipStream_t) override { return FDSP_OK; }
+    // Convolver::reset: the history goes; no block before the new sample 0 is read again
+    hipError_t reset(hipStream_t s) override { return hipMemsetAsync(st_.samples, 0, sizeof(unsigned long long), s); }
+    int clone(hipStream_t s, std::unique_ptr<FxBank>* out) override {
+        auto d = std::make_unique<ConvolveFx>(c_, ftz_, V_, max_len_);
+        d->M_ = M_;
+        hipError_t e = alloc_bufs(d->bufs());
+        if (e == hipSuccess) e = copy_bufs(d->bufs(), bufs(), s);
+        if (e != hipSuccess) return hip_fail(e, "fdsp_bank_clone: convolver buffers");
+        *out = std::move(d);
+        return FDSP_OK;
+    }
+    // every split of an input into launches gives the same bits: FDSP_MODE_PROCESS == FDSP_MODE_TICK
+    void render(const float* in, float* out, size_t T, size_t fstride, int layout, int, bool, hipStream_t s) override {
+        (ftz_ ? cv_ftz::cv_launch_render : cv_ieee::cv_launch_render)(c_, st_, V_, in, out, T, fstride, layout, s);
+    }
+    // the buffers, the twiddles, the rings defined, then the response [rows][C][len]
+    int init(const float* response, size_t len, hipStream_t s) {
+        const Bufs l = bufs();
+        std::vector<float> tw(2 * (size_t)c_.B);
+        rs_tables(2 * c_.B, nullptr, nullptr, tw.data());
+        hipError_t e = alloc_bufs(l);
+        if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.tw, tw.data(), l[0].bytes, hipMemcpyHostToDevice, s);
+        for (size_t i = 3; i < l.size() && e == hipSuccess; i++) e = hipMemsetAsync(*l[i].p, 0, l[i].bytes, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (tw is a local)
+        if (e != hipSuccess) return hip_fail(e, "fdsp_convolve_create buffers");
+        if (int rc = set_response(response, len, 0, (size_t)c_.rows, s)) return rc;
+        e = hipStreamSynchronize(s);
+        return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_convolve_create response");
+    }
+    int check_response(size_t len, size_t first, size_t count) const {
+        const size_t rows = (size_t)c_.rows;
+        if (len < 1 || len > max_len_)
+            return api_fail(FDSP_EINVAL, "fdsp_convolve_set_response: len = " + std::to_string(len) + " takes 1 .. the bank's max_len = " + std::to_string(max_len_));
+        if (first > rows || count > rows - first)
+            return api_fail(FDSP_EINVAL, "fdsp_convolve_set_response: rows out of range (one row per instance with per_instance, else the single row 0)");
+        if (count != 0 && count != rows && len != M_)
+            return api_fail(FDSP_EINVAL, "fdsp_convolve_set_response: a bank has one response length; replacing some of the rows takes the current len = " + std::to_string(M_));
+        return FDSP_OK;
+    }
+    // what re-initialising the node does: new taps (zero beyond len), their partitions' spectra, the lengths, and the history cleared
+    int set_response(const float* h, size_t len, size_t first, size_t count, hipStream_t s) {
+        const size_t rowf = (size_t)c_.C * c_.Hcap;
+        float* dst = (float*)c_.h + first * rowf;
+        const int dims[2] = {(int)len, (int)((len + c_.B - 1) / c_.B)};
+        hipError_t e = hipMemsetAsync(dst, 0, count * rowf * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(dst, c_.Hcap * sizeof(float), h, len * sizeof(float), len * sizeof(float), count * c_.C, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(st_.dims, dims, sizeof(dims), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            (ftz_ ? cv_ftz::cv_launch_response : cv_ieee::cv_launch_response)(c_, first, count, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = reset(s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (dims is a local, h is borrowed)
+        if (e != hipSuccess) return hip_fail(e, "fdsp_convolve_set_response");
+        M_ = len;
+        return FDSP_OK;
+    }
+    Bufs bufs() {   // the tables first
+        const size_t B = (size_t)c_.B, B1 = B + 1, rc = (size_t)c_.rows * c_.C, vc = V_ * c_.C;
+        return {{(void**)&c_.tw, B * sizeof(float2)}, {(void**)&c_.h, rc * c_.Hcap * sizeof(float)}, {(void**)&c_.G, rc * c_.Pcap * B1 * sizeof(float2)},
+                {(void**)&st_.xin, vc * (size_t)c_.Rx * sizeof(float)}, {(void**)&st_.spec, vc * (size_t)c_.R * B1 * sizeof(float2)},
+                {(void**)&st_.zbuf, vc * (size_t)c_.KB * B1 * sizeof(float2)}, {(void**)&st_.pend, vc * (size_t)(c_.KB + 1) * B * sizeof(float)},
+                {(void**)&st_.samples, sizeof(unsigned long long)}, {(void**)&st_.dims, 2 * sizeof(int)}};
+    }
+
+    CvConst c_;
+    CvState st_{};
+    int ftz_;   // 1: the flush-to-zero instantiation (a Feedback node in front)
+    size_t V_, max_len_, M_ = 0;
+};
+
 }  // namespace
 
 int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t s, std::unique_ptr<FxBank>* out) {
@@ -399,6 +481,38 @@ int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** 
     *row0 = (gain ? (float*)c.gain : (float*)c.band) + first * *row_floats;
     return FDSP_OK;
 }
+
+int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    const size_t V = instances;
+    CvConst c{};
+    c.B = cv_block_length(sp.max_len);
+    while ((1 << c.logB) < c.B) c.logB++;
+    c.C = sp.channels;
+    c.rows = sp.per_instance ? (int)V : 1;
+    c.Pcap = (int)((sp.max_len + c.B - 1) / c.B);
+    c.Hcap = (size_t)(c.Pcap + 1) * c.B;
+    // blocks per chunk: the Z buffer within 256 MiB where the bank is large, at least one tile of the tail kernel
+    size_t KB = ((size_t)256 << 20) / (V * (size_t)c.C * (c.B + 1) * sizeof(float2));
+    KB = KB < 8 ? 8 : (KB > 64 ? 64 : KB);
+    c.KB = (int)KB;
+    c.R = c.Pcap + c.KB;
+    c.Rx = 1;
+    while (c.Rx < (c.KB + 1) * c.B) c.Rx <<= 1;
+    c.invN = 1.0f / (float)(2 * c.B);
+    auto r = std::make_unique<ConvolveFx>(c, sp.flush_denormals, V, sp.max_len);
+    if (int rc = r->init(sp.response, sp.len, s)) return rc;
+    *out = std::move(r);
+    return FDSP_OK;
+}
+int fx_convolve_check(FxBank* fx, size_t len, size_t first, size_t count) {
+    auto* r = dynamic_cast<ConvolveFx*>(fx);
+    if (!r) return api_fail(FDSP_EINVAL, "fdsp_convolve_set_response: not a convolver bank");
+    return r->check_response(len, first, count);
+}
+int fx_convolve_response(FxBank* fx, const float* h, size_t len, size_t first, size_t count, hipStream_t s) {
+    return static_cast<ConvolveFx*>(fx)->set_response(h, len, first, count, s);
+}
+int fx_convolve_block_length(size_t max_len) { return cv_block_length(max_len); }
 
 }  // namespace fd
 

@@ -1,6 +1,6 @@
 // fd_fxbank.hpp -- the effect banks: banks of one stock node per instance instead of a voice graph of slots -- the Hadamard networks
 // (reverb_stereo, reverb4_stereo, the generic `fdn`: fd_fdn.hpp), reverb3_stereo (fd_reverb3.hpp), the filtered / per-instance networks
-// (fd_fdnx.hpp) and the resynthesizer (fd_resynth.hpp).  fd_capi.hip keeps the bank handle (stream, events, pan weights, launch options)
+// (fd_fdnx.hpp), the resynthesizer (fd_resynth.hpp) and the convolver (fd_convolve.hpp).  fd_capi.hip keeps the bank handle (stream, events, pan weights, launch options)
 // and the public constructors' argument checks; what a family allocates, configures, copies and launches is behind FxBank (fd_fxbank.hip).
 #pragma once
 
@@ -22,7 +22,7 @@ struct FxBank {
     virtual ~FxBank() = default;   // frees every device buffer the instance allocated
     virtual int inputs() const = 0;
     virtual int outputs() const = 0;
-    virtual FdnBus* bus() { return nullptr; }   // nullptr: the resynthesizer, which renders through fdsp_bank_process only
+    virtual FdnBus* bus() { return nullptr; }   // nullptr: the resynthesizer and the convolver, which render through fdsp_bank_process only
     // a network changes nothing unless the rate changes and reconfigures transactionally: on failure it keeps its rate and state
     virtual int set_sample_rate(double sr, hipStream_t stream) = 0;
     virtual hipError_t reset(hipStream_t stream) = 0;
@@ -44,5 +44,12 @@ int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_
 int fx_resynth(size_t instances, const fdsp_resynth_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
 // fdsp_resynth_set_band / _gain: checks the bank (`fx` may be NULL) and the rows; the device address of row `first` and the floats per row
 int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats);
+int fx_convolve(size_t instances, const fdsp_convolve_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// fdsp_convolve_set_response: _check refuses what is not a convolver bank (`fx` may be NULL), a length beyond the capacity and rows out of
+// range before anything is touched; _response uploads [count][channels][len] for rows first .. first+count-1, transforms the partitions on
+// `stream` and clears the history (the caller waits for the stream: the host array is borrowed)
+int fx_convolve_check(FxBank* fx, size_t len, size_t first, size_t count);
+int fx_convolve_response(FxBank* fx, const float* h_response, size_t len, size_t first, size_t count, hipStream_t stream);
+int fx_convolve_block_length(size_t max_len);   // the block length B a bank of this response capacity uses (fd_convolve.hpp)
 
 }  // namespace fd

@@ -3,6 +3,7 @@
 // -fgpu-flush-denormals-to-zero -DFD_FTZ=1 (namespace rs_ftz).
 #include <cmath>
 
+#include "fd_fft.hpp"
 #include "fd_math.hpp"
 #include "fd_resynth.hpp"
 #include "../../include/fundsp_hip.h"
@@ -34,28 +35,6 @@ void rs_tables(int N, float* hann, float* hz, float* tw) {
 
 namespace FD_RS_NS {
 namespace {
-
-struct Cf {
-    float re, im;
-};
-
-__device__ __forceinline__ unsigned bitrev(unsigned x, int bits) { return __brev(x) >> (32 - bits); }
-
-// one radix-2 stage of cfft_inplace over `n` points at buf: butterflies j = lane, lane + P, ..; twiddle k * (N / span) of the N table
-template <int P>
-__device__ __forceinline__ void stage(Cf* buf, int n, int lspan, int N, int logN, const float2* __restrict__ tw, int lane) {
-    const int half = 1 << (lspan - 1);
-    const int tstep = logN - lspan;   // N / span = 2^tstep
-    for (int j = lane; j < n / 2; j += P) {
-        const int k = j & (half - 1);
-        const int i = ((j >> (lspan - 1)) << lspan) + k;
-        const float2 w = tw[k << tstep];
-        Cf p = buf[i], q = buf[i + half];
-        const float yr = w.x * q.re - w.y * q.im, yi = w.x * q.im + w.y * q.re;
-        buf[i + half] = Cf{p.re - yr, p.im - yi};
-        buf[i] = Cf{p.re + yr, p.im + yi};
-    }
-}
 
 // chunk input -> input ring (raw samples)
 __global__ void k_rs_input(RsConst c, RsState st, size_t V, const float* __restrict__ in, size_t T, size_t t0, int L, size_t fs, int layout) {
@@ -121,20 +100,7 @@ __global__ __launch_bounds__(256) void k_rs_frames(RsConst c, RsState st, size_t
     for (int r = 0; r < NB; r++) {
         const int b = lane + r * P;
         if (b > NH) break;
-        Cf X;
-        if (b == 0 || b == NH) {
-            const Cf z0 = buf[0];
-            X = Cf{b == 0 ? z0.re + z0.im : z0.re - z0.im, 0.0f};
-        } else {
-            const Cf A = buf[b], Bc = buf[NH - b];
-            const Cf B{Bc.re, -Bc.im};
-            const Cf E{0.5f * (A.re + B.re), 0.5f * (A.im + B.im)};
-            const Cf D{0.5f * (A.re - B.re), 0.5f * (A.im - B.im)};
-            const float2 w = c.tw[b];
-            const float qr = D.im, qi = -D.re;
-            const float wr = w.x * qr - w.y * qi, wi = w.x * qi + w.y * qr;
-            X = Cf{E.re + wr, E.im + wi};
-        }
+        const Cf X = rfft_bin(buf, b, NH, c.tw);
         Cf Y{0.0f, 0.0f};
         if (src >= 0) {
             if (c.proc == RS_PASS) {
@@ -156,13 +122,7 @@ __global__ __launch_bounds__(256) void k_rs_frames(RsConst c, RsState st, size_t
     for (int r = 0; r < NB; r++) {
         const int b = lane + r * P;
         if (b > NH) break;
-        const Cf Y = y[r];
-        if (b == 0 || b == NH) {
-            buf[bitrev(b, LOGN)] = Y;
-        } else {
-            buf[bitrev(b, LOGN)] = Cf{Y.re, -Y.im};
-            buf[bitrev(N - b, LOGN)] = Y;
-        }
+        ifft_store_bin(buf, b, y[r], LOGN);
     }
     __syncthreads();
     for (int ls = 1; ls <= LOGN; ls++) {

@@ -44,7 +44,9 @@ class Graph:
         return g
 
     def __or__(self, other):
-        return self._pair(other, "Stack", self.nin + other.nin, self.nout + other.nout)
+        g = self._pair(other, "Stack", self.nin + other.nin, self.nout + other.nout)
+        g.stack_parts = (self, other)   # convolve_plan: a stack of convolvers is one bank with a channel each
+        return g
 
     def __and__(self, other):  # Bus, combinator.rs `&`
         if self.nin != other.nin or self.nout != other.nout:
@@ -903,3 +905,67 @@ def resynth(window, inputs=1, outputs=1, processor="pass", source=None, band=Non
 
 def has_resynth(graph):
     return "ResynthPing<" in graph.type
+
+
+# --- convolve (convolve.rs): rendered by its own bank family (Bank.convolve, fdsp_convolve_create), never by the run-time compiler.  As for
+# resynth, the type only lets the hash probe walk a graph that contains the node: Convolver::ID = 100 with the default ping.
+_CONVOLVE_SRC = """
+struct ConvolvePing {
+    static constexpr int IN = 1, OUT = 1, RINGS = 0;
+    static constexpr uint64_t ID = 100;
+    template <class V> FD_HD void visit(V&) {}
+    FD_HD void bind(Ctx&) {}
+    FD_HD void init() {}
+    FD_HD void update(double) {}
+    FD_HD void reset() {}
+    FD_HD uint64_t ping(bool, uint64_t h) { return atto(h, ID); }
+    FD_HD void begin_block(int) {}
+    FD_HD bool tripped() const { return false; }
+    FD_HD void end_simd() {}
+    template <int PH> FD_HD void step(const float*, float* out) { out[0] = 0.0f; }
+    FD_STEP2_VIA_STEP
+};
+"""
+
+
+def convolve(response, channel=0):
+    """convolve(&wave, channel) (prelude.rs:3154-3160): a 1 -> 1 convolver with channel `channel` of the Wave `response` ([len] or
+    [channels, len]; the Wave's sample rate plays no part).  Bank.from_graph renders the node alone, a stack of them, or either as the last
+    node of a pipe."""
+    w = np.asarray(response, dtype=np.float32)
+    if w.ndim == 1:
+        w = w[None]
+    if w.ndim != 2 or w.shape[1] < 1:
+        raise ValueError(f"convolve: the response takes [len] or [channels, len] with len >= 1; got shape {np.shape(response)}")
+    if not 0 <= int(channel) < w.shape[0]:
+        raise ValueError(f"convolve: channel {channel} of a response with {w.shape[0]} channel(s)")
+    g = Graph("ConvolvePing", 1, 1, [], 0, _CONVOLVE_SRC)
+    g.convolve_response = np.ascontiguousarray(w[int(channel)])
+    return g
+
+
+def has_convolve(graph):
+    return "ConvolvePing" in graph.type
+
+
+def convolve_plan(graph):
+    """[channels, len] responses when `graph` is convolve(..) or a stack of convolvers (one channel each, in stack order; shorter responses
+    are zero-padded to the longest: a bank has one response length), else None."""
+    def leaves(g):
+        if getattr(g, "convolve_response", None) is not None:
+            return [g.convolve_response]
+        parts = getattr(g, "stack_parts", None)
+        if parts is None:
+            return None
+        a, b = leaves(parts[0]), leaves(parts[1])
+        return None if a is None or b is None else a + b
+
+    rs = leaves(graph)
+    if rs is None:
+        return None
+    if len(rs) > 8:
+        raise ValueError(f"convolve: a stack of {len(rs)} convolvers (a bank takes 1 .. 8 channels)")
+    h = np.zeros((len(rs), max(len(r) for r in rs)), dtype=np.float32)
+    for c, r in enumerate(rs):
+        h[c, :len(r)] = r
+    return h

@@ -285,6 +285,44 @@ int fdsp_resynth_set_gain(fdsp_bank* bank, const float* h_gain, size_t first, si
 /* Host only, no device: the bank's tables for window_length N -- hann[N] = 0.5 + 0.5 * cosf(((i - N/2) as f32 * TAU) / N as f32) and
  * twiddles[N/2][2] = (cos, -sin)(2 pi j / N) computed in double and rounded to f32.  Either pointer may be NULL. */
 int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles);
+/* Convolver banks: `instances` x `channels` independent convolve(&wave, channel) nodes (src/convolve.rs, src/prelude.rs:3154-3160; the
+ * reference's stereo form is convolve(&w, 0) | convolve(&w, 1)): channel c is its own 1 -> 1 convolver with response row c,
+ *   y[n] = sum over k < len of h[k] * x[n - k],  x[n < 0] = 0,  no latency,
+ * in f32 by uniformly partitioned FFT convolution that this project states operation by operation in fundsp_amd/csrc/fd_convolve.hpp:
+ * block length B chosen from the capacity max_len (fdsp_convolve_block_length), one forward transform per COMPLETE block, the partitions'
+ * products summed in increasing partition order, one inverse per block for the part of the output that older blocks decide, and the
+ * current block's own samples added directly (h[0] * x[n] first, then h[i] * x[n - i] for increasing i).  Only complete blocks are ever
+ * transformed, so every split of an input into launches -- one launch, sample by sample, ragged, a captured launch replayed -- gives the
+ * same bits, and FDSP_MODE_PROCESS == FDSP_MODE_TICK.  Parity: bit-exact against that statement (tests/convolve_ref.py restates it in
+ * numpy).  The reference wraps the crate fft_convolver, whose source is not in the reference tree: the crate's own bits (its butterflies,
+ * its partition scheme, any trimming of trailing near-zero taps) are NOT pinned; what the reference's tests ask -- no latency, the known
+ * answer and tick == process within 1e-4 -- holds.
+ * response is [rows][channels][len], rows = instances with per_instance = 1, else 1.  max_len is the capacity: nothing is allocated,
+ * grown or freed after creation, so a launch may be captured on a caller's stream and replayed (the sample counter and the lengths live
+ * on the device: a replay moves on and follows set_response).  With Pcap = ceil(max_len / B) and KB = clamp(256 MiB / (instances x
+ * channels x (B + 1) x 8 B), 8, 64) a bank takes
+ *   instances x channels x (Rx x 4 + (Pcap + 2 KB) x (B + 1) x 8 + (KB + 1) x B x 4) + rows x channels x ((Pcap + 1) x B x 4 + Pcap x (B + 1) x 8)
+ * bytes, Rx the power of two at or above (KB + 1) x B.  flush_denormals = 1 selects the flush-to-zero build (a Feedback node in front, as
+ * for the resynthesizer).  set_sample_rate is accepted and changes nothing (the node has no override); reset clears the history; clone
+ * continues where the source stands.  fdsp_bank_set_bus, fdsp_bank_process_mix, slots, rings and events answer FDSP_ENOTSUP; invalid specs
+ * FDSP_EINVAL before anything is allocated or launched. */
+typedef struct fdsp_convolve_spec {
+    int channels;                       /* 1 .. 8 */
+    size_t max_len;                     /* response capacity in taps, 1 .. 2^24 */
+    size_t len;                         /* 1 .. max_len */
+    int per_instance;                   /* 0: response [channels][len]; 1: [instances][channels][len] */
+    int flush_denormals;                /* 1: f32 denormals flushed (a Feedback node in front) */
+    const float* response;
+} fdsp_convolve_spec;
+int fdsp_convolve_create(size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out);
+int fdsp_convolve_create_on(int device, size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out);
+/* Re-initialise the convolvers between launches, as Convolver::set_response does: rows first .. first+count-1 take h_response
+ * [count][channels][len] (borrowed for the call), their partitions are transformed on the device, and the history of the WHOLE bank is
+ * cleared (the instances share one sample counter).  len takes 1 .. max_len; a bank has one response length, so replacing only some of
+ * the rows of a per-instance bank takes the current len. */
+int fdsp_convolve_set_response(fdsp_bank* bank, const float* h_response, size_t len, size_t first, size_t count);
+/* Host only, no device: the block length B of a bank of capacity max_len -- the power of two at or above sqrt(8 x max_len), 64 .. 4096. */
+int fdsp_convolve_block_length(size_t max_len);
 /* reverb3_stereo(time, diffusion, lowpole_hz(cutoff)) (src/prelude.rs:1858-1871): the allpass-loop reverb Reverb<F> of src/reverb.rs:152-279
  * with the documented loop filter, a one-pole lowpass (src/filter.rs:19-66).  `instances` independent reverbs, 2 inputs / 2 outputs each, all
  * with the same parameters.  One wave per instance, one lane per FRAME of a 64-sample block: all 76 delay lines of the structure (4 input

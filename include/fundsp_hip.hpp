@@ -586,6 +586,17 @@ class Bank {
         b.kind_ = "resynth";
         return b;
     }
+    // convolve(&wave, channel) per channel (fdsp_convolve_create, include/fundsp_hip.h): partitioned FFT convolution, no latency
+    static Bank convolve(size_t instances, const fdsp_convolve_spec& spec) {
+        Bank b;
+        check(fdsp_convolve_create(instances, &spec, &b.h_));
+        b.kind_ = "convolve";
+        return b;
+    }
+    // Convolver::set_response for rows first .. first+count-1: h_response [count][channels][len]; the bank's history is cleared
+    void set_response(const float* h_response, size_t len, size_t first = 0, size_t count = 1) {
+        check(fdsp_convolve_set_response(h_, h_response, len, first, count));
+    }
     Bank(Bank&& o) noexcept { *this = std::move(o); }
     Bank& operator=(Bank&& o) noexcept {
         if (this != &o) {

@@ -65,6 +65,16 @@ pub mod ffi {
         pub hi_hz: *const f32,
         pub gain: *const f32,
     }
+    /// `struct fdsp_convolve_spec` (fdsp_convolve_create): convolvers by partitioned FFT convolution, one response row per channel
+    #[repr(C)]
+    pub struct FdspConvolveSpec {
+        pub channels: c_int,
+        pub max_len: usize,
+        pub len: usize,
+        pub per_instance: c_int,
+        pub flush_denormals: c_int,
+        pub response: *const f32,
+    }
     pub const FDSP_RESYNTH_PASS: c_int = 0;
     pub const FDSP_RESYNTH_BAND: c_int = 1;
     pub const FDSP_RESYNTH_GAIN: c_int = 2;
@@ -99,6 +109,8 @@ pub mod ffi {
         pub fn fdsp_resynth_create_on(device: c_int, instances: usize, spec: *const FdspResynthSpec, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_resynth_set_band(bank: *mut FdspBank, lo_hi: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_resynth_set_gain(bank: *mut FdspBank, gain: *const f32, first: usize, count: usize) -> c_int;
+        pub fn fdsp_convolve_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_convolve_set_response(bank: *mut FdspBank, response: *const f32, len: usize, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_destroy(bank: *mut FdspBank);
         pub fn fdsp_bank_clone(bank: *const FdspBank, out: *mut *mut FdspBank) -> c_int; // Clone: slots, rings, sample rate, options, events
         pub fn fdsp_bank_inputs(bank: *const FdspBank) -> c_int;
@@ -333,6 +345,38 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_resynth_create_on(device as c_int, instances, &spec, &mut bank) })?;
         Self::adopt(bank, "resynth", instances)
+    }
+
+    /// `instances` x `channels` convolvers, `convolve(&wave, channel)` per channel (src/convolve.rs; include/fundsp_hip.h
+    /// `fdsp_convolve_spec`): `response` holds [channels][len], or [instances][channels][len] with `per_instance`; `max_len` is the capacity
+    /// [`Self::set_response`] can fill later.  No latency; the bits are the project's own statement (fd_convolve.hpp), not the crate's.
+    /// Source only: no Rust toolchain has built it.
+    pub fn convolve(instances: usize, channels: usize, response: &[f32], len: usize, max_len: usize, per_instance: bool, flush_denormals: bool,
+                    device: i32) -> Result<Self, String> {
+        let rows = if per_instance { instances } else { 1 };
+        if channels < 1 || channels > 8 || len < 1 || response.len() != rows * channels * len {
+            return Err("HipBank::convolve: response needs rows x channels x len taps (rows = instances with per_instance), 1 .. 8 channels".into());
+        }
+        let spec = FdspConvolveSpec {
+            channels: channels as c_int,
+            max_len,
+            len,
+            per_instance: per_instance as c_int,
+            flush_denormals: flush_denormals as c_int,
+            response: response.as_ptr(),
+        };
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_convolve_create_on(device as c_int, instances, &spec, &mut bank) })?;
+        Self::adopt(bank, "convolve", instances)
+    }
+
+    /// Convolver::set_response for rows `first` .. : `response` holds [count][channels][len]; the history of the whole bank is cleared
+    pub fn set_response(&mut self, response: &[f32], len: usize, first: usize, count: usize) -> Result<(), String> {
+        let channels = unsafe { fdsp_bank_outputs(self.bank) as usize };
+        if response.len() != count * channels * len {
+            return Err("HipBank::set_response: response needs count x channels x len taps".into());
+        }
+        check(unsafe { fdsp_convolve_set_response(self.bank, response.as_ptr(), len, first, count) })
     }
 
     fn adopt(bank: *mut FdspBank, kind: &str, voices: usize) -> Result<Self, String> {
