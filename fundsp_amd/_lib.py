@@ -41,6 +41,12 @@ class ResynthSpec(C.Structure):
                 ("flush_denormals", _i), ("lo_hz", _fp), ("hi_hz", _fp), ("gain", _fp)]
 
 
+class ResynthFnSpec(C.Structure):
+    """struct fdsp_resynth_fn_spec (include/fundsp_hip.h)"""
+    _fields_ = [("window_length", _i), ("inputs", _i), ("outputs", _i), ("params", _i), ("state", _i), ("flush_denormals", _i),
+                ("functor", _cs), ("source", _cs), ("param_values", _fp)]
+
+
 class ConvolveSpec(C.Structure):
     """struct fdsp_convolve_spec (include/fundsp_hip.h)"""
     _fields_ = [("channels", _i), ("max_len", _sz), ("len", _sz), ("per_instance", _i), ("flush_denormals", _i), ("response", _fp)]
@@ -82,6 +88,10 @@ SYMBOLS = {
     "fdsp_resynth_set_band": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_resynth_set_gain": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_resynth_tables": (_i, [_i, _fp, _fp]),
+    "fdsp_resynth_fn_create": (_i, [_sz, C.POINTER(ResynthFnSpec), C.POINTER(_P)]),
+    "fdsp_resynth_fn_create_on": (_i, [_i, _sz, C.POINTER(ResynthFnSpec), C.POINTER(_P)]),
+    "fdsp_resynth_fn_check": (_i, [C.POINTER(ResynthFnSpec)]),
+    "fdsp_resynth_set_params": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_convolve_create": (_i, [_sz, C.POINTER(ConvolveSpec), C.POINTER(_P)]),
     "fdsp_convolve_create_on": (_i, [_i, _sz, C.POINTER(ConvolveSpec), C.POINTER(_P)]),
     "fdsp_convolve_set_response": (_i, [_P, _fp, _sz, _sz, _sz]),

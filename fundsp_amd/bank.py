@@ -67,6 +67,12 @@ class Bank:
             if sample_rate is not None:
                 b.set_sample_rate(sample_rate)
             return b
+        rf = getattr(graph, "resynth_fn_plan", None)
+        if rf is not None:   # resynth_fn(..) itself: the same kernels around the caller's closure (fdsp_resynth_fn_create)
+            b = cls.resynth_fn(voices, **rf, flush_denormals=flush_denormals)
+            if sample_rate is not None:
+                b.set_sample_rate(sample_rate)
+            return b
         cv = G.convolve_plan(graph)
         if cv is not None:   # convolve(..) or a stack convolve(..) | convolve(..) | ..: one convolver bank, one channel each (fdsp_convolve_create)
             b = cls.convolve(voices, cv, flush_denormals=flush_denormals)
@@ -88,12 +94,15 @@ class Bank:
             raise ValueError("convolve(..) renders as a whole graph, as a stack of convolvers `convolve(..) | convolve(..)`, or as the last node "
                              "of a pipe, `front >> convolve(..)` / `front >> (convolve(..) | convolve(..))` (a Chain); inside any other stack, a "
                              "sum, bus or feedback, or followed by more nodes, it is not supported")
-        if parts is not None and getattr(parts[1], "resynth_plan", None) is not None and not G.has_resynth(parts[0]):
+        if parts is not None and (getattr(parts[1], "resynth_plan", None) or getattr(parts[1], "resynth_fn_plan", None)) is not None and not G.has_resynth(parts[0]):
             # `front >> resynth(..)` -- the reference's criterion bench noise() >> resynth::<U1, U1, _>(1024, ..): the front keeps its fused kernel,
             # the resynthesizer its FFT kernels; the front is seeded from the whole graph's construction hash (Resynth::ID = 80 enters it through the
             # probe's ResynthPing) and both halves flush denormals when the front has a Feedback node, as the one graph would
             ftz = flush_denormals or "Feedback" in parts[0].type
-            eff = cls.resynth(voices, **parts[1].resynth_plan, flush_denormals=ftz)
+            if getattr(parts[1], "resynth_fn_plan", None) is not None:
+                eff = cls.resynth_fn(voices, **parts[1].resynth_fn_plan, flush_denormals=ftz)
+            else:
+                eff = cls.resynth(voices, **parts[1].resynth_plan, flush_denormals=ftz)
             if sample_rate is not None:
                 eff.set_sample_rate(sample_rate)
             src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, fdn_kernel=fdn_kernel, flush_denormals=ftz)
@@ -331,6 +340,40 @@ class Bank:
         return b
 
     @classmethod
+    def resynth_fn(cls, instances, window, functor, source, inputs=1, outputs=1, state=0, param_values=None, flush_denormals=False, device=-1,
+                   **params):
+        """Bank of `instances` x resynth::<I, O, _>(window, closure) with the caller's closure (fdsp_resynth_fn_create): `functor` names a
+        C++ type in namespace fd that `source` defines in the per-bin form of fundsp_amd/csrc/fd_resynth_fn.hpp; it is compiled here, at
+        creation.  `state`: f32 values per (instance, bin) kept from frame to frame; `**params`: the functor's parameters in keyword order,
+        scalars or per-instance arrays (or param_values=[P] / [instances, P])."""
+        from . import graph as G
+
+        V = int(instances)
+        plan = G.resynth_fn(window, functor, source, inputs, outputs, state, param_values, **params).resynth_fn_plan   # (the argument checks)
+        t = G.resynth_fn_params({}, plan["param_values"], V) if plan["param_values"] is not None else None
+        spec = resynth_fn_spec(plan, 0 if t is None else t.shape[-1], flush_denormals)
+        if t is not None:
+            t = np.ascontiguousarray(np.broadcast_to(t, (V, t.shape[-1])))
+            spec.param_values = _fptr(t)
+        h = C.c_void_p()
+        check(lib().fdsp_resynth_fn_create_on(int(device), V, C.byref(spec), C.byref(h)))
+        b = cls("resynth", V, _handle=h)
+        b.window, b.params = plan["window"], int(spec.params)
+        return b
+
+    def set_resynth_params(self, values, first=0):
+        """Replace a closure bank's parameters for instances from `first` (fdsp_resynth_set_params): [params] for one instance or
+        [rows, params]; they apply from the next launch."""
+        t = np.asarray(values, dtype=np.float32)
+        if t.ndim == 1:
+            t = t[None]
+        P = getattr(self, "params", None)
+        if t.ndim != 2 or (P is not None and t.shape[1] != P):
+            raise ValueError(f"set_resynth_params: takes [params = {P}] or [rows, params]; got shape {np.shape(values)}")
+        t = np.ascontiguousarray(t)
+        check(lib().fdsp_resynth_set_params(self._h, _fptr(t), int(first), t.shape[0]))
+
+    @classmethod
     def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None):
         """Bank of `instances` x `channels` convolvers, convolve(&wave, channel) (convolve.rs) per channel, through the partitioned FFT
         convolution kernels (fdsp_convolve_create): y[n] = sum h[k] x[n - k], no latency, every split into launches the same bits.
@@ -384,7 +427,7 @@ class Bank:
         check(lib().fdsp_bank_clone(self._h, C.byref(h)))
         b = Bank(self.kind, self.voices, _handle=h)
         b.sample_rate = self.sample_rate
-        for k in ("window", "max_len", "block_length", "per_instance"):
+        for k in ("window", "params", "max_len", "block_length", "per_instance"):
             if hasattr(self, k):
                 setattr(b, k, getattr(self, k))
         return b
@@ -670,6 +713,16 @@ def convolve_response_rows(response, channels, rows):
         raise ValueError(f"convolve: the response has {t.shape[-2]} channels for a bank of {Cn}")
     shape = (Cn, t.shape[-1]) if rows is None else (rows, Cn, t.shape[-1])
     return np.ascontiguousarray(np.broadcast_to(t, shape))
+
+
+def resynth_fn_spec(plan, params, flush_denormals=False):
+    """struct fdsp_resynth_fn_spec of a graph.resynth_fn plan with `params` parameters per instance (param_values left NULL)"""
+    spec = _lib.ResynthFnSpec()
+    spec.window_length, spec.inputs, spec.outputs = plan["window"], plan["inputs"], plan["outputs"]
+    spec.params, spec.state = int(params), plan["state"]
+    spec.flush_denormals = 1 if flush_denormals else 0
+    spec.functor, spec.source = plan["functor"].encode(), plan["source"].encode()
+    return spec
 
 
 def resynth_table_rows(values, width, outputs, what):

@@ -1,6 +1,7 @@
 // fd_capi.hip -- C ABI (include/fundsp_hip.h) of the MI355X voice-bank engine.
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -1094,6 +1095,47 @@ static int rs_set_table(fdsp_bank* b, const float* h, size_t first, size_t count
 }
 int fdsp_resynth_set_band(fdsp_bank* b, const float* h_lo_hi, size_t first, size_t count) { return rs_set_table(b, h_lo_hi, first, count, false); }
 int fdsp_resynth_set_gain(fdsp_bank* b, const float* h_gain, size_t first, size_t count) { return rs_set_table(b, h_gain, first, count, true); }
+// closure banks (fd_resynth_fn.hpp, fx_resynth_fn)
+static int rs_check_fn_spec(const fdsp_resynth_fn_spec* sp) {
+    if (!sp) return fail(FDSP_EINVAL, "fdsp_resynth_fn: spec NULL");
+    const int N = sp->window_length;
+    if (N < 4 || N > 8192 || (N & (N - 1)) != 0) return fail(FDSP_EINVAL, "fdsp_resynth_fn: window_length takes a power of two from 4 to 8192");
+    if (sp->inputs < 1 || sp->inputs > 8 || sp->outputs < 1 || sp->outputs > 8) return fail(FDSP_EINVAL, "fdsp_resynth_fn: inputs and outputs take 1 .. 8");
+    if (sp->params < 0 || sp->params > 65536) return fail(FDSP_EINVAL, "fdsp_resynth_fn: params takes 0 .. 65536");
+    if (sp->state < 0 || sp->state > 16) return fail(FDSP_EINVAL, "fdsp_resynth_fn: state takes 0 .. 16 (a bin's state lives in registers)");
+    if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, "fdsp_resynth_fn: flush_denormals takes 0 or 1");
+    if (!sp->functor || !sp->source) return fail(FDSP_EINVAL, "fdsp_resynth_fn: functor or source NULL");
+    bool ident = *sp->functor != 0;   // a type name, template arguments allowed: nothing that could end the generated declaration
+    for (const char* p = sp->functor; *p && ident; p++) ident = isalnum((unsigned char)*p) || *p == '_' || *p == ':' || *p == '<' || *p == '>' || *p == ',' || *p == ' ';
+    if (!ident) return fail(FDSP_EINVAL, "fdsp_resynth_fn: functor takes the name of a type in namespace fd");
+    return FDSP_OK;
+}
+int fdsp_resynth_fn_check(const fdsp_resynth_fn_spec* sp) {
+    if (int rc = rs_check_fn_spec(sp)) return rc;
+    std::shared_ptr<const std::vector<char>> code;
+    return fd::fx_resynth_fn_compile(*sp, &code);
+}
+int fdsp_resynth_fn_create_on(int device, size_t instances, const fdsp_resynth_fn_spec* sp, fdsp_bank** out) {
+    if (!out) return fail(FDSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_resynth_fn_create: no instances");
+    if (int rc = rs_check_fn_spec(sp)) return rc;
+    std::shared_ptr<const std::vector<char>> code;   // compiled before the bank exists: a compile error allocates nothing (fx_resynth_fn finds the code object cached)
+    if (int rc = fd::fx_resynth_fn_compile(*sp, &code)) return rc;
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_resynth_fn(instances, *sp, s, fx); });
+}
+int fdsp_resynth_fn_create(size_t instances, const fdsp_resynth_fn_spec* spec, fdsp_bank** out) { return fdsp_resynth_fn_create_on(-1, instances, spec, out); }
+int fdsp_resynth_set_params(fdsp_bank* b, const float* h, size_t first, size_t count) {
+    if (!b || !h) return fail(FDSP_EINVAL, "fdsp_resynth_set_params: bank or values NULL");
+    float* row0 = nullptr; size_t row = 0;
+    if (int rc = fd::fx_resynth_params(b->fx.get(), first, count, &row0, &row)) return rc;
+    if (count == 0 || row == 0) return FDSP_OK;
+    DeviceGuard guard(b->device);
+    HIPCHK(await_last_render(b));
+    HIPCHK(hipMemcpyAsync(row0, h, count * row * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(sync_bank_stream(b));   // (h is borrowed for the call)
+    return FDSP_OK;
+}
 // ---- convolver banks (fd_fxbank.hpp fx_convolve) -------------------------------------------------------------------------------------------
 static int cv_check_spec(size_t instances, const fdsp_convolve_spec* sp) {
     if (!sp) return fail(FDSP_EINVAL, "fdsp_convolve_create: spec NULL");

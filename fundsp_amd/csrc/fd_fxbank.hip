@@ -267,23 +267,38 @@ int make_net(std::unique_ptr<NetFx> f, double sr, hipStream_t s, std::unique_ptr
 class ResynthFx final : public FxBank {
   public:
     // (the table pointers of `c` are another instance's)
-    ResynthFx(const RsConst& c, int ftz, size_t V) : c_(c), ftz_(ftz), V_(V) { for (const Buf& b : bufs()) *b.p = nullptr; }
-    ~ResynthFx() override { free_bufs(bufs()); }
+    ResynthFx(const RsConst& c, int ftz, size_t V, const RsFn& fn = RsFn{}, std::shared_ptr<const std::vector<char>> code = nullptr)
+        : c_(c), fn_(fn), code_(std::move(code)), ftz_(ftz), V_(V) {
+        for (const Buf& b : bufs()) *b.p = nullptr;
+        fn_.process = nullptr;
+    }
+    ~ResynthFx() override {
+        free_bufs(bufs());
+        if (mod_) hipModuleUnload(mod_);
+    }
     int inputs() const override { return c_.I; }
     int outputs() const override { return c_.O; }
     // FftWindow::set_sample_rate: frequency() follows, every other state stays (resynth.rs:170-172, 325-330).  The bin spacing lives in device
     // memory, in stream order behind the last render: a captured launch replays with the new rate
     int set_sample_rate(double sr, hipStream_t s) override {
         const float fstep = (float)sr / (float)c_.N;
+        const float srf = (float)sr;   // FftWindow::set_sample_rate(sample_rate as f32): what a closure's time() family divides by
         hipError_t e = hipMemcpyAsync(st_.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (fstep is a local)
+        if (e == hipSuccess && fn_.srf) e = hipMemcpyAsync(fn_.srf, &srf, sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (fstep and srf are locals)
         return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_bank_set_sample_rate");
     }
     // Resynth::reset: the sample count and the four windows start over (resynth.rs:332-337)
-    hipError_t reset(hipStream_t s) override { return hipMemsetAsync(st_.samples, 0, sizeof(unsigned long long), s); }
-    // a new bank with zero band / gain tables, then everything but the window and twiddle tables copied over
+    // ... and a closure's state starts over with them (a fresh closure)
+    hipError_t reset(hipStream_t s) override {
+        hipError_t e = hipMemsetAsync(st_.samples, 0, sizeof(unsigned long long), s);
+        if (e == hipSuccess && fn_.state) e = hipMemsetAsync(fn_.state, 0, state_bytes(), s);
+        return e;
+    }
+    // a new bank with zero band / gain tables, then everything but the window and twiddle tables copied over (a closure's parameters and
+    // state among it; its module is loaded from the same code object)
     int clone(hipStream_t s, std::unique_ptr<FxBank>* out) override {
-        auto d = std::make_unique<ResynthFx>(c_, ftz_, V_);
+        auto d = std::make_unique<ResynthFx>(c_, ftz_, V_, fn_, code_);
         const Bufs l = bufs();
         const std::vector<float> band(l[7].bytes / sizeof(float)), gain(l[8].bytes / sizeof(float));
         if (int rc = d->init(band.data(), gain.data(), s)) return rc;
@@ -293,14 +308,19 @@ class ResynthFx final : public FxBank {
     }
     // Resynth has no process override: FDSP_MODE_PROCESS == FDSP_MODE_TICK
     void render(const float* in, float* out, size_t T, size_t fstride, int layout, int, bool, hipStream_t s) override {
-        (ftz_ ? rs_ftz::rs_launch_render : rs_ieee::rs_launch_render)(c_, st_, V_, in, out, T, fstride, layout, s);
+        if (c_.proc == RS_FN) (ftz_ ? rs_ftz::rs_launch_render_fn : rs_ieee::rs_launch_render_fn)(c_, st_, fn_, V_, in, out, T, fstride, layout, s);
+        else (ftz_ ? rs_ftz::rs_launch_render : rs_ieee::rs_launch_render)(c_, st_, V_, in, out, T, fstride, layout, s);
     }
     // the buffers, the tables uploaded (band [rows][O][2] and gain [rows][O][N/2 + 1] where the processor has them), empty windows at 44.1 kHz
     int init(const float* band, const float* gain, hipStream_t s) {
         const Bufs l = bufs();
-        const float fstep = (float)FDSP_DEFAULT_SR / (float)c_.N;
+        const float fstep = (float)FDSP_DEFAULT_SR / (float)c_.N, srf = (float)FDSP_DEFAULT_SR;
         std::vector<float> tw(c_.N), hann(c_.N), hz(c_.N);
         rs_tables(c_.N, hann.data(), hz.data(), tw.data());
+        if (code_) {   // a closure bank: its module on this device, before anything is allocated
+            if (hipModuleLoadData(&mod_, code_->data()) != hipSuccess) { mod_ = nullptr; (void)hipGetLastError(); return api_fail(FDSP_EDEVICE, "fdsp_resynth_fn_create: hipModuleLoadData failed for the compiled functor"); }
+            if (hipModuleGetFunction(&fn_.process, mod_, "rs_process") != hipSuccess) { (void)hipGetLastError(); return api_fail(FDSP_EDEVICE, "fdsp_resynth_fn_create: the compiled functor lacks its entry point"); }
+        }
         hipError_t e = alloc_bufs(l);
         if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.tw, tw.data(), l[0].bytes, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync((void*)c_.hann, hann.data(), l[1].bytes, hipMemcpyHostToDevice, s);
@@ -312,18 +332,29 @@ class ResynthFx final : public FxBank {
         if (e == hipSuccess) e = hipMemcpyAsync(st_.fstep, &fstep, sizeof(float), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemsetAsync(st_.frames, 0, l[3].bytes, s);
         if (e == hipSuccess) e = hipMemsetAsync(st_.xin, 0, l[4].bytes, s);
+        for (size_t i = 9; i < l.size() && e == hipSuccess; i++)   // a closure bank's workspace, parameters, state: defined from the start
+            if (l[i].bytes) e = hipMemsetAsync(*l[i].p, 0, l[i].bytes, s);
+        if (e == hipSuccess && fn_.srf) e = hipMemcpyAsync(fn_.srf, &srf, sizeof(float), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_resynth_create buffers");
     }
+    size_t state_bytes() const { return V_ * (size_t)(c_.N / 2 + 1) * fn_.S * sizeof(float); }
     Bufs bufs() {   // the constant tables first
         const size_t N = (size_t)c_.N, rows = (size_t)c_.rows * c_.O;
+        const bool fn = c_.proc == RS_FN;
         return {{(void**)&c_.tw, N / 2 * sizeof(float2)}, {(void**)&c_.hann, N * sizeof(float)}, {(void**)&c_.hz, N * sizeof(float)},
                 {(void**)&st_.frames, (size_t)c_.R * V_ * c_.O * N * sizeof(float)}, {(void**)&st_.xin, V_ * (size_t)c_.I * c_.Rx * sizeof(float)},
                 {(void**)&st_.samples, sizeof(unsigned long long)}, {(void**)&st_.fstep, sizeof(float)},
-                {(void**)&c_.band, c_.proc == RS_BAND ? rows * sizeof(float2) : 0}, {(void**)&c_.gain, c_.proc == RS_GAIN ? rows * (N / 2 + 1) * sizeof(float) : 0}};
+                {(void**)&c_.band, c_.proc == RS_BAND ? rows * sizeof(float2) : 0}, {(void**)&c_.gain, c_.proc == RS_GAIN ? rows * (N / 2 + 1) * sizeof(float) : 0},
+                // a closure bank's part (0 bytes on a stock bank: the pointers stay NULL)
+                {(void**)&fn_.x, fn ? V_ * fn_.Fc * (size_t)c_.I * (N / 2 + 1) * sizeof(float2) : 0}, {(void**)&fn_.y, fn ? V_ * fn_.Fc * (size_t)c_.O * (N / 2 + 1) * sizeof(float2) : 0},
+                {(void**)&fn_.params, fn ? V_ * (size_t)fn_.P * sizeof(float) : 0}, {(void**)&fn_.state, fn ? state_bytes() : 0}, {(void**)&fn_.srf, fn ? sizeof(float) : 0}};
     }
 
     RsConst c_;
+    RsFn fn_;
+    std::shared_ptr<const std::vector<char>> code_;   // the process module's code object (shared by the banks of one functor)
+    hipModule_t mod_ = nullptr;
     RsState st_{};
     int ftz_;   // 1: the flush-to-zero instantiation (a Feedback node in front)
     size_t V_;
@@ -440,8 +471,18 @@ int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_
     return make_net(std::make_unique<FdnxFx>(d, instances), sample_rate, s, out);
 }
 
+// the frame ring of a bank: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large
+static void rs_ring(RsConst& c, size_t V) {
+    const int H = c.N / 4;
+    size_t R = ((size_t)256 << 20) / (V * (size_t)c.O * c.N * sizeof(float));
+    const size_t rmax = 5 + 65536 / (size_t)H;
+    R = R < 8 ? 8 : (R > rmax ? rmax : R);
+    c.R = (int)R;
+    c.Lmax = (c.R - 5) * H;
+}
+
 int fx_resynth(size_t instances, const fdsp_resynth_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
-    const int N = sp.window_length, H = N / 4, O = sp.outputs;
+    const int N = sp.window_length, O = sp.outputs;
     const size_t V = instances;
     RsConst c{};
     c.N = N;
@@ -452,12 +493,7 @@ int fx_resynth(size_t instances, const fdsp_resynth_spec& sp, hipStream_t s, std
     for (int o = 0; o < RS_MAX_CH; o++) c.src[o] = o < O ? sp.source[o] : -1;
     c.rows = sp.per_instance ? (int)V : 1;
     c.invN = 1.0f / (float)N;
-    // frame ring: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large
-    size_t R = ((size_t)256 << 20) / (V * (size_t)O * N * sizeof(float));
-    const size_t rmax = 5 + 65536 / (size_t)H;
-    R = R < 8 ? 8 : (R > rmax ? rmax : R);
-    c.R = (int)R;
-    c.Lmax = (c.R - 5) * H;
+    rs_ring(c, V);
     c.Rx = 1;
     while (c.Rx < c.Lmax + N) c.Rx <<= 1;
     std::vector<float> band;
@@ -469,10 +505,64 @@ int fx_resynth(size_t instances, const fdsp_resynth_spec& sp, hipStream_t s, std
     return FDSP_OK;
 }
 
+int fx_resynth_fn_compile(const fdsp_resynth_fn_spec& sp, std::shared_ptr<const std::vector<char>>* code) {
+    std::string log;
+    if (jit_compile_resynth_fn(sp.functor, sp.source, sp.params, sp.state, sp.flush_denormals != 0, code, &log) != 0)
+        return api_fail(FDSP_EINVAL, "fdsp_resynth_fn: " + log);
+    return FDSP_OK;
+}
+
+int fx_resynth_fn(size_t instances, const fdsp_resynth_fn_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    std::shared_ptr<const std::vector<char>> code;
+    if (int rc = fx_resynth_fn_compile(sp, &code)) return rc;   // before anything is allocated
+    const int N = sp.window_length, H = N / 4, I = sp.inputs, O = sp.outputs;
+    const size_t V = instances;
+    RsConst c{};
+    c.N = N;
+    while ((1 << c.logN) < N) c.logN++;
+    c.I = I;
+    c.O = O;
+    c.proc = RS_FN;
+    for (int o = 0; o < RS_MAX_CH; o++) c.src[o] = -1;
+    c.rows = 1;
+    c.invN = 1.0f / (float)N;
+    rs_ring(c, V);
+    // frames per chunk (fd_resynth_fn.hpp): the spectrum workspace within the frame ring's size, at least two frames
+    RsFn fn{};
+    fn.P = sp.params;
+    fn.S = sp.state;
+    long long Fc = ((long long)c.R * O * N) / (2LL * (I + O) * (N / 2 + 1));
+    Fc = Fc < 2 ? 2 : (Fc > c.R - 4 ? c.R - 4 : Fc);
+    fn.Fc = (int)Fc;
+    c.Lmax = (fn.Fc - 1) * H;
+    c.Rx = 1;
+    while (c.Rx < c.Lmax + N) c.Rx <<= 1;
+    auto r = std::make_unique<ResynthFx>(c, sp.flush_denormals, V, fn, code);
+    if (int rc = r->init(nullptr, nullptr, s)) return rc;
+    if (sp.param_values && sp.params > 0) {
+        hipError_t e = hipMemcpyAsync(r->fn_.params, sp.param_values, V * (size_t)sp.params * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the host array is borrowed)
+        if (e != hipSuccess) return hip_fail(e, "fdsp_resynth_fn_create parameters");
+    }
+    *out = std::move(r);
+    return FDSP_OK;
+}
+
+int fx_resynth_params(FxBank* fx, size_t first, size_t count, float** row0, size_t* row_floats) {
+    auto* r = dynamic_cast<ResynthFx*>(fx);
+    if (!r) return api_fail(FDSP_EINVAL, "fdsp_resynth_set_params: not a resynthesizer bank");
+    if (r->c_.proc != RS_FN) return api_fail(FDSP_ENOTSUP, "fdsp_resynth_set_params: a stock-processor bank has no closure parameters (fdsp_resynth_set_band / _gain)");
+    if (first > r->V_ || count > r->V_ - first) return api_fail(FDSP_EINVAL, "fdsp_resynth_set_params: instances out of range");
+    *row_floats = (size_t)r->fn_.P;
+    *row0 = r->fn_.params + first * *row_floats;
+    return FDSP_OK;
+}
+
 int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats) {
     auto* r = dynamic_cast<ResynthFx*>(fx);
     if (!r) return api_fail(FDSP_EINVAL, "fdsp_resynth_set_band / _gain: not a resynthesizer bank");
     const RsConst& c = r->c_;
+    if (c.proc == RS_FN) return api_fail(FDSP_ENOTSUP, "fdsp_resynth_set_band / _gain: a closure bank has no stock tables (fdsp_resynth_set_params)");
     if (c.proc != (gain ? FDSP_RESYNTH_GAIN : FDSP_RESYNTH_BAND))
         return api_fail(FDSP_EINVAL, gain ? "fdsp_resynth_set_gain: the bank's processor is not FDSP_RESYNTH_GAIN" : "fdsp_resynth_set_band: the bank's processor is not FDSP_RESYNTH_BAND");
     const size_t rows = (size_t)c.rows;

@@ -9,6 +9,7 @@
 
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/fundsp_hip.h"
 #include "fd_fdn.hpp"   // FdnBus
@@ -42,6 +43,11 @@ int fx_reverb3_stereo(size_t instances, double time, double diffusion, int svf_m
                       std::unique_ptr<FxBank>* out);
 int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t stream, std::unique_ptr<FxBank>* out);
 int fx_resynth(size_t instances, const fdsp_resynth_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// a closure bank (fd_resynth_fn.hpp): the functor's module is compiled and loaded before anything is allocated; _compile alone needs no device
+int fx_resynth_fn(size_t instances, const fdsp_resynth_fn_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
+int fx_resynth_fn_compile(const fdsp_resynth_fn_spec& spec, std::shared_ptr<const std::vector<char>>* code);
+// fdsp_resynth_set_params: checks the bank (`fx` may be NULL) and the instances; the device address of row `first` and the floats per row
+int fx_resynth_params(FxBank* fx, size_t first, size_t count, float** row0, size_t* row_floats);
 // fdsp_resynth_set_band / _gain: checks the bank (`fx` may be NULL) and the rows; the device address of row `first` and the floats per row
 int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats);
 int fx_convolve(size_t instances, const fdsp_convolve_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);

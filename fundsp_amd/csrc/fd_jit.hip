@@ -17,12 +17,14 @@
 
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <cstdio>
 #include <sstream>
 
 #include "fd_engine.hpp"
+#include "fd_resynth.hpp"
 
 namespace fd {
 
@@ -467,21 +469,14 @@ int jit_compile_code(const std::string& type_expr, const std::string& prelude, s
 
 const char* jit_compiler_origin() { return rtc().origin.c_str(); }
 
+namespace {
+// `src` next to the library's own headers `names` (read from csrc/ beside the .so), with the library's code-generation flags; `what` names
+// the thing compiled in the error message and the dump
+int compile_program(const std::string& src, const std::string& what, const char* const* names, int nh, bool ftz, bool wide_ilp, std::vector<char>* code,
+                    std::string* log);
+}  // namespace
+
 int jit_compile_src(const std::string& src, const std::string& type_expr, std::vector<char>* code, std::string* log) {
-    const std::string dir = lib_dir() + "/csrc/";
-    const char* names[3] = {"fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp"};
-    std::string hdr[3];
-    for (int i = 0; i < 3; i++)
-        if (!read_file(dir + names[i], &hdr[i])) {
-            *log = "cannot read " + dir + names[i] + " (the JIT compiles the engine's own headers)";
-            return -1;
-        }
-    const char* hsrc[3] = {hdr[0].c_str(), hdr[1].c_str(), hdr[2].c_str()};
-    hiprtcProgram prog;
-    if (rtc().create(&prog, src.c_str(), "fdsp_jit_graph.hip", 3, hsrc, names) != HIPRTC_SUCCESS) {
-        *log = "hiprtcCreateProgram failed";
-        return -1;
-    }
     // same code-generation flags as the ahead-of-time kinds (see Makefile for -fno-slp-vectorize)
     // a graph with a Feedback node renders with f32 denormals flushed, like the reference after Feedback::new's
     // prevent_denormals() (feedback.rs:96, denormal.rs:18)
@@ -508,6 +503,52 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
             }
         }
     }
+    static const char* const names[3] = {"fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp"};
+    return compile_program(src, "graph type `" + type_expr + "`", names, 3, ftz, wide_ilp, code, log);
+}
+
+// The process module of a resynthesizer bank's closure (fd_resynth_fn.hpp): the functor's source in namespace fd and rs_process around it.
+// Equal requests share one code object: banks of one functor (and their clones) compile once per process.
+int jit_compile_resynth_fn(const std::string& functor, const std::string& source, int params, int state, bool ftz,
+                           std::shared_ptr<const std::vector<char>>* code, std::string* log) {
+    static std::mutex mu;
+    static std::map<std::string, std::shared_ptr<const std::vector<char>>> cache;
+    const std::string key = functor + '\n' + std::to_string(params) + ' ' + std::to_string(state) + ' ' + (ftz ? '1' : '0') + '\n' + source;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = cache.find(key);
+        if (it != cache.end()) { *code = it->second; return 0; }
+    }
+    std::string s = "#include \"fd_resynth_fn.hpp\"\nnamespace fd {\n" + source + "\n}\n";
+    s += "static_assert(fd::" + functor + "::PARAMS == " + std::to_string(params) + ", \"the functor's PARAMS differs from the spec's params\");\n";
+    s += "static_assert(fd::" + functor + "::STATE == " + std::to_string(state) + ", \"the functor's STATE differs from the spec's state\");\n";
+    s += "extern \"C\" __global__ __launch_bounds__(256) void rs_process(fd::RsFnArgs a) { fd::rs_process_body<fd::" + functor + ">(a); }\n";
+    static const char* const names[1] = {"fd_resynth_fn.hpp"};
+    auto co = std::make_shared<std::vector<char>>();
+    if (compile_program(s, "resynth functor `" + functor + "`", names, 1, ftz, false, co.get(), log) != 0) return -1;
+    std::lock_guard<std::mutex> lock(mu);
+    *code = cache.emplace(key, co).first->second;
+    return 0;
+}
+
+namespace {
+int compile_program(const std::string& src, const std::string& what, const char* const* names, int nh, bool ftz, bool wide_ilp, std::vector<char>* code,
+                    std::string* log) {
+    const std::string dir = lib_dir() + "/csrc/";
+    std::vector<std::string> hdr(nh);
+    std::vector<const char*> hsrc(nh);
+    for (int i = 0; i < nh; i++) {
+        if (!read_file(dir + names[i], &hdr[i])) {
+            *log = "cannot read " + dir + names[i] + " (the JIT compiles the engine's own headers)";
+            return -1;
+        }
+        hsrc[i] = hdr[i].c_str();
+    }
+    hiprtcProgram prog;
+    if (rtc().create(&prog, src.c_str(), "fdsp_jit_graph.hip", nh, hsrc.data(), (const char**)names) != HIPRTC_SUCCESS) {
+        *log = "hiprtcCreateProgram failed";
+        return -1;
+    }
     std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize"};
     if (ftz) {
         opts.push_back("-fgpu-flush-denormals-to-zero");
@@ -521,7 +562,7 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
     if (const char* dump = getenv("FDSP_JIT_DUMP")) {  // debugging aid: the generated source and code object of every compiled module, numbered
         static int dump_n = 0;
         const std::string base = std::string(dump) + "/jit_" + std::to_string(dump_n++);
-        if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(("// " + type_expr + "\n" + src).c_str(), f); fclose(f); }
+        if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(("// " + what + "\n" + src).c_str(), f); fclose(f); }
         size_t n = 0;
         if (r == HIPRTC_SUCCESS && rtc().code_size(prog, &n) == HIPRTC_SUCCESS) {
             std::vector<char> co(n);
@@ -536,7 +577,7 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
         rtc().get_log(prog, &(*log)[0]);
     }
     if (r != HIPRTC_SUCCESS) {
-        *log = "hiprtc: " + std::string(rtc().error_string(r)) + " while compiling graph type `" + type_expr + "`:\n" + *log;
+        *log = "hiprtc: " + std::string(rtc().error_string(r)) + " while compiling " + what + ":\n" + *log;
         rtc().destroy(&prog);
         return -1;
     }
@@ -547,6 +588,7 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
     rtc().destroy(&prog);
     return 0;
 }
+}  // namespace
 
 int jit_make_kind(const std::string& name, const std::string& type_expr, const std::string& prelude, KindOps* out,
                   std::string* err) {

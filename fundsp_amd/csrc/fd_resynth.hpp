@@ -41,9 +41,16 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "fd_resynth_fn.hpp"   // RsFnArgs: the argument block of a closure bank's run-time compiled process kernel
+
 namespace fd {
 
 constexpr int RS_PASS = 0, RS_BAND = 1, RS_GAIN = 2;
+constexpr int RS_FN = 3;   // a caller's closure (fd_resynth_fn.hpp): the host's mark only, k_rs_frames never sees it
 constexpr int RS_MAX_CH = 8;
 constexpr int RS_MIN_LOGN = 2, RS_MAX_LOGN = 13;   // N = 4 .. 8192
 
@@ -70,16 +77,35 @@ struct RsState {
     float* fstep;                  // [1] (sample_rate as f32) / (N as f32): frequency(i) = fstep * i (device memory, so a replayed capture follows set_sample_rate)
 };
 
+// a closure bank's part (fd_resynth_fn.hpp): the spectrum workspace, parameters, per-bin state and the process kernel of its module
+struct RsFn {
+    int P, S, Fc;             // parameters per instance, state values per (instance, bin), frames per chunk (RsConst::Lmax = (Fc - 1) * H)
+    float2* x;                // [V][Fc][I][N/2 + 1] input spectra of the chunk
+    float2* y;                // [V][Fc][O][N/2 + 1] output spectra
+    float* params;            // [V][P]
+    float* state;             // [V][N/2 + 1][S]
+    float* srf;               // [1] sample rate as f32 (the time() family; device memory like fstep)
+    hipFunction_t process;    // rs_process of the bank's module
+};
+
 // host: the window and twiddle tables of N (fdsp_resynth_tables); hz = hann * (2/3 as f32)
 void rs_tables(int N, float* hann, float* hz, float* tw);
+// fd_jit.hip: the process module of a functor -- fd_resynth_fn.hpp + `source` in namespace fd + rs_process around `functor`, with
+// static_asserts that its PARAMS / STATE equal `params` / `state`.  No device needed.  Equal requests share one code object.  0 or -1 + log
+int jit_compile_resynth_fn(const std::string& functor, const std::string& source, int params, int state, bool ftz,
+                           std::shared_ptr<const std::vector<char>>* code, std::string* log);
 
 namespace rs_ieee {
 void rs_launch_render(const RsConst& c, const RsState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout,
                       hipStream_t stream);
+void rs_launch_render_fn(const RsConst& c, const RsState& st, const RsFn& fn, size_t V, const float* in, float* out, size_t T, size_t fstride,
+                         int layout, hipStream_t stream);
 }
 namespace rs_ftz {   // the same kernels compiled with f32 denormals flushed (a Feedback node in front of the resynthesizer)
 void rs_launch_render(const RsConst& c, const RsState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout,
                       hipStream_t stream);
+void rs_launch_render_fn(const RsConst& c, const RsState& st, const RsFn& fn, size_t V, const float* in, float* out, size_t T, size_t fstride,
+                         int layout, hipStream_t stream);
 }
 
 }  // namespace fd

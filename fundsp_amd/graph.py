@@ -882,7 +882,8 @@ def resynth(window, inputs=1, outputs=1, processor="pass", source=None, band=Non
     if not (1 <= I <= 8 and 1 <= O <= 8):
         raise ValueError(f"resynth: inputs and outputs take 1 .. 8 (got {I} -> {O})")
     if processor not in RESYNTH_PROCESSORS:
-        raise ValueError(f"resynth: processor takes one of {RESYNTH_PROCESSORS}, got {processor!r}")
+        raise ValueError(f"resynth: processor takes one of {RESYNTH_PROCESSORS}, got {processor!r}; a closure of your own goes through "
+                         "resynth_fn(window, functor, source, ..)")
     src = [o % I for o in range(O)] if source is None else [int(x) for x in source]
     if len(src) != O or any(x < -1 or x >= I for x in src):
         raise ValueError(f"resynth: source needs {O} entries, each an input channel 0 .. {I - 1} or -1 (silent): {src}")
@@ -900,6 +901,54 @@ def resynth(window, inputs=1, outputs=1, processor="pass", source=None, band=Non
             raise ValueError(f"resynth: gain takes [window/2 + 1 = {N // 2 + 1}], [outputs, bins] or [instances, outputs, bins]; got shape {t.shape}")
     g = Graph(f"ResynthPing<{I},{O}>", I, O, [], 0, _RESYNTH_SRC)
     g.resynth_plan = dict(window=N, inputs=I, outputs=O, processor=processor, source=src, band=band, gain=gain)
+    return g
+
+
+def resynth_fn_params(params, values, instances=None):
+    """A closure's parameters as the C ABI reads them: None (no parameters), f32 [P] (every instance the same) or [instances, P].  `params`:
+    keyword -> scalar or per-instance array, keyword order = parameter index; `values`: the whole table at once, [P] or [instances, P]."""
+    if values is not None:
+        if params:
+            raise ValueError("resynth_fn: give the parameters as keywords or as param_values=, not both")
+        t = np.asarray(values, dtype=np.float32)
+        if t.ndim not in (1, 2) or t.shape[-1] < 1:
+            raise ValueError(f"resynth_fn: param_values takes [params] or [instances, params]; got shape {t.shape}")
+    elif not params:
+        return None
+    else:
+        cols = [np.asarray(v, dtype=np.float32) for v in params.values()]
+        for k, c in zip(params, cols):
+            if c.ndim > 1:
+                raise ValueError(f"resynth_fn: parameter {k!r} takes a scalar or a per-instance array; got shape {c.shape}")
+        lens = {c.shape[0] for c in cols if c.ndim == 1}
+        if len(lens) > 1:
+            raise ValueError(f"resynth_fn: per-instance parameters of different lengths {sorted(lens)}")
+        t = np.stack([np.broadcast_to(c, tuple(lens)) for c in cols], axis=-1) if lens else np.array(cols, dtype=np.float32)
+    if t.shape[-1] > 65536:
+        raise ValueError(f"resynth_fn: {t.shape[-1]} parameters (a bank takes 0 .. 65536)")
+    if instances is not None and t.ndim == 2 and t.shape[0] != instances:
+        raise ValueError(f"resynth_fn: per-instance parameters for {t.shape[0]} instances on a bank of {instances}")
+    return np.ascontiguousarray(t, dtype=np.float32)
+
+
+def resynth_fn(window, functor, source, inputs=1, outputs=1, state=0, param_values=None, **params):
+    """resynth::<I, O, _>(window, |fft| ...) (prelude.rs:2825-2856) with the caller's closure: `functor` names a C++ type in namespace fd that
+    `source` defines in the per-bin form of fundsp_amd/csrc/fd_resynth_fn.hpp (`bin(fft, i)` reads any input bin, writes output bin i);
+    `state`: f32 values per bin that live from frame to frame (the functor's STATE); `**params`: the functor's PARAMS in keyword order,
+    scalars or per-instance arrays as for envelope(..) (or the whole table as param_values=[P] / [instances, P]).  The arguments are checked
+    here, on the host; Bank.from_graph renders the node alone or as `front >> resynth_fn(..)`."""
+    N, I, O, S = int(window), int(inputs), int(outputs), int(state)
+    if N < 4 or N > 8192 or N & (N - 1):
+        raise ValueError(f"resynth_fn: window {N} is not a power of two from 4 to 8192")
+    if not (1 <= I <= 8 and 1 <= O <= 8):
+        raise ValueError(f"resynth_fn: inputs and outputs take 1 .. 8 (got {I} -> {O})")
+    if not 0 <= S <= 16:
+        raise ValueError(f"resynth_fn: state takes 0 .. 16 values per bin (got {S})")
+    if not isinstance(functor, str) or not isinstance(source, str) or not functor.strip() or not source.strip():
+        raise ValueError("resynth_fn: functor (the type's name) and source (its C++ definition) take non-empty strings")
+    t = resynth_fn_params(params, param_values)
+    g = Graph(f"ResynthPing<{I},{O}>", I, O, [], 0, _RESYNTH_SRC)
+    g.resynth_fn_plan = dict(window=N, functor=functor, source=source, inputs=I, outputs=O, state=S, param_values=t)
     return g
 
 

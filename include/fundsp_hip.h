@@ -282,6 +282,35 @@ int fdsp_resynth_create_on(int device, size_t instances, const fdsp_resynth_spec
  * set_band takes [count][outputs][2] (lo, hi) in Hz, set_gain [count][outputs][window_length / 2 + 1]. */
 int fdsp_resynth_set_band(fdsp_bank* bank, const float* h_lo_hi, size_t first, size_t count);
 int fdsp_resynth_set_gain(fdsp_bank* bank, const float* h_gain, size_t first, size_t count);
+/* Resynthesizer banks with the CALLER's processing closure: resynth::<I, O, _>(window_length, |fft| ...) where the closure is a C++ functor
+ * in namespace fd, given as source text in the per-bin form and compiled by the library's own run-time compiler when the bank is created
+ * (never inside a render: a first launch can be captured).  fundsp_amd/csrc/fd_resynth_fn.hpp states the contract -- bin(fft, i) is called
+ * once per frame and bin, reads any input bin through fft.at(channel, j) and writes output bin i only through fft.set(channel, i, value);
+ * fft mirrors FftWindow (bins, frequency, the time() family in f64, param(p), state(s)) -- and the three stock closures as functors.
+ * `functor` names the type, `source` defines it; `params` f32 values per instance (0 .. 65536) and `state` f32 values per (instance, bin)
+ * (0 .. 16) must equal the functor's PARAMS / STATE.  param_values is [instances][params], NULL = zeros.  With state > 0 the frames of an
+ * instance are processed in increasing order.  The forward and inverse transforms are the stock bank's, cut at the spectra, which pass
+ * through a workspace of instances x Fc x (inputs + outputs) x (N/2 + 1) x 8 bytes (Fc frames per chunk, chosen so that the workspace does
+ * not exceed the frame ring); everything is allocated at creation.  A compile error answers FDSP_EINVAL with the compiler's log in
+ * fdsp_last_error() and allocates nothing.  reset zeroes the state and restarts the windows; clone copies state and parameters;
+ * set_sample_rate moves frequency() and the time() family only.  fdsp_resynth_set_band / _gain on a closure bank and
+ * fdsp_resynth_set_params on a stock bank answer FDSP_ENOTSUP; bus, mix-down, slots, rings and events FDSP_ENOTSUP as for the stock banks. */
+typedef struct fdsp_resynth_fn_spec {
+    int window_length, inputs, outputs;
+    int params;                         /* f32 parameters per instance: the functor's PARAMS */
+    int state;                          /* f32 state values per (instance, bin): the functor's STATE */
+    int flush_denormals;                /* 1: f32 denormals flushed (a Feedback node in front) */
+    const char* functor;                /* the type's name in namespace fd */
+    const char* source;                 /* its definition */
+    const float* param_values;          /* [instances][params], NULL = zeros */
+} fdsp_resynth_fn_spec;
+int fdsp_resynth_fn_create(size_t instances, const fdsp_resynth_fn_spec* spec, fdsp_bank** out);
+int fdsp_resynth_fn_create_on(int device, size_t instances, const fdsp_resynth_fn_spec* spec, fdsp_bank** out);
+/* Host only, no device (like fdsp_graph_check): checks the spec and compiles the functor's module; FDSP_EINVAL + the compiler's log. */
+int fdsp_resynth_fn_check(const fdsp_resynth_fn_spec* spec);
+/* Replace the parameters of instances first .. first+count-1 between launches from h_values [count][params], with the ordering of
+ * fdsp_bank_set_param: they apply from the next launch, i.e. to the frames completing at sample counts above the launch's start. */
+int fdsp_resynth_set_params(fdsp_bank* bank, const float* h_values, size_t first, size_t count);
 /* Host only, no device: the bank's tables for window_length N -- hann[N] = 0.5 + 0.5 * cosf(((i - N/2) as f32 * TAU) / N as f32) and
  * twiddles[N/2][2] = (cos, -sin)(2 pi j / N) computed in double and rounded to f32.  Either pointer may be NULL. */
 int fdsp_resynth_tables(int window_length, float* h_hann, float* h_twiddles);

@@ -579,6 +579,15 @@ class Bank {
         b.kind_ = "fdn_network";
         return b;
     }
+    // resynth::<I, O, _>(window_length, |fft| ...) with the caller's closure as a C++ functor in source form (fdsp_resynth_fn_create,
+    // fundsp_amd/csrc/fd_resynth_fn.hpp): compiled here, at creation; set_resynth_params replaces parameter rows between launches
+    static Bank resynth_fn(size_t instances, const fdsp_resynth_fn_spec& spec) {
+        Bank b;
+        check(fdsp_resynth_fn_create(instances, &spec, &b.h_));
+        b.kind_ = "resynth";
+        return b;
+    }
+    void set_resynth_params(const float* values, size_t first, size_t count) { check(fdsp_resynth_set_params(h_, values, first, count)); }
     // resynth::<I, O, _>(window_length, closure) with a stock closure (fdsp_resynth_create, include/fundsp_hip.h): batched FFT frames
     static Bank resynth(size_t instances, const fdsp_resynth_spec& spec) {
         Bank b;

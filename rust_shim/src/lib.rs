@@ -65,6 +65,19 @@ pub mod ffi {
         pub hi_hz: *const f32,
         pub gain: *const f32,
     }
+    /// `struct fdsp_resynth_fn_spec` (fdsp_resynth_fn_create): a resynthesizer with the caller's closure as a C++ functor in source form
+    #[repr(C)]
+    pub struct FdspResynthFnSpec {
+        pub window_length: c_int,
+        pub inputs: c_int,
+        pub outputs: c_int,
+        pub params: c_int,
+        pub state: c_int,
+        pub flush_denormals: c_int,
+        pub functor: *const c_char,
+        pub source: *const c_char,
+        pub param_values: *const f32,
+    }
     /// `struct fdsp_convolve_spec` (fdsp_convolve_create): convolvers by partitioned FFT convolution, one response row per channel
     #[repr(C)]
     pub struct FdspConvolveSpec {
@@ -107,6 +120,8 @@ pub mod ffi {
         pub fn fdsp_fdn_create_on(device: c_int, instances: usize, lines: c_int, delays: *const f64, taps: c_int, weights: *const f32, inputs: c_int, outputs: c_int, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_network_create_on(device: c_int, instances: usize, net: *const FdspFdnNetwork, sample_rate: f64, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_resynth_create_on(device: c_int, instances: usize, spec: *const FdspResynthSpec, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_resynth_fn_create_on(device: c_int, instances: usize, spec: *const FdspResynthFnSpec, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_resynth_set_params(bank: *mut FdspBank, values: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_resynth_set_band(bank: *mut FdspBank, lo_hi: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_resynth_set_gain(bank: *mut FdspBank, gain: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_convolve_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, out: *mut *mut FdspBank) -> c_int;
@@ -345,6 +360,38 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_resynth_create_on(device as c_int, instances, &spec, &mut bank) })?;
         Self::adopt(bank, "resynth", instances)
+    }
+
+    /// `instances` x `resynth::<I, O, _>(window_length, |fft| ...)` with the caller's closure (include/fundsp_hip.h `fdsp_resynth_fn_spec`):
+    /// `functor` names a C++ type in namespace fd that `source` defines in the per-bin form of fundsp_amd/csrc/fd_resynth_fn.hpp; `params`
+    /// f32 values per instance (`param_values`: [instances][params], empty = zeros) and `state` f32 values per (instance, bin) must equal the
+    /// functor's PARAMS / STATE.  Compiled at creation.  Source only: no Rust toolchain has built it.
+    pub fn resynth_fn(instances: usize, window_length: usize, inputs: usize, outputs: usize, functor: &str, source: &str, params: usize,
+                      state: usize, param_values: &[f32], flush_denormals: bool, device: i32) -> Result<Self, String> {
+        if !param_values.is_empty() && param_values.len() != instances * params {
+            return Err("HipBank::resynth_fn: param_values takes instances x params values (or none: zeros)".into());
+        }
+        let functor = CString::new(functor).map_err(|e| e.to_string())?;
+        let source = CString::new(source).map_err(|e| e.to_string())?;
+        let spec = FdspResynthFnSpec {
+            window_length: window_length as c_int,
+            inputs: inputs as c_int,
+            outputs: outputs as c_int,
+            params: params as c_int,
+            state: state as c_int,
+            flush_denormals: flush_denormals as c_int,
+            functor: functor.as_ptr(),
+            source: source.as_ptr(),
+            param_values: if param_values.is_empty() { core::ptr::null() } else { param_values.as_ptr() },
+        };
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_resynth_fn_create_on(device as c_int, instances, &spec, &mut bank) })?;
+        Self::adopt(bank, "resynth", instances)
+    }
+
+    /// Replace the closure parameters of instances `first ..` (fdsp_resynth_set_params): `values` holds [count][params]; they apply from the next launch.
+    pub fn set_resynth_params(&mut self, values: &[f32], first: usize, count: usize) -> Result<(), String> {
+        check(unsafe { fdsp_resynth_set_params(self.bank, values.as_ptr(), first, count) })
     }
 
     /// `instances` x `channels` convolvers, `convolve(&wave, channel)` per channel (src/convolve.rs; include/fundsp_hip.h
