@@ -44,6 +44,11 @@
 // M and P live on the device too (dims), so a replayed capture follows set_response.  KB = clamp(256 MiB / (V * C * (B + 1) * 8 B), 8, 64).
 // Memory: V*C * (Rx*4 + (R + KB)*(B + 1)*8 + (KB + 1)*B*4) + rows*C * ((Pcap + 1)*B*4 + Pcap*(B + 1)*8) bytes, rows = V with per-instance
 // responses, else 1.
+//
+// Accuracy of the statement against a float64 convolution, max |y - y64| / (sum |h| * max |x|) (tests/test_convolve_ref.py, four times the
+// largest figure measured over 8 seeds): 4.1e-7 at B = 64, 9.5e-7 at B = 128 .. 4096.  The error follows sqrt(P) * log2(2B) * 2^-24 with a
+// constant of 0.33 at most; the largest figures belong to SHORT responses under a large capacity, where the transforms' noise of the order
+// log2(2B) * 2^-24 stands against a small sum |h|, not to the long heads or the many partitions.
 #pragma once
 
 #include <hip/hip_runtime.h>

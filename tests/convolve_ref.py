@@ -2,7 +2,8 @@
 
 Uniformly partitioned FFT convolution over COMPLETE blocks with a direct head, every operation one f32 rounding in the order the header
 states, vectorised over instances and channels; `ftz=True` flushes every operand and result below 2^-126 to a zero of the same sign
-(resynth_ref._Ops).  The transforms are resynth_ref's (the project's cfft, the real-FFT split, the inverse), as the kernels share them.
+(resynth_ref._Ops: a result on its exact value, before rounding, as the hardware does).  The transforms are resynth_ref's (the project's
+cfft, the real-FFT split, the inverse), as the kernels share them.
 
 Because only complete blocks are transformed and every output sample is a function of the absolute sample index, rendering in one piece, sample
 by sample or in ragged pieces is the same computation: `Convolver.process` may be called with any split.
@@ -22,6 +23,11 @@ def block_length(max_len):
     while B < 4096 and B * B < 8 * int(max_len):
         B *= 2
     return B
+
+
+def blocks_per_chunk(V, C, B):
+    """KB of fd_convolve.hpp: a launch is cut into chunks of at most KB * B samples, KB = clamp(256 MiB / (V * C * (B + 1) * 8 B), 8, 64)"""
+    return min(max((256 << 20) // (int(V) * int(C) * (int(B) + 1) * 8), 8), 64)
 
 
 def twiddles(N):
@@ -108,12 +114,11 @@ class Convolver:
             j, r0 = divmod(self.n, B)
             cnt = min(B - r0, T - t)                            # the samples of this call inside block j
             xb = self.x[..., j * B:j * B + r0 + cnt]
-            r = np.arange(r0, r0 + cnt)
-            a = op.mul(self.h[..., 0:1], xb[..., r])
+            a = op.mul(self.h[..., 0:1], xb[..., r0:])
             for i in range(1, min(r0 + cnt - 1, M - 1) + 1):
-                sel = r >= i
-                a[..., sel] = op.add(a[..., sel], op.mul(self.h[..., i:i + 1], xb[..., r[sel] - i]))
-            y[..., t:t + cnt] = op.add(self.pend[..., r], a)
+                k = max(i - r0, 0)                              # tap i meets the samples r >= i of the block: a[k:] (slices, at 4096 taps)
+                a[..., k:] = op.add(a[..., k:], op.mul(self.h[..., i:i + 1], xb[..., r0 + k - i:r0 + cnt - i]))
+            y[..., t:t + cnt] = op.add(self.pend[..., r0:r0 + cnt], a)
             self.n += cnt
             t += cnt
             if self.n % B == 0:

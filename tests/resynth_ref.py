@@ -4,7 +4,7 @@ resynth::<I, O, _>(N, closure) (resynth.rs:216-372) in explicit f32 steps, vecto
 windows a hop H = N/4 apart, the project's restatement of microfft's rfft_N (pack z[m] = x[2m] + i x[2m+1], the N/2-point radix-2 complex
 FFT of cfft_inplace, the split), the stock processors, fix_negative, the inverse FFT (reverse elements 1 .. N-1, forward, / N), and the
 overlap-add in WINDOW order.  Every operation is one f32 rounding in the order the header states; `ftz=True` flushes every operand and result
-below 2^-126 to a zero of the same sign, as a build with f32 denormals flushed does.
+below 2^-126 to a zero of the same sign, as a build with f32 denormals flushed does; a result is judged on its exact value, before rounding.
 """
 import math
 
@@ -26,9 +26,22 @@ class _Ops:
             return x
         return np.where(np.abs(x) < _TINY, np.copysign(f32(0.0), x), x).astype(f32)
 
-    def add(self, a, b): return self.fl(self.fl(a) + self.fl(b))
-    def sub(self, a, b): return self.fl(self.fl(a) - self.fl(b))
-    def mul(self, a, b): return self.fl(self.fl(a) * self.fl(b))
+    def _res(self, a, b, fn):
+        """fn(a, b) of flushed operands, flushed as the hardware flushes a result: on its exact value, BEFORE rounding -- a sum or product
+        just below 2^-126 that IEEE rounds up to 2^-126 is a zero too.  (The exact value, where the f32 result is 2^-126: a product of two f32
+        is exact in f64, and so is a sum of this size unless its operands cancel, and then the f32 sum is exact itself.)"""
+        a, b = self.fl(a), self.fl(b)
+        r = self.fl(fn(a, b))
+        if self.ftz:
+            m = np.abs(r) == _TINY
+            if m.any():
+                a64, b64 = np.broadcast_to(a, r.shape)[m].astype(np.float64), np.broadcast_to(b, r.shape)[m].astype(np.float64)
+                r[m] = np.where(np.abs(fn(a64, b64)) < 2.0 ** -126, np.copysign(f32(0.0), r[m]), r[m])
+        return r
+
+    def add(self, a, b): return self._res(a, b, lambda x, y: x + y)
+    def sub(self, a, b): return self._res(a, b, lambda x, y: x - y)
+    def mul(self, a, b): return self._res(a, b, lambda x, y: x * y)
 
 
 def tables(N, cosf):
