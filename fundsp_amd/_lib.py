@@ -131,6 +131,7 @@ SYMBOLS = {
     "fdsp_bank_synchronize": (_i, [_P]),
     "fdsp_bank_last_kernel_ms": (_i, [_P, C.POINTER(C.c_float)]),
     "fdsp_bank_process_mix": (_i, [_P, _sz, _P, _P, _i, _i, _P]),
+    "fdsp_bank_process_mix_planar": (_i, [_P, _sz, _P, _sz, _P, _i, _i, _P]),
     "fdsp_bank_set_pan": (_i, [_P, _fp, _sz, _sz]),
     "fdsp_bank_mix_reserve": (_i, [_P, _sz]),
     "fdsp_mix_stereo": (_i, [_P, _P, _P, _sz, _sz, _P]),

@@ -547,14 +547,31 @@ class Bank:
                                       C.c_void_p(stream) if stream else None))
         return out
 
-    def process_mix(self, frames, inp=None, mix=MIX_SUM, out=None, mode=MODE_PROCESS, stream=None):
+    def process_mix(self, frames, inp=None, mix=MIX_SUM, out=None, mode=MODE_PROCESS, stream=None, layout=LAYOUT_VOICE_MINOR, frame_stride=None):
         """Render `frames` samples per voice and reduce them over the voices in the same launch (fdsp_bank_process_mix): the
         per-voice output never exists in HBM.  mix = MIX_SUM -> [outputs, frames]; MIX_PAN (mono graphs, positions from
-        set_pan) -> [2, frames].  inp: voice-minor [inputs, frames, V].  Same summation order as sum_voices / mix_stereo."""
+        set_pan) -> [2, frames].  inp: voice-minor [inputs, frames, V].  Same summation order as sum_voices / mix_stereo.
+        layout = LAYOUT_PLANAR (reverb / network banks, fdsp_bank_process_mix_planar): inp [V, inputs, frame_stride], the same mix bits."""
         import torch
 
         frames = int(frames)
         ni, nm = self.inputs(), (2 if mix == MIX_PAN else self.outputs())
+        if layout == LAYOUT_PLANAR:
+            fs = int(frame_stride) if frame_stride else max(frames, 1)
+            assert fs >= frames, f"frame_stride {fs} < frames {frames}"
+            if out is None:
+                out = torch.empty((nm, frames), dtype=torch.float32, device="cuda")
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nm * frames
+            d_in = None
+            if ni:
+                assert inp is not None and inp.is_cuda and inp.dtype == torch.float32 and inp.is_contiguous()
+                assert inp.numel() >= self.voices * ni * fs, f"inp has {inp.numel()} floats, the planar layout needs {self.voices * ni * fs}"
+                d_in = C.c_void_p(inp.data_ptr())
+            if stream is None:
+                stream = torch.cuda.current_stream().cuda_stream
+            check(lib().fdsp_bank_process_mix_planar(self._h, frames, d_in, fs, C.c_void_p(out.data_ptr()), int(mix), mode,
+                                                     C.c_void_p(stream) if stream else None))
+            return out
         if out is None:
             out = torch.empty((nm, frames), dtype=torch.float32, device="cuda")
         assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nm * frames
@@ -867,6 +884,52 @@ class Chain:
     def frame_stride(frames):
         """default row stride of a planar chain launch: `frames` rounded up to whole blocks"""
         return (int(frames) + 63) // 64 * 64
+
+    def _mid_for(self, frames, layout, frame_stride):
+        """the buffer between the halves for a launch of this shape (kept from launch to launch), and the planar row stride (0: voice-minor)"""
+        import torch
+
+        V, c = self.voices, self.source.outputs()
+        fs = (int(frame_stride) if frame_stride else self.frame_stride(frames)) if layout == LAYOUT_PLANAR else 0
+        mshape = (V, c, fs) if layout == LAYOUT_PLANAR else (c, int(frames), V)
+        if self._mid is None or tuple(self._mid.shape) != mshape:
+            self._mid = torch.empty(mshape, dtype=torch.float32, device="cuda")
+        return self._mid, fs
+
+    def process_mix(self, frames, inp=None, mix=MIX_SUM, out=None, mode=MODE_PROCESS, stream=None, layout=LAYOUT_VOICE_MINOR, frame_stride=None):
+        """As Bank.process_mix of the effect (a reverb / network bank): the source renders into the chain's mid buffer, in the layout of the
+        call, and the effect mixes it -- [outputs, frames], or [2, frames] with MIX_PAN; the instances' output never exists.  `inp` (a source
+        with inputs) has the layout of the call.  One stream, as in `process`."""
+        import torch
+
+        frames = int(frames)
+        mid, fs = self._mid_for(frames, layout, frame_stride)
+        own = None
+        if stream is None:
+            if self._stream is None:
+                self._stream = torch.cuda.Stream()
+            own, cur = self._stream, torch.cuda.current_stream()
+            own.wait_stream(cur)
+            stream = own.cuda_stream
+        self.source.process(frames, inp, mid, layout=layout, frame_stride=fs or None, mode=mode, stream=stream)
+        out = self.effect.process_mix(frames, mid, mix=mix, out=out, mode=mode, stream=stream, layout=layout, frame_stride=fs or None)
+        if own is not None:
+            cur.wait_stream(own)
+        return out
+
+    def set_pan(self, pan, first=0):
+        """Pan position per instance for MIX_PAN: the effect's (Bank.set_pan)"""
+        self.effect.set_pan(pan, first)
+
+    def mix_reserve(self, frames, layout=LAYOUT_VOICE_MINOR, frame_stride=None):
+        """Bank.mix_reserve of the effect, and the mid buffer of a launch of `frames` in `layout`: a reserved chain allocates nothing in
+        process_mix (a stream capture)."""
+        self.effect.mix_reserve(frames)
+        self._mid_for(frames, layout, frame_stride)
+        if self._stream is None:
+            import torch
+
+            self._stream = torch.cuda.Stream()
 
     def process(self, frames, inp=None, out=None, layout=LAYOUT_VOICE_MINOR, frame_stride=None, mode=MODE_PROCESS, stream=None):
         """As Bank.process: voice-minor out [outputs, frames, V] / planar out [V, outputs, frame_stride] (planar default stride: frames

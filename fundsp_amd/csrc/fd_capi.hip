@@ -33,6 +33,7 @@ namespace fd {
 // hosts drive banks from several threads.  The launch code never reads these: it reads the thread-local block below.
 std::atomic<int> g_pipe_split{1}, g_fdn_kernel{0}, g_time_split{1};
 std::atomic<int> g_math{FDSP_MATH_EXACT};  // default arithmetic of banks created from now on (fdsp_set_option("math", ..))
+std::atomic<int> g_fx_mix_chunk{0};       // effect banks' fused mix-down: frames per scratch chunk, 0 = from the byte budget (fd_fxbank.hip)
 std::atomic<int> g_timing{1};              // default of the per-launch HIP event pair (fdsp_bank_last_kernel_ms)
 std::atomic<long> g_zero_copy_max{1 << 18};  // floats; fdsp_bank_process_host reads/writes pinned host memory directly below this
 thread_local LaunchOpts tl_opts;           // fd_opts.hpp: what the launch code reads, resolved per bank by every render entry point
@@ -407,7 +408,7 @@ struct fdsp_bank {
     mutable bool async_param_pending = false;
     int math = FDSP_MATH_EXACT;  // FDSP_MATH_FAST: renders take the kind's tolerance-mode variant when it has one
     // per-bank launch options (fdsp_bank_set_option); -1 = follow the process-wide default at every launch
-    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1;
+    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1, opt_fx_mix_chunk = -1;
     size_t ring_frames = 0;      // as given at creation (fdsp_bank_clone)
     int last_kernel = 0;         // fd::LastKernel of the most recent render launch (fdsp_bank_get_option "last_kernel")
     bool ring_check_pending = false;  // a lifecycle launch may have changed a delay length: verify capacity before rendering
@@ -712,12 +713,15 @@ int fdsp_kind_by_name(const char* name) {
 namespace {
 // the launch options by name: range check shared by the process-wide and the per-bank setter
 // ... each entry names its process-wide default and its per-bank override itself: the setters and the getter index by the table
-struct OptSpec { const char* name; int lo, hi; const char* what; std::atomic<int>* global; int fdsp_bank::* field; };
+struct OptSpec { const char* name; int lo, hi; const char* what; std::atomic<int>* global; int fdsp_bank::* field; int step = 1; };
+bool opt_in_range(const OptSpec& o, int value) { return value >= o.lo && value <= o.hi && value % o.step == 0; }
 const OptSpec LAUNCH_OPTS[] = {
     {"pipe_split", 0, 4, "pipe_split takes 0 (off), 1 (auto), 2 or 3 (stages), 4 (loader only)", &fd::g_pipe_split, &fdsp_bank::opt_pipe_split},
     {"time_split", 0, 2, "time_split takes 0 (off), 1 (small banks of eligible graphs: 3 + 3 + 1 waves per group) or 2 (round 2's 2 + 2 + 1 / 2 + 1 + 1 layouts)", &fd::g_time_split, &fdsp_bank::opt_time_split},
     {"fdn_kernel", 0, 1, "fdn_kernel takes 0 (lane per frame) or 1 (lane per delay line)", &fd::g_fdn_kernel, &fdsp_bank::opt_fdn_kernel},
     {"timing", 0, 1, "timing takes 0 (no per-launch event pair) or 1 (fdsp_bank_last_kernel_ms available)", &fd::g_timing, &fdsp_bank::opt_timing},
+    {"fx_mix_chunk_frames", 0, 1 << 21, "fx_mix_chunk_frames takes 0 (automatic: from the scratch budget) or a multiple of 64 up to 2 097 152 (frames per chunk of an effect bank's mix scratch)",
+     &fd::g_fx_mix_chunk, &fdsp_bank::opt_fx_mix_chunk, 64},
 };
 const OptSpec* launch_opt(const char* name) {
     if (!name) return nullptr;
@@ -731,6 +735,7 @@ void resolve_opts(const fdsp_bank* b) {
     fd::tl_opts.pipe_split = b->opt_pipe_split >= 0 ? b->opt_pipe_split : fd::g_pipe_split.load(std::memory_order_relaxed);
     fd::tl_opts.time_split = b->opt_time_split >= 0 ? b->opt_time_split : fd::g_time_split.load(std::memory_order_relaxed);
     fd::tl_opts.fdn_kernel = b->opt_fdn_kernel >= 0 ? b->opt_fdn_kernel : fd::g_fdn_kernel.load(std::memory_order_relaxed);
+    fd::tl_opts.fx_mix_chunk_frames = b->opt_fx_mix_chunk >= 0 ? b->opt_fx_mix_chunk : fd::g_fx_mix_chunk.load(std::memory_order_relaxed);
     fd::tl_opts.last_kernel = fd::LK_NONE;
 }
 bool timing_on(const fdsp_bank* b) { return (b->opt_timing >= 0 ? b->opt_timing : fd::g_timing.load(std::memory_order_relaxed)) != 0; }
@@ -738,7 +743,7 @@ bool timing_on(const fdsp_bank* b) { return (b->opt_timing >= 0 ? b->opt_timing 
 
 int fdsp_set_option(const char* name, int value) {
     if (const OptSpec* o = launch_opt(name)) {
-        if (value < o->lo || value > o->hi) return fail(FDSP_EINVAL, o->what);
+        if (!opt_in_range(*o, value)) return fail(FDSP_EINVAL, o->what);
         o->global->store(value);
         return FDSP_OK;
     }
@@ -769,7 +774,7 @@ int fdsp_bank_set_option(fdsp_bank* b, const char* name, int value) {
         return FDSP_OK;
     }
     if (const OptSpec* o = launch_opt(name)) {  // -1 = back to the process-wide default
-        if (value != -1 && (value < o->lo || value > o->hi)) return fail(FDSP_EINVAL, std::string(o->what) + "; -1 = follow the process-wide default");
+        if (value != -1 && !opt_in_range(*o, value)) return fail(FDSP_EINVAL, std::string(o->what) + "; -1 = follow the process-wide default");
         b->*(o->field) = value;
         return FDSP_OK;
     }
@@ -780,7 +785,7 @@ int fdsp_bank_get_option(const fdsp_bank* b, const char* name) {
     if (name && std::strcmp(name, "math") == 0) return b->math;
     if (name && std::strcmp(name, "math_has_fast_variant") == 0) return (b->ops && b->ops->render_fast) ? 1 : 0;
     if (const OptSpec* o = launch_opt(name)) return b->*(o->field) >= 0 ? b->*(o->field) : o->global->load();
-    if (name && std::strcmp(name, "has_fused_mix") == 0) return (b->ops && b->ops->render_mix) ? 1 : 0;
+    if (name && std::strcmp(name, "has_fused_mix") == 0) return b->fx ? (b->fx->has_mix() ? 1 : 0) : ((b->ops && b->ops->render_mix) ? 1 : 0);
     if (name && std::strcmp(name, "last_kernel") == 0) return b->last_kernel;
     return fail(FDSP_EINVAL, "unknown bank option");
 }
@@ -1269,6 +1274,7 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     b->opt_time_split = src->opt_time_split;
     b->opt_fdn_kernel = src->opt_fdn_kernel;
     b->opt_timing = src->opt_timing;
+    b->opt_fx_mix_chunk = src->opt_fx_mix_chunk;
     e = sync_bank_stream(b);
     if (e != hipSuccess) return bail(e, "copy");
     *out = b;
@@ -1588,7 +1594,70 @@ int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
     DeviceGuard guard(b->device);
     const size_t nm = (size_t)(fdsp_bank_outputs(b) > 2 ? fdsp_bank_outputs(b) : 2);
     if (b->ops && b->ops->prepare_mix) b->ops->prepare_mix(b->math == FDSP_MATH_FAST && (bool)b->ops->render_mix_fast);  // run-time compiled graphs: build the mix kernels NOW
+    if (b->fx) {  // an effect bank: the partials of its groups and the chunked scratch its mix launches render into
+        if (!b->fx->has_mix()) return fail(FDSP_ENOTSUP, "this effect bank has no fused mix-down");
+        if (int rc = mix_reserve(b, ((b->V + 63) / 64) * nm * frames)) return rc;
+        resolve_opts(b);  // ("fx_mix_chunk_frames")
+        return b->fx->mix_reserve(frames);  // (the bank is idle: mix_reserve above waited)
+    }
     return mix_reserve(b, (b->stride / 64) * nm * frames);
+}
+
+namespace {
+// fdsp_bank_process_mix / _planar of an effect bank: the arguments are checked; render into the scratch, partials, tree
+int fx_process_mix(fdsp_bank* b, size_t frames, const float* d_in, size_t frame_stride, int layout, float* d_mix, int mix, int mode, void* stream) {
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s != b->stream) hipStreamIsCapturing(s, &cap);
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const size_t nm = (size_t)mix_channels(b, mix), groups = (b->V + 63) / 64, R = nm * frames;
+    resolve_opts(b);
+    if (groups * R > b->mix_part_n || !b->fx->mix_reserved(frames) || (mix == FDSP_MIX_PAN && !b->panw)) {
+        if (capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_mix during a stream capture: call fdsp_bank_mix_reserve (and fdsp_bank_set_pan) before capturing");
+        if (int rc = mix_reserve(b, groups * R)) return rc;
+        if (!b->fx->mix_reserved(frames)) {
+            HIPCHK(sync_bank_stream(b));
+            if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));  // a mix launch on a caller's stream may still use the old scratch
+            if (int rc = b->fx->mix_reserve(frames)) return rc;
+        }
+        if (mix == FDSP_MIX_PAN) if (int rc = ensure_panw(b)) return rc;
+    }
+    if (int rc = order_after_bank_stream(b, s)) return rc;
+    if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
+    const bool timing = timing_on(b);
+    if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
+    resolve_opts(b);
+    b->fx->render_mix(d_in, b->mix_part, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, mix == FDSP_MIX_PAN ? b->panw : nullptr, b->stride, s);
+    b->last_kernel = fd::tl_opts.last_kernel;
+    launch_mix_tree(b->mix_part, d_mix, R, groups, s);
+    HIPCHK(hipGetLastError());
+    if (!capturing) {
+        if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
+        b->timed = timing;
+        b->ext_pending = s != b->stream;
+    }
+    return FDSP_OK;
+}
+// the argument checks the two mix entry points share
+int check_mix_args(const fdsp_bank* b, const float* d_in, const float* d_mix, int mix, int mode) {
+    if (!d_mix) return fail(FDSP_EINVAL, "d_mix is NULL");
+    if (fdsp_bank_inputs(b) > 0 && !d_in) return fail(FDSP_EINVAL, "d_in is NULL but the graph has inputs");
+    if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
+    if (mix != FDSP_MIX_SUM && mix != FDSP_MIX_PAN) return fail(FDSP_EINVAL, "mix takes FDSP_MIX_SUM or FDSP_MIX_PAN");
+    if (mix == FDSP_MIX_PAN && fdsp_bank_outputs(b) != 1) return fail(FDSP_EINVAL, "FDSP_MIX_PAN pans a mono graph; this one has " + std::to_string(fdsp_bank_outputs(b)) + " outputs (use FDSP_MIX_SUM)");
+    return FDSP_OK;
+}
+}  // namespace
+
+int fdsp_bank_process_mix_planar(fdsp_bank* b, size_t frames, const float* d_in, size_t frame_stride, float* d_mix, int mix, int mode, void* stream) {
+    if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (int rc = render_only(b)) return rc;
+    if (!b->fx) return fail(FDSP_ENOTSUP, "fdsp_bank_process_mix_planar is for effect banks (planar is their kernels' layout): a voice bank mixes voice-minor inputs with fdsp_bank_process_mix");
+    DeviceGuard guard(b->device);
+    if (frames == 0) return FDSP_OK;
+    if (int rc = check_mix_args(b, d_in, d_mix, mix, mode)) return rc;
+    if (frame_stride < frames) return fail(FDSP_EINVAL, "frame_stride < frames");
+    return fx_process_mix(b, frames, d_in, frame_stride, FDSP_LAYOUT_PLANAR, d_mix, mix, mode, stream);
 }
 
 int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float* d_mix, int mix, int mode, void* stream) {
@@ -1596,12 +1665,8 @@ int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float*
     if (int rc = render_only(b)) return rc;
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
-    if (!d_mix) return fail(FDSP_EINVAL, "d_mix is NULL");
-    if (fdsp_bank_inputs(b) > 0 && !d_in) return fail(FDSP_EINVAL, "d_in is NULL but the graph has inputs");
-    if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
-    if (mix != FDSP_MIX_SUM && mix != FDSP_MIX_PAN) return fail(FDSP_EINVAL, "mix takes FDSP_MIX_SUM or FDSP_MIX_PAN");
-    if (mix == FDSP_MIX_PAN && fdsp_bank_outputs(b) != 1) return fail(FDSP_EINVAL, "FDSP_MIX_PAN pans a mono graph; this one has " + std::to_string(fdsp_bank_outputs(b)) + " outputs (use FDSP_MIX_SUM)");
-    if (b->fx) return fail(FDSP_ENOTSUP, "reverb_stereo banks have no fused mix-down: render the instances and call fdsp_sum_voices");
+    if (int rc = check_mix_args(b, d_in, d_mix, mix, mode)) return rc;
+    if (b->fx) return fx_process_mix(b, frames, d_in, 0, FDSP_LAYOUT_VOICE_MINOR, d_mix, mix, mode, stream);
     const bool fast = b->math == FDSP_MATH_FAST && b->ops->render_mix_fast;
     const auto& launch = fast ? b->ops->render_mix_fast : b->ops->render_mix;
     if (!launch) return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' was built without a fused mix-down kernel: render voice-out and call fdsp_sum_voices / fdsp_mix_stereo");

@@ -1,5 +1,5 @@
 // fd_fxbank.hip -- the effect banks of fd_fxbank.hpp: buffers, configuration, clone and launch of each family (host code; the kernels are in
-// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_resynth.hip and fd_convolve.hip).
+// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_resynth.hip and fd_convolve.hip; those of the networks' fused mix-down in fd_fxmix.hip).
 #include <vector>
 
 #include "fd_fxbank.hpp"
@@ -54,7 +54,10 @@ void carry_and_free(const Bufs& to, const Bufs& from, size_t first, hipStream_t 
 // ---- the lane-per-frame networks: rate, bus and the planar staging copy of voice-minor launches ------------------------------------------------
 class NetFx : public FxBank {
   public:
-    ~NetFx() override { free_stage(); }
+    ~NetFx() override {
+        free_stage();
+        if (mixs_) hipFree(mixs_);
+    }
     int inputs() const override { return nin_; }
     int outputs() const override { return nout_; }
     FdnBus* bus() override { return &bus_; }
@@ -100,7 +103,52 @@ class NetFx : public FxBank {
     }
     int create(double sr, hipStream_t s) { sr0_ = sr; return configure(sr, s); }   // the first configuration
 
+    // ---- the fused mix-down: planar render into the mix scratch, chunk by chunk, then the groups' partials (fd_fxmix.hip) ----
+    // The scratch holds one chunk: [V][inputs][L] (the planar copy of the chunk's input) | [V][outputs][L].  A chunk is a multiple of 64
+    // frames, so the kernels see whole blocks but for the launch's ragged end, as in any split of a launch -- and these banks render
+    // chunked == whole.  Every chunk writes its own columns of the full-length partial buffer.
+    bool has_mix() const override { return true; }
+    bool mix_reserved(size_t T) const override { return mix_need(T) <= mixs_n_; }
+    int mix_reserve(size_t T) override {
+        const size_t need = mix_need(T);
+        if (need <= mixs_n_) return FDSP_OK;
+        float* p = nullptr;
+        if (hipError_t e = hipMalloc((void**)&p, need * sizeof(float))) return hip_fail(e, std::string("fdsp_bank_mix_reserve: ") + what_ + " mix scratch");
+        if (mixs_) hipFree(mixs_);   // (hipFree waits for launches that still use the old buffer)
+        mixs_ = p;
+        mixs_n_ = need;
+        return FDSP_OK;
+    }
+    void render_mix(const float* in, float* part, size_t T, size_t fstride, int layout, int tick, const float* panw, size_t pstride, hipStream_t s) override {
+        const size_t L = mix_chunk(T);
+        // a planar launch that fits the scratch with the caller's own row stride: the input is read in place
+        if (layout == FDSP_LAYOUT_PLANAR && T <= L && (size_t)nout_ * fstride <= (size_t)(nin_ + nout_) * L) {
+            launch(in, mixs_, T, fstride, FDSP_LAYOUT_PLANAR, tick, s);
+            fx_launch_mix_groups(mixs_, V_, nout_, fstride, T, part, T, 0, panw, pstride, s);
+            return;
+        }
+        float *pin = mixs_, *pout = mixs_ + V_ * (size_t)nin_ * L;
+        for (size_t t0 = 0; t0 < T; t0 += L) {
+            const size_t n = T - t0 < L ? T - t0 : L;
+            if (layout == FDSP_LAYOUT_VOICE_MINOR) fx_launch_stage_in(in, pin, V_, T, nin_, t0, n, L, s);
+            else fx_launch_copy_rows(in + t0, fstride, pin, L, V_ * (size_t)nin_, n, s);   // (one stride per launch: the chunk's rows move over)
+            launch(pin, pout, n, L, FDSP_LAYOUT_PLANAR, tick, s);
+            fx_launch_mix_groups(pout, V_, nout_, L, n, part, T, t0, panw, pstride, s);
+        }
+    }
+
   protected:
+    // frames per chunk of a launch of T frames: the option, else what the byte budget holds; never more than the launch in whole blocks
+    size_t mix_chunk(size_t T) const {
+        size_t L = (size_t)tl_opts.fx_mix_chunk_frames;
+        if (L == 0) L = MIX_SCRATCH_BYTES / (V_ * (size_t)(nin_ + nout_) * sizeof(float)) / 64 * 64;
+        L = L < 64 ? 64 : (L > MIX_CHUNK_MAX ? MIX_CHUNK_MAX : L);
+        const size_t whole = (T + 63) / 64 * 64;
+        return whole < L ? whole : L;
+    }
+    size_t mix_need(size_t T) const { return V_ * (size_t)(nin_ + nout_) * mix_chunk(T); }
+    static constexpr size_t MIX_SCRATCH_BYTES = (size_t)256 << 20;   // the automatic chunk's budget: the fastest of 16 / 64 / 256 MiB
+    static constexpr size_t MIX_CHUNK_MAX = (size_t)1 << 21;        // frames: the grids of the transpose-in and the partial kernel
     NetFx(size_t V, const char* what) : V_(V), what_(what) {}
     // (re)allocate the lines for a sample rate.  Transactional: the constants are validated and the new buffers allocated BEFORE anything of
     // the instance changes; on any failure it keeps its old constants, buffers and rate
@@ -118,6 +166,8 @@ class NetFx : public FxBank {
     const char* what_;
     float* stage_ = nullptr;   // planar staging of voice-minor launches: [V][inputs][frames] | [V][outputs][frames] (fd_fdn.hip "voice-minor I/O")
     size_t stage_n_ = 0;
+    float* mixs_ = nullptr;    // the mix scratch: apart from stage_, allocated by mix_reserve alone, never shrunk, not cloned
+    size_t mixs_n_ = 0;
 };
 
 // reverb_stereo, reverb4_stereo and the generic network (fd_fdn.hpp): one kernel family, three ways to make its constants

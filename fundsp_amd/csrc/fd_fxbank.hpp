@@ -30,7 +30,22 @@ struct FxBank {
     // a new instance that continues exactly where this one stands (state copied on `stream`, bus included)
     virtual int clone(hipStream_t stream, std::unique_ptr<FxBank>* out) = 0;
     virtual void render(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, bool capturing, hipStream_t stream) = 0;
+    // The fused mix-down (fdsp_bank_process_mix): the family renders into a scratch of its own, chunk by chunk, and leaves the groups'
+    // partial mixes in part[groups][mix channels][T] (panw = [2][pstride] weights: FDSP_MIX_PAN, one output; else NULL); the caller runs the
+    // tree.  The default is a family without one (the resynthesizer, the convolver).  The scratch is sized by mix_reserve only -- never by
+    // render_mix, which a capture may record -- and lives until the bank goes; mix_reserved tells whether a launch of T frames fits.
+    virtual bool has_mix() const { return false; }
+    virtual bool mix_reserved(size_t) const { return false; }
+    virtual int mix_reserve(size_t) { return api_fail(FDSP_ENOTSUP, "this effect bank has no fused mix-down"); }
+    virtual void render_mix(const float*, float*, size_t, size_t, int, int, const float*, size_t, hipStream_t) {}
 };
+
+// fd_fxmix.hip: planar [V][C][xstride], frames 0 .. n-1 -> columns t0 .. t0+n-1 of the groups' partial mixes part[groups][C or 2][T]
+void fx_launch_mix_groups(const float* x, size_t V, int C, size_t xstride, size_t n, float* part, size_t T, size_t t0, const float* panw,
+                          size_t pstride, hipStream_t stream);
+// frames t0 .. t0+n-1 of voice-minor [channels][T][V] -> planar [V][channels][dstride], frames 0 .. n-1
+void fx_launch_stage_in(const float* src, float* dst, size_t V, size_t T, int channels, size_t t0, size_t n, size_t dstride, hipStream_t stream);
+void fx_launch_copy_rows(const float* src, size_t sstride, float* dst, size_t dstride, size_t rows, size_t n, hipStream_t stream);
 
 // The factories build and initialise an instance on `stream`.  The arguments are checked by the caller; what can still fail is the
 // kernels' delay rule at the creation rate (44.1 kHz but for fx_fdn_network) and the allocation.

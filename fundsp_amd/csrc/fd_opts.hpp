@@ -11,6 +11,7 @@ struct LaunchOpts {
     int pipe_split = 1;  // 0 = single-wave kernel, 1 = best plan (default), 2 / 3 = exactly that many compute stages, 4 = loader wave only
     int time_split = 1;  // 1 (default) = small banks of eligible graphs take the time-split kernel (3 + 3 + 1 waves), 2 = round 2's layouts, 0 = never
     int fdn_kernel = 0;  // reverb banks: 0 = lane-per-frame (default), 1 = lane-per-delay-line
+    int fx_mix_chunk_frames = 0;  // effect banks' fused mix-down: frames per chunk of the mix scratch, a multiple of 64; 0 (default) = from the byte budget
     // OUT: which kernel family the launch code chose (fdsp_bank_get_option(bank, "last_kernel")) -- lets a test assert that
     // the path it means to exercise is the one that ran, since every path produces the same samples
     int last_kernel = 0;

@@ -128,7 +128,10 @@ int fdsp_bank_get_option(const fdsp_bank* bank, const char* name);
  * fdsp_bank_get_option(bank, "last_kernel") (read-only): the kernel family the most recent render launch took --
  * 1 single-wave, 2 pipeline, 3 planar pipeline, 4 time-split, 5 voice scheduler, 6 / 7 reverb lane-per-frame / -line,
  * 8 the chain of waves that renders a wide sum of generators (sumi / busi of >= 8 oscillators) on a small bank. */
-/* fdsp_bank_get_option(bank, "has_fused_mix") (read-only): 1 if fdsp_bank_process_mix has kernels for the bank's kind. */
+/* fdsp_bank_get_option(bank, "has_fused_mix") (read-only): 1 if fdsp_bank_process_mix has kernels for the bank's kind (voice banks), or
+ * the bank is a reverb / network bank (their mix-down renders into a scratch: "the stereo mix-down" below); 0 for resynthesizer and convolver banks. */
+/* "fx_mix_chunk_frames" (default 0 = automatic, from a 256 MiB budget): frames per chunk of the mix scratch of a reverb / network bank, a
+ * multiple of 64 (FDSP_EINVAL otherwise).  The chunking changes no bit of the mix. */
 /* "host_zero_copy_max" (default 262144): fdsp_bank_process_host calls moving at most this many floats per direction
  * let the kernel read/write pinned host memory directly instead of staging through HBM (lower per-block latency). */
 /* "fdn_kernel" (default 0): reverb banks render with one lane per FRAME (0) or one lane per DELAY LINE (1); identical
@@ -530,7 +533,19 @@ double fdsp_bank_events_time(const fdsp_bank* bank);       /* Sequencer::time() 
  * voice-out and call the functions below, which use the same order. */
 #define FDSP_MIX_SUM 1
 #define FDSP_MIX_PAN 2
+/* EFFECT BANKS.  The lane-per-frame families -- reverb_stereo, reverb4_stereo, fdsp_fdn_create, reverb3_stereo, fdsp_fdn_network_create --
+ * mix as well (resynthesizer and convolver banks answer FDSP_ENOTSUP).  One wave of their kernels owns one instance, so the reduction is a
+ * launch of its own: the instances render PLANAR into a scratch the bank owns, chunk by chunk (whole 64-frame blocks, "fx_mix_chunk_frames"),
+ * a kernel adds every group of 64 instances into the partial-mix buffer in the order above, and the tree runs once at the end; no output
+ * transpose and no full-length output exist.  The bus (fdsp_bank_set_bus) is part of the render, so the mix is the mix of the bussed output.
+ * fdsp_bank_process_mix takes d_in voice-minor [inputs][frames][instances]; fdsp_bank_process_mix_planar takes it planar
+ * [instances][inputs][frame_stride] -- these kernels' native layout; a launch that fits one chunk reads it in place -- and gives the same
+ * bits; voice banks answer FDSP_ENOTSUP to it.  FDSP_MIX_PAN pans one-output banks (fdsp_bank_set_pan).
+ * The scratch follows the partial-mix buffer's rule: fdsp_bank_mix_reserve(bank, frames) sizes both for launches of up to `frames`; an
+ * uncaptured launch that needs more grows them; a captured one is refused (FDSP_EINVAL, reserve first).  The scratch is never shrunk, lives
+ * until the bank is destroyed, is apart from the staging copy of fdsp_bank_process, and a clone starts without one. */
 int fdsp_bank_process_mix(fdsp_bank* bank, size_t frames, const float* d_in, float* d_mix, int mix, int mode, void* stream);
+int fdsp_bank_process_mix_planar(fdsp_bank* bank, size_t frames, const float* d_in, size_t frame_stride, float* d_mix, int mix, int mode, void* stream);
 int fdsp_bank_set_pan(fdsp_bank* bank, const float* h_pan, size_t first, size_t count);
 int fdsp_bank_mix_reserve(fdsp_bank* bank, size_t frames);
 

@@ -687,6 +687,11 @@ class Bank {
     void process_mix(size_t frames, const float* d_in, float* d_mix, int mix = FDSP_MIX_SUM, int mode = FDSP_MODE_PROCESS, void* stream = nullptr) {
         check(fdsp_bank_process_mix(h_, frames, d_in, d_mix, mix, mode, stream));
     }
+    // the same for the effect banks (reverbs, networks) with a PLANAR input [instances][inputs][frame_stride], their kernels' native layout
+    void process_mix_planar(size_t frames, const float* d_in, size_t frame_stride, float* d_mix, int mix = FDSP_MIX_SUM, int mode = FDSP_MODE_PROCESS,
+                            void* stream = nullptr) {
+        check(fdsp_bank_process_mix_planar(h_, frames, d_in, frame_stride, d_mix, mix, mode, stream));
+    }
     void set_pan(const std::vector<float>& per_voice, size_t first = 0) { check(fdsp_bank_set_pan(h_, per_voice.data(), first, per_voice.size())); }
     void mix_reserve(size_t frames) { check(fdsp_bank_mix_reserve(h_, frames)); }  // AudioNode::allocate for the mix path
     void synchronize() { check(fdsp_bank_synchronize(h_)); }

@@ -149,6 +149,8 @@ pub mod ffi {
                                  frame_stride: usize, mode: c_int, stream: *mut c_void) -> c_int; // device-resident I/O
         pub fn fdsp_bank_process_mix(bank: *mut FdspBank, frames: usize, d_in: *const f32, d_mix: *mut f32, mix: c_int, mode: c_int,
                                      stream: *mut c_void) -> c_int; // render + reduce over the voices in one launch
+        pub fn fdsp_bank_process_mix_planar(bank: *mut FdspBank, frames: usize, d_in: *const f32, frame_stride: usize, d_mix: *mut f32, mix: c_int,
+                                            mode: c_int, stream: *mut c_void) -> c_int; // effect banks: the same from a planar input
         pub fn fdsp_bank_process_events_mix(bank: *mut FdspBank, frames: usize, d_in: *const f32, d_mix: *mut f32, mode: c_int, stream: *mut c_void) -> c_int; // Sequencer output
         pub fn fdsp_bank_set_pan(bank: *mut FdspBank, pan: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_mix_reserve(bank: *mut FdspBank, frames: usize) -> c_int; // AudioNode::allocate for the mix path
@@ -538,6 +540,18 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
             return Err(format!("render_mix: buffers of {} / {} floats, the launch needs {} / {}", input.len, mix.len, i * frames * self.voices, nm * frames));
         }
         check(unsafe { fdsp_bank_process_mix(self.bank, frames, input.ptr, mix.ptr, if pan { FDSP_MIX_PAN } else { FDSP_MIX_SUM }, FDSP_MODE_PROCESS, stream) })
+    }
+
+    /// [`Self::render_mix`] of an effect bank (reverbs, networks) from a PLANAR input `[instances][inputs][frame_stride]`, the layout
+    /// their kernels read (`fdsp_bank_process_mix_planar`); the same mix bits as the voice-minor call.  Voice banks answer an error.
+    pub fn render_mix_planar(&mut self, frames: usize, input: DevicePtr<'_>, frame_stride: usize, mix: DevicePtrMut<'_>, pan: bool,
+                             stream: *mut c_void) -> Result<(), String> {
+        let (i, o) = unsafe { (fdsp_bank_inputs(self.bank) as usize, fdsp_bank_outputs(self.bank) as usize) };
+        let nm = if pan { 2 } else { o };
+        if frame_stride < frames || input.len < self.voices * i * frame_stride || mix.len < nm * frames {
+            return Err(format!("render_mix_planar: buffers of {} / {} floats, the launch needs {} / {}", input.len, mix.len, self.voices * i * frame_stride, nm * frames));
+        }
+        check(unsafe { fdsp_bank_process_mix_planar(self.bank, frames, input.ptr, frame_stride, mix.ptr, if pan { FDSP_MIX_PAN } else { FDSP_MIX_SUM }, FDSP_MODE_PROCESS, stream) })
     }
 
     /// Pan position (-1 .. 1) per voice for `render_mix(.., pan = true, ..)`; every voice starts in the centre (`pan(0.0)`).
