@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "fd_fdn.hpp"
+#include "fd_fdn_frames.hpp"
 #include "fd_opts.hpp"
 #include "fd_math.hpp"
 
@@ -131,15 +132,18 @@ void fdn_make_const_generic(const FdnDesc& d, double sample_rate, FdnConst* c) {
 
 constexpr int TS = 65;  // LDS row stride (floats): lane-per-row access is bank-conflict free
 
-__global__ __launch_bounds__(256) void k_fdn_reset(FdnConst c, FdnState s, size_t instances) {
-    // zero the rings and the per-line state (Feedback::reset feedback.rs:123-126 -> Delay::reset, Fir::reset)
-    const size_t total = instances * c.ring_stride;
+__global__ __launch_bounds__(256) void k_fdn_reset(FdnState s, float* s1, float* s2, size_t ring_stride, size_t instances) {
+    // zero the rings and the per-line state (Feedback(2)::reset feedback.rs:123-126, 248-252 -> Delay::reset, Fir::reset), and the line
+    // filters' state where the network has filters (s1, s2: the filtered networks of fd_fdnx.hpp)
+    const size_t total = instances * ring_stride;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) s.rings[i] = 0.0f;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < instances * 32; i += (size_t)gridDim.x * 256) {
         if (i < instances) s.wpos[i] = 0;
         s.v1[i] = 0.0f;
         s.v2[i] = 0.0f;
         s.fb[i] = 0.0f;
+        if (s1) s1[i] = 0.0f;
+        if (s2) s2[i] = 0.0f;
     }
 }
 
@@ -164,12 +168,6 @@ __device__ __forceinline__ float xor_lane(float v, bool upper16) {
         r = upper16 ? (int)sw[0] : (int)sw[1];
     }
     return __builtin_bit_cast(float, r);
-}
-
-__device__ __forceinline__ void fdn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // layout 0: voice-minor [ch][frame][instance]; layout 1: planar [instance][ch][fstride]
@@ -246,7 +244,6 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
         // ---- phase 2: 64 samples of the recirculating network, one lane per delay line.  Ring reads and inputs of 8
         // frames are fetched from LDS ahead of the serial recurrence (they do not depend on it); the only cross-lane
         // traffic on the per-sample critical path is the 5-stage Hadamard.
-#ifndef FD_FDN_SKIP_P2
         if (line) {
             const float* trow = tile + lane * TS;
             const float* irow = tin + (j * 2 + (k & 1)) * 64;  // MultiSplit<U2,U16>: channel i takes input i % 2 (audionode.rs:600)
@@ -288,7 +285,6 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
                 }
             }
         }
-#endif
         fdn_wave_sync();
         // ---- phase 3: write the 64 new ring samples per line back (coalesced), ordered pan sum with lane = frame
         for (int r0 = 0; r0 < R; r0 += 32) {
@@ -301,13 +297,11 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
                 const size_t ri = inst0 + (r0 >> 5);
                 const int w0 = __builtin_amdgcn_readlane(wp, r);
                 const int pos = (w0 + lane) & cmask;
-#ifndef FD_FDN_SKIP_STORE
                 if (ri < V && lane < size) {
                     float* ring = s.rings + ri * c.ring_stride + (size_t)kk * cp;
                     ring[pos] = xw[u];
                     if (pos < 64) ring[c.cap + pos] = xw[u];  // the mirror of the first 64 slots
                 }
-#endif
             }
         }
 #pragma unroll
@@ -357,7 +351,12 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
 // (no LDS transposes), the pan sum is a register fold, and the one-frame shifts go through two small LDS rows per line.
 // ~610 VALU + ~160 LDS instructions per instance-block instead of ~1660 + ~350; no LDS-bound occupancy limit.
 // (non-temporal ring loads / stores measured 10.2 ms vs 6.4-6.9 ms: the L2 write-combining matters)
-constexpr int HS = 68;  // floats per history row: [0..1] carry-in, [2..65] this block (also used with offset 1 for fb)
+// the lines' parameters of these kernels: uniform over the bank, kernel arguments (SGPRs)
+struct FdnUniformLines {
+    const FdnConst& c;
+    __device__ __forceinline__ int len(int k) const { return c.len[k]; }
+    __device__ __forceinline__ float w(int j, int) const { return c.w[j]; }
+};
 
 // CAP_LOG2: the ring capacity C = 1 << CAP_LOG2 is a compile-time constant here, so the 32 ring bases inside an instance
 // are immediates and a block's ring addresses come out of a handful of scalar instructions:
@@ -373,7 +372,7 @@ constexpr int HS = 68;  // floats per history row: [0..1] carry-in, [2..65] this
 template <int CAP_LOG2, int NSEC>
 __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState s, size_t V, const float* __restrict__ in,
                                                            float* __restrict__ out, size_t T, size_t fstride, int layout, int tick_mode, FdnBus bus) {
-    constexpr int C = 1 << CAP_LOG2, CMASK = C - 1, CP = C + 64;
+    constexpr int C = 1 << CAP_LOG2, CMASK = C - 1;
     constexpr int NL = 32 / NSEC;  // lines per network
     __shared__ float hist_all[4][32 * HS];  // per line: delay outputs d[n-2], d[n-1] | d[0..63]
     __shared__ float fbr_all[4][32 * HS];   // per line: fb[-1] | fb[0..63]
@@ -388,29 +387,17 @@ __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState 
     float* fbr = fbr_all[wib];
     const size_t inst = (size_t)blockIdx.x * 4 + wib;
     if (inst >= V) return;
-    const float w0 = c.w[0], w1 = c.w[1], w2 = c.w[2];
-    const float scale = c.had_scale;  // (1.0 / sqrt(N as f64)) as f32  feedback.rs:57
-    // The instance's rings as a buffer resource: buffer_load / buffer_store take a VGPR offset (lane * 4, the same for
-    // every access), an SGPR offset (the line's base + the block's slot, scalar arithmetic) and no 64-bit VALU address math.
-    const __amdgpu_buffer_rsrc_t rings = __builtin_amdgcn_make_buffer_rsrc(s.rings + inst * c.ring_stride, 0, (int)(c.ring_stride * sizeof(float)), 0x00020000);
+    const FdnUniformLines p{c};
+    const FdnOut io{out, V, T, fstride, inst, layout, lane};
+    const __amdgpu_buffer_rsrc_t rings = fdn_rings(s, inst, c.ring_stride);
     const int lane4 = lane * 4;
     int wp = __builtin_amdgcn_readfirstlane(s.wpos[inst]);  // write position of the block's first frame: wave-uniform
-    if (lane < 32) {  // carry-in: Fir::v[1], v[2] and Feedback::value of every line
-        hist[lane * HS + 0] = s.v1[inst * 32 + lane];
-        hist[lane * HS + 1] = s.v2[inst * 32 + lane];
-        fbr[lane * HS + 0] = s.fb[inst * 32 + lane];
-    }
+    if (lane < 32) fdn_state_load<3>(s, inst, lane, hist, fbr);
     float dn[32], xin[2];  // prefetched ring reads / inputs of the NEXT block (lane = frame)
     auto fetch = [&](size_t t0n, int wpn) {
-        const int sizen = (int)((T - t0n) < 64 ? (T - t0n) : 64);
-        // frame 0 of the block reads the slot written len - 1 frames ago; the 64 slots from there on are contiguous (mirror
-        // zone), in bounds for every lane, and lanes past a ragged end read values nobody uses
-#pragma unroll
-        for (int k = 0; k < 32; k++) {
-            const int r = (wpn - (c.len[k] - 1)) & CMASK;
-            dn[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rings, lane4, (k * CP + r) * 4, 0));
-        }
-        if (sizen == 64) {
+        fdn_ring_fetch(dn, rings, lane4, C, wpn, p);
+        const int sizen = fdn_block_size(T, t0n);
+        if (sizen == 64) {  // (always two channels, and a full block loads them from a scalar base: not fdn_input_fetch)
 #pragma unroll
             for (int ch = 0; ch < 2; ch++)
                 xin[ch] = layout == 0 ? in[((size_t)ch * T + t0n + lane) * V + inst] : (in + (inst * 2 + ch) * fstride + t0n)[lane];
@@ -422,74 +409,26 @@ __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState 
     };
     fetch(0, wp);
     for (size_t t0 = 0; t0 < T; t0 += 64) {
-        const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
+        const int size = fdn_block_size(T, t0);
         float d[32], xi0 = xin[0], xi1 = xin[1];
 #pragma unroll
         for (int k = 0; k < 32; k++) d[k] = dn[k];
         if (t0 + 64 < T) fetch(t0 + 64, (wp + 64) & CMASK);  // loads of the next block fly during this block's arithmetic
-        // delay outputs -> history rows (lane n writes slot n + 2), then the FIR reads slots n, n + 1 (fir.rs:57-70)
-#pragma unroll
-        for (int k = 0; k < 32; k++) hist[k * HS + 2 + lane] = d[k];
-        fdn_wave_sync();
         float o[32], h[32];
+        fdn_fir_lines<32, 3>(o, d, hist, lane, p);
 #pragma unroll
-        for (int k = 0; k < 32; k++) {
-            const float v0 = hist[k * HS + lane], v1 = hist[k * HS + lane + 1];
-            float acc = 0.0f;
-            acc += w0 * v0;
-            acc += w1 * v1;
-            acc += w2 * d[k];
-            o[k] = acc;
-            h[k] = acc;
-        }
-        // FrameHadamard feedback.rs:35-57: in-place butterflies h = 1, 2, 4, 8 (, 16); (x, y) -> (x + y, x - y), within each network
-#pragma unroll
-        for (int st = 1; st < NL; st <<= 1)
-#pragma unroll
-            for (int i = 0; i < 32; i++)
-                if ((i & st) == 0) {
-                    const float x = h[i], y = h[i + st];
-                    h[i] = x + y;
-                    h[i + st] = x - y;
-                }
-        // feedback of frame n -> row slot n + 1; the ring write of frame n needs slot n (Feedback::tick: input + value)
-#pragma unroll
-        for (int k = 0; k < 32; k++) fbr[k * HS + 1 + lane] = h[k] * scale;
-        fdn_wave_sync();
-        float xw[32];  // MultiSplit<U2, N/2>: line k takes input channel k % 2 (audionode.rs:600); Feedback::tick: input + value
-#pragma unroll
-        for (int k = 0; k < NL; k++) xw[k] = ((k & 1) ? xi1 : xi0) + fbr[k * HS + lane];
+        for (int k = 0; k < 32; k++) h[k] = o[k];
+        fdn_hadamard<NL>(h);  // within each network
+        fdn_feedback_put(h, c.had_scale, fbr, lane);
+        float xw[32];
+        fdn_ring_input<0, NL>(xw, fbr, lane, xi0, xi1);
         if constexpr (NSEC == 2) {
-            // MultiJoin<U2, U8> of the first network's 16 outputs -> 2 channels -> MultiSplit<U2, U8> into the second network.
-            // process(): every term scaled by z = 1/8, then added (audionode.rs:706-720); tick(): the sum, divided by 8 (:697-705)
+            // MultiJoin<U2, U8> of the first network's 16 outputs -> 2 channels -> MultiSplit<U2, U8> into the second network
             float j0, j1;
-            if (tick_mode) {
-                j0 = o[0]; j1 = o[1];
-#pragma unroll
-                for (int i = 1; i < 8; i++) { j0 += o[2 * i]; j1 += o[2 * i + 1]; }
-                j0 = j0 / 8.0f; j1 = j1 / 8.0f;
-            } else {
-                const float z = 1.0f / 8.0f;
-                j0 = o[0] * z; j1 = o[1] * z;
-#pragma unroll
-                for (int i = 1; i < 8; i++) { j0 += o[2 * i] * z; j1 += o[2 * i + 1] * z; }
-            }
-#pragma unroll
-            for (int k = NL; k < 32; k++) xw[k] = ((k & 1) ? j1 : j0) + fbr[k * HS + lane];
+            fdn_join<16>(o, 2, tick_mode, j0, j1);
+            fdn_ring_input<NL, 32>(xw, fbr, lane, j0, j1);
         }
-        if (size == 64 && wp >= 64 && wp + 64 <= C) {  // the common block: one scalar offset per line
-#pragma unroll
-            for (int k = 0; k < 32; k++)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, lane4, (k * CP + wp) * 4, 0);
-        } else if (lane < size) {  // wrap, mirror zone or ragged tail: per-lane slots, Delay::tick slot by slot
-            const int pos = (wp + lane) & CMASK;
-#pragma unroll
-            for (int k = 0; k < 32; k++) {
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, pos * 4, k * CP * 4, 0);
-                if (pos < 64)  // keep the mirror of the first 64 slots
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, (C + pos) * 4, k * CP * 4, 0);
-            }
-        }
+        fdn_ring_store(xw, rings, lane, lane4, C, wp, size);
         float l = 0.0f, rr = 0.0f;  // Reduce::tick left fold (audionode.rs:2427-2439) of the Panner outputs of the LAST network's lines
 #pragma unroll
         for (int k = 32 - NL; k < 32; k++) {
@@ -499,38 +438,13 @@ __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState 
         }
         l *= c.out_scale;  // * dc((1/16, 1/16)) | * dc((1/4, 1/4))
         rr *= c.out_scale;
-        if (bus.mode) {  // wet * reverb [& dry * multipass()] (fd_fdn.hpp FdnBus)
-            l = fdn_bus(bus, l, xi0);
-            rr = fdn_bus(bus, rr, xi1);
-        }
-        if (lane < size) {
-            if (layout == 0) {
-                out[((size_t)0 * T + t0 + lane) * V + inst] = l;
-                out[((size_t)1 * T + t0 + lane) * V + inst] = rr;
-            } else {
-                (out + (inst * 2 + 0) * fstride + t0)[lane] = l;
-                (out + (inst * 2 + 1) * fstride + t0)[lane] = rr;
-            }
-        }
-        fdn_wave_sync();
-        // carry the last two delay outputs and the last feedback value of this block into slots 0, 1 / 0
-        if (lane < 32) {
-            const float a = hist[lane * HS + size], b = hist[lane * HS + size + 1], f = fbr[lane * HS + size];
-            hist[lane * HS + 0] = a;
-            hist[lane * HS + 1] = b;
-            fbr[lane * HS + 0] = f;
-        }
+        fdn_output_store(io, 2, t0, size, bus, l, rr, xi0, xi1);
+        fdn_block_carry<32, 3>(hist, fbr, lane, size);
         wp = (wp + size) & CMASK;
-        fdn_wave_sync();
     }
     if (lane == 0) s.wpos[inst] = wp;
-    if (lane < 32) {
-        s.v1[inst * 32 + lane] = hist[lane * HS + 0];
-        s.v2[inst * 32 + lane] = hist[lane * HS + 1];
-        s.fb[inst * 32 + lane] = fbr[lane * HS + 0];
-    }
+    if (lane < 32) fdn_state_store<3>(s, inst, lane, hist, fbr);
 }
-
 
 // ---- the generic network, lane = FRAME -----------------------------------------------------------------------------------------------
 // `split::<N>() / multisplit::<M, N/M>() >> fdn::<N, _>(stacki(|i| delay(t_i) >> fir(w))) >> join::<N>() / multijoin::<M, N/M>()`: the Hadamard
@@ -547,126 +461,55 @@ template <int NL, int K>
 __global__ __launch_bounds__(256) void k_fdn_frames_generic(FdnConst c, FdnState s, size_t V, const float* __restrict__ in,
                                                             float* __restrict__ out, size_t T, size_t fstride, int layout, int tick_mode, FdnBus bus) {
     static_assert(K >= 1 && K <= 3 && NL >= 2 && NL <= 32 && (NL & (NL - 1)) == 0, "generic FDN: 2..32 lines (a power of two), FIR order 1..3");
-    constexpr int H0 = K - 1;               // carried delay outputs per line: Fir::v[1 .. K-1]
-    __shared__ float hist_all[4][NL * HS];  // per line: the H0 carried delay outputs | d[0..63]
+    __shared__ float hist_all[4][NL * HS];  // per line: the K - 1 carried delay outputs | d[0..63]
     __shared__ float fbr_all[4][NL * HS];   // per line: fb[-1] | fb[0..63]
     const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* hist = hist_all[wib];
     float* fbr = fbr_all[wib];
     const size_t inst = (size_t)blockIdx.x * 4 + wib;
     if (inst >= V) return;
-    const float w0 = c.w[0], w1 = c.w[1], w2 = c.w[2];
-    const float scale = c.had_scale;
+    const FdnUniformLines p{c};
     const int nin = c.nin, nout = c.nout;   // 1 or 2
-    const int CMASK = c.cap - 1, CP = c.cap + 64;
-    const __amdgpu_buffer_rsrc_t rings = __builtin_amdgcn_make_buffer_rsrc(s.rings + inst * c.ring_stride, 0, (int)(c.ring_stride * sizeof(float)), 0x00020000);
+    const int CMASK = c.cap - 1;
+    const __amdgpu_buffer_rsrc_t rings = fdn_rings(s, inst, c.ring_stride);
     const int lane4 = lane * 4;
     int wp = __builtin_amdgcn_readfirstlane(s.wpos[inst]);
-    if (lane < NL) {  // carry-in: Fir::v[1..K-1] (v1 = the older, v2 = the newer of a Fir<U3>; a Fir<U2> keeps its one sample in v2), Feedback::value
-        if (K == 3) hist[lane * HS + 0] = s.v1[inst * 32 + lane];
-        if (K >= 2) hist[lane * HS + H0 - 1] = s.v2[inst * 32 + lane];
-        fbr[lane * HS + 0] = s.fb[inst * 32 + lane];
-    }
+    if (lane < NL) fdn_state_load<K>(s, inst, lane, hist, fbr);
     float dn[NL], xin[2];
     auto fetch = [&](size_t t0n, int wpn) {
-        const int sizen = (int)((T - t0n) < 64 ? (T - t0n) : 64);
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int r = (wpn - (c.len[k] - 1)) & CMASK;   // frame 0 reads the slot written len - 1 frames ago; 64 contiguous slots from there (mirror zone)
-            dn[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rings, lane4, (k * CP + r) * 4, 0));
-        }
+        fdn_ring_fetch(dn, rings, lane4, c.cap, wpn, p);
+        // The block's input frames (zeros past a ragged end).  The same four lines stand in k_fdn_frames_filtered (fd_fdnx.hip): a fix to one
+        // is a fix to both.  Not a shared step: as a function it compiled to another shape (profiles/fdn_frames_shared_isa.txt).
+        const int sizen = fdn_block_size(T, t0n);
 #pragma unroll
         for (int ch = 0; ch < 2; ch++)
             xin[ch] = (ch < nin && lane < sizen) ? (layout == 0 ? in[((size_t)ch * T + t0n + lane) * V + inst] : in[(inst * nin + ch) * fstride + t0n + lane]) : 0.0f;
     };
     fetch(0, wp);
     for (size_t t0 = 0; t0 < T; t0 += 64) {
-        const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
+        const int size = fdn_block_size(T, t0);
         float d[NL];
-        const float xi0 = xin[0], xi1 = nin == 2 ? xin[1] : xin[0];
-        const float xin_now[2] = {xin[0], xin[1]};   // (this block's input frames, by channel: the bus reads them at the end of the block)
+        const float x0 = xin[0], x1 = xin[1];   // this block's input frames, by channel
+        const float xi1 = nin == 2 ? x1 : x0;   // line k takes input channel k % nin
 #pragma unroll
         for (int k = 0; k < NL; k++) d[k] = dn[k];
         if (t0 + 64 < T) fetch(t0 + 64, (wp + 64) & CMASK);
-        if (K > 1) {
-#pragma unroll
-            for (int k = 0; k < NL; k++) hist[k * HS + H0 + lane] = d[k];
-            fdn_wave_sync();
-        }
         float o[NL], h[NL];
+        fdn_fir_lines<NL, K>(o, d, hist, lane, p);
 #pragma unroll
-        for (int k = 0; k < NL; k++) {  // Fir::tick fir.rs:57-70: the sum starts at 0.0 and takes the taps oldest first
-            float acc = 0.0f;
-            if (K == 3) {
-                acc += w0 * hist[k * HS + lane];
-                acc += w1 * hist[k * HS + lane + 1];
-                acc += w2 * d[k];
-            } else if (K == 2) {
-                acc += w0 * hist[k * HS + lane];
-                acc += w1 * d[k];
-            } else {
-                acc += w0 * d[k];
-            }
-            o[k] = acc;
-            h[k] = acc;
-        }
-#pragma unroll
-        for (int st = 1; st < NL; st <<= 1)  // FrameHadamard feedback.rs:35-57
-#pragma unroll
-            for (int i = 0; i < NL; i++)
-                if ((i & st) == 0) {
-                    const float x = h[i], y = h[i + st];
-                    h[i] = x + y;
-                    h[i + st] = x - y;
-                }
-#pragma unroll
-        for (int k = 0; k < NL; k++) fbr[k * HS + 1 + lane] = h[k] * scale;
-        fdn_wave_sync();
-        float xw[NL];  // Feedback::tick: input + value (feedback.rs:130-134)
-#pragma unroll
-        for (int k = 0; k < NL; k++) xw[k] = ((k & 1) ? xi1 : xi0) + fbr[k * HS + lane];
-        if (size == 64 && wp >= 64 && wp + 64 <= c.cap) {
-#pragma unroll
-            for (int k = 0; k < NL; k++)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, lane4, (k * CP + wp) * 4, 0);
-        } else if (lane < size) {  // wrap, mirror zone or ragged tail
-            const int pos = (wp + lane) & CMASK;
-#pragma unroll
-            for (int k = 0; k < NL; k++) {
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, pos * 4, k * CP * 4, 0);
-                if (pos < 64) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, xw[k]), rings, (c.cap + pos) * 4, k * CP * 4, 0);
-            }
-        }
-        // Join<N> / MultiJoin<M, N/M>: channel j over lines j, j + nout, ..
-        float y0, y1 = 0.0f;
-        if (nout == 1) {
-            if (tick_mode) {
-                y0 = o[0];
-#pragma unroll
-                for (int i = 1; i < NL; i++) y0 += o[i];
-                y0 = y0 / (float)NL;
-            } else {
-                const float z = 1.0f / (float)NL;
-                y0 = o[0] * z;
-#pragma unroll
-                for (int i = 1; i < NL; i++) y0 += o[i] * z;
-            }
-        } else {
-            if (tick_mode) {
-                y0 = o[0]; y1 = o[1];
-#pragma unroll
-                for (int i = 1; i < NL / 2; i++) { y0 += o[2 * i]; y1 += o[2 * i + 1]; }
-                y0 = y0 / (float)(NL / 2); y1 = y1 / (float)(NL / 2);
-            } else {
-                const float z = 1.0f / (float)(NL / 2);
-                y0 = o[0] * z; y1 = o[1] * z;
-#pragma unroll
-                for (int i = 1; i < NL / 2; i++) { y0 += o[2 * i] * z; y1 += o[2 * i + 1] * z; }
-            }
-        }
-        if (bus.mode) {  // wet * network [& dry * multipass()] (fd_fdn.hpp FdnBus; mode 2: nin == nout)
-            y0 = fdn_bus(bus, y0, xin_now[0]);
-            y1 = fdn_bus(bus, y1, xin_now[1]);
+        for (int k = 0; k < NL; k++) h[k] = o[k];
+        fdn_hadamard<NL>(h);
+        fdn_feedback_put(h, c.had_scale, fbr, lane);
+        float xw[NL];
+        fdn_ring_input<0, NL>(xw, fbr, lane, x0, xi1);
+        fdn_ring_store(xw, rings, lane, lane4, c.cap, wp, size);
+        float y0, y1;
+        fdn_join<NL>(o, nout, tick_mode, y0, y1);
+        // The bus epilogue and the output store: fdn_output_store's text, in place.  Called as the shared step, the 32-line instantiations
+        // of THIS kernel took more SGPR spills (<32, 3>: 18 for 11; profiles/fdn_frames_shared_isa.txt); the other two kernels call it.
+        if (bus.mode) {
+            y0 = fdn_bus(bus, y0, x0);
+            y1 = fdn_bus(bus, y1, x1);
         }
         if (lane < size) {
             if (layout == 0) {
@@ -677,34 +520,11 @@ __global__ __launch_bounds__(256) void k_fdn_frames_generic(FdnConst c, FdnState
                 if (nout == 2) out[(inst * nout + 1) * fstride + t0 + lane] = y1;
             }
         }
-        fdn_wave_sync();
-        if (lane < NL) {  // the block's last delay outputs and feedback value become the next block's carry-in
-            float a = 0.0f, b = 0.0f;
-            if (K == 3) { a = hist[lane * HS + size]; b = hist[lane * HS + size + 1]; }
-            if (K == 2) b = hist[lane * HS + size];
-            const float f = fbr[lane * HS + size];
-            if (K == 3) hist[lane * HS + 0] = a;
-            if (K >= 2) hist[lane * HS + H0 - 1] = b;
-            fbr[lane * HS + 0] = f;
-        }
+        fdn_block_carry<NL, K>(hist, fbr, lane, size);
         wp = (wp + size) & CMASK;
-        fdn_wave_sync();
     }
     if (lane == 0) s.wpos[inst] = wp;
-    if (lane < NL) {
-        if (K == 3) s.v1[inst * 32 + lane] = hist[lane * HS + 0];
-        if (K >= 2) s.v2[inst * 32 + lane] = hist[lane * HS + H0 - 1];
-        s.fb[inst * 32 + lane] = fbr[lane * HS + 0];
-    }
-}
-
-template <int NL>
-static void fdn_launch_generic(const FdnConst& c, const FdnState& s, size_t instances, const float* in, float* out, size_t T, size_t fstride, int layout,
-                               int tick_mode, hipStream_t stream, const FdnBus& bus) {
-    const dim3 grid((unsigned)((instances + 3) / 4)), block(256);
-    if (c.taps == 3) hipLaunchKernelGGL((k_fdn_frames_generic<NL, 3>), grid, block, 0, stream, c, s, instances, in, out, T, fstride, layout, tick_mode, bus);
-    else if (c.taps == 2) hipLaunchKernelGGL((k_fdn_frames_generic<NL, 2>), grid, block, 0, stream, c, s, instances, in, out, T, fstride, layout, tick_mode, bus);
-    else hipLaunchKernelGGL((k_fdn_frames_generic<NL, 1>), grid, block, 0, stream, c, s, instances, in, out, T, fstride, layout, tick_mode, bus);
+    if (lane < NL) fdn_state_store<K>(s, inst, lane, hist, fbr);
 }
 
 // ---- voice-minor I/O for the lane = frame kernels -----------------------------------------------------------------------------------
@@ -744,8 +564,8 @@ void fdn_launch_transpose(const float* src, float* dst, size_t V, size_t T, int 
                        channels, to_planar ? 1 : 0);
 }
 
-void fdn_launch_reset(const FdnConst& c, const FdnState& s, size_t instances, hipStream_t stream) {
-    hipLaunchKernelGGL(k_fdn_reset, dim3(2048), dim3(256), 0, stream, c, s, instances);
+void fdn_launch_reset_state(const FdnState& s, float* s1, float* s2, size_t ring_stride, size_t instances, hipStream_t stream) {
+    hipLaunchKernelGGL(k_fdn_reset, dim3(2048), dim3(256), 0, stream, s, s1, s2, ring_stride, instances);
 }
 
 void fdn_launch_render(const FdnConst& c, const FdnState& s, size_t instances, const float* in, float* out, size_t T,
@@ -753,13 +573,8 @@ void fdn_launch_render(const FdnConst& c, const FdnState& s, size_t instances, c
     if (instances == 0 || T == 0) return;
     if (c.generic) {
         tl_opts.last_kernel = LK_FDN_FRAMES;
-        switch (c.lines) {
-        case 2: return fdn_launch_generic<2>(c, s, instances, in, out, T, fstride, layout, tick_mode, stream, bus);
-        case 4: return fdn_launch_generic<4>(c, s, instances, in, out, T, fstride, layout, tick_mode, stream, bus);
-        case 8: return fdn_launch_generic<8>(c, s, instances, in, out, T, fstride, layout, tick_mode, stream, bus);
-        case 16: return fdn_launch_generic<16>(c, s, instances, in, out, T, fstride, layout, tick_mode, stream, bus);
-        default: return fdn_launch_generic<32>(c, s, instances, in, out, T, fstride, layout, tick_mode, stream, bus);
-        }
+        FD_FDN_FRAMES_LAUNCH(k_fdn_frames_generic, 1, c.lines, c.taps, instances, stream, c, s, instances, in, out, T, fstride, layout, tick_mode, bus);
+        return;
     }
     const bool frames = tl_opts.fdn_kernel == 0 || c.sections == 2;  // (two networks in series: the lane = frame formulation only)
     tl_opts.last_kernel = frames ? LK_FDN_FRAMES : LK_FDN_LINES;

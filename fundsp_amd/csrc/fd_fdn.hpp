@@ -85,7 +85,12 @@ __device__ __forceinline__ float fdn_bus(const FdnBus& b, float y, float x) {
 
 // host: constants of reverb_stereo(room_size, time, damping) at `sample_rate` (prelude.rs:1739-1759)
 void fdn_make_const(double room_size, double time, double damping, double sample_rate, FdnConst* c);
-void fdn_launch_reset(const FdnConst& c, const FdnState& s, size_t instances, hipStream_t stream);
+// Feedback::reset of every instance: one kernel for all the networks.  s1, s2: the line filters' state of the filtered networks (fd_fdnx.hpp
+// FdnxState), null where the network has none
+void fdn_launch_reset_state(const FdnState& s, float* s1, float* s2, size_t ring_stride, size_t instances, hipStream_t stream);
+inline void fdn_launch_reset(const FdnConst& c, const FdnState& s, size_t instances, hipStream_t stream) {
+    fdn_launch_reset_state(s, nullptr, nullptr, c.ring_stride, instances, stream);
+}
 // host: constants of reverb4_stereo(room_size, time) at `sample_rate` (prelude.rs:1873-1941): two fdn::<U16> of delay >> fir3 lines in
 // series, `multijoin::<U2, U8>() >> multisplit::<U2, U8>()` between them, sumf::<U16>(pan) * dc((1/4, 1/4)) behind the second
 void fdn_make_const_reverb4(double room_size, double time, double sample_rate, FdnConst* c);

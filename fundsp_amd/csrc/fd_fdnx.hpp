@@ -23,7 +23,7 @@
 
 #include <vector>
 
-#include "fd_fdn.hpp"   // FdnBus
+#include "fd_fdn.hpp"   // FdnBus, FdnState
 
 namespace fd {
 
@@ -55,12 +55,7 @@ struct FdnxDesc {                 // host side: the network as created (P = per_
     std::vector<float> cutoff, q, gain, line_gain;   // [P][lines] (empty where the network has none)
 };
 
-struct FdnxState {
-    float* rings;                 // [instances][lines][cap + 64]
-    int* wpos;                    // [instances] shared write position
-    float* v1;                    // [instances][32] Fir::v[1]
-    float* v2;                    // [instances][32] Fir::v[2]
-    float* fb;                    // [instances][32] Feedback::value
+struct FdnxState : FdnState {     // the rings, the write position, the Fir carry and the feedback value of fd_fdn.hpp, and the filters' state
     float* s1;                    // [instances][32] Lowpole::value | FixedSvf ic1eq
     float* s2;                    // [instances][32] FixedSvf ic2eq
 };
@@ -68,7 +63,9 @@ struct FdnxState {
 // host: the parameter table at `sample_rate` (instances entries, or 1) and the constants; returns the shortest delay in samples over all
 // instances and lines (the caller applies the two-block rule) and -1 when a ring would exceed 2^18 slots
 int fdnx_make_table(const FdnxDesc& d, size_t instances, double sample_rate, std::vector<FdnxInst>& tab, FdnxConst* c);
-void fdnx_launch_reset(const FdnxConst& c, const FdnxState& s, size_t instances, hipStream_t stream);
+inline void fdnx_launch_reset(const FdnxConst& c, const FdnxState& s, size_t instances, hipStream_t stream) {
+    fdn_launch_reset_state(s, s.s1, s.s2, c.ring_stride, instances, stream);   // Feedback(2)::reset: fd_fdn.hpp's kernel, with the filters
+}
 void fdnx_launch_render(const FdnxConst& c, const FdnxState& s, size_t instances, const float* in, float* out, size_t T, size_t fstride,
                         int layout, int tick_mode, hipStream_t stream, const FdnBus& bus = FdnBus());
 

@@ -19,10 +19,11 @@ pytestmark = pytest.mark.gpu
 SR = 48000.0
 
 
-def params(n, V, filt, taps, gain, per_voice, seed):
-    """Bank.fdn_network keyword arguments: per-line values, and with per_voice a [V, n] spread of room sizes / cutoffs / gains"""
+def params(n, V, filt, taps, gain, per_voice, seed, delay_range=None):
+    """Bank.fdn_network keyword arguments: per-line values, and with per_voice a [V, n] spread of room sizes / cutoffs / gains;
+    delay_range: (lo, hi) seconds in place of the doc example's 0.01 .. 0.03"""
     rng = np.random.default_rng(seed)
-    base = np.array(delays_of(n), dtype=np.float32)
+    base = np.array(delays_of(n, *delay_range) if delay_range else delays_of(n), dtype=np.float32)
     p = {}
     if per_voice:
         room = np.linspace(1.0, 1.6, V, dtype=np.float32)[:, None]
@@ -118,21 +119,34 @@ def signal(V, nin, T, seed):
     return x
 
 
-CASES = [  # lines, filter, place, taps, gain, inputs, outputs, per-voice parameters, instances
-    (32, "lowpole", "loop", 3, True, 2, 2, True, 66),
-    (16, "lowpass", "line", 0, True, 1, 1, False, 6),
-    (2, "highshelf", "loop", 3, False, 1, 2, False, 6),
-    (16, "highshelf", "line", 3, False, 2, 1, True, 66),
-    (32, "lowpass", "line", 2, True, 1, 1, True, 5),
+# The smallest ring that can still go wrong: delays of 0.003 .. 0.005 s are 144 .. 240 samples at 48 kHz (above the 128-sample rule), so the
+# rings have 256 slots, the write window of the 1 933 frames below wraps seven times, and the ragged launches of 77, 1 and 333 frames cross
+# the mirror zone (the first 64 slots, copied behind the ring) slot by slot.
+SHORT_RING_DELAYS = (0.003, 0.005)
+
+CASES = [  # lines, filter, place, taps, gain, inputs, outputs, per-voice parameters, instances, delay range (None: the doc example's)
+    (32, "lowpole", "loop", 3, True, 2, 2, True, 66, None),
+    (16, "lowpass", "line", 0, True, 1, 1, False, 6, None),
+    (2, "highshelf", "loop", 3, False, 1, 2, False, 6, None),
+    (16, "highshelf", "line", 3, False, 2, 1, True, 66, None),
+    (32, "lowpass", "line", 2, True, 1, 1, True, 5, None),
+    # the filtered kernel without a filter (its instantiation of the steps the generic kernel shares with it), a workgroup with one live wave
+    (16, None, "line", 3, False, 1, 1, False, 5, None),
+    (4, None, "line", 2, True, 2, 2, True, 5, None),
+    (2, "lowpole", "loop", 3, True, 1, 2, False, 5, SHORT_RING_DELAYS),
 ]
+# (the ids pytest would give the first nine columns: a row's id does not change when a column is added behind them)
+CASE_IDS = ["-".join(str(v) for v in r[:9]) for r in CASES]
 
 
 @pytest.mark.parametrize("mode", [MODE_PROCESS, MODE_TICK])
 @pytest.mark.parametrize("layout", [LAYOUT_PLANAR, LAYOUT_VOICE_MINOR])
-@pytest.mark.parametrize("n,filt,place,taps,gain,nin,nout,per_voice,V", CASES)
-def test_network_matches_oracle(gpu, n, filt, place, taps, gain, nin, nout, per_voice, V, layout, mode):
+@pytest.mark.parametrize("n,filt,place,taps,gain,nin,nout,per_voice,V,delay_range", CASES, ids=CASE_IDS)
+def test_network_matches_oracle(gpu, n, filt, place, taps, gain, nin, nout, per_voice, V, delay_range, layout, mode):
     T = 64 * 30 + 13
-    p = params(n, V, filt, taps, gain, per_voice, n + taps)
+    p = params(n, V, filt, taps, gain, per_voice, n + taps, delay_range)
+    if delay_range == SHORT_RING_DELAYS:   # (the case is about a 256-slot ring)
+        assert 128 <= int(np.round(p["delays"] * SR).min()) and int(np.round(p["delays"] * SR).max()) + 1 <= 256
     b = gpu.Bank.fdn_network(V, n, place=place, inputs=nin, outputs=nout, sample_rate=SR, **p)
     assert b.kind == "fdn_network" and b.inputs() == nin and b.outputs() == nout
     x = signal(V, nin, T, 11 * n + taps)
@@ -147,6 +161,27 @@ def test_network_matches_oracle(gpu, n, filt, place, taps, gain, nin, nout, per_
     assert not np.any((got[1] != 0) & (np.abs(got[1]) < np.float32(1.17549435e-38)))   # no denormal reaches the output
     b.reset()   # reset mid-stream: the same first launches again
     assert_bit_equal(run(b, x[:, :, :700], layout, mode, [0, 64, 700]), got[:, :, :700], "after reset")
+
+
+@pytest.mark.parametrize("mode", [MODE_PROCESS, MODE_TICK])
+@pytest.mark.parametrize("n", [2, 16])
+def test_unfiltered_network_equals_the_generic_fdn_kernel(gpu, n, mode):
+    """k_fdn_frames_generic and k_fdn_frames_filtered are two instantiations of the same block steps (fd_fdn_frames.hpp): the same network
+    through fdsp_fdn_create and, with its weights repeated per line and no filter, through fdsp_fdn_network_create gives identical samples
+    over full, ragged and one-frame launches.  No oracle: this holds the two kernels against each other."""
+    V, T, w = 5, 64 * 9 + 13, (0.2, 0.4, 0.2)
+    delays = delays_of(n, *SHORT_RING_DELAYS)   # 144 .. 240 samples: the network recirculates (and its 256-slot rings wrap) within the 589 frames
+    a = gpu.Bank.fdn(V, n, delays, 3, w)
+    a.set_sample_rate(SR)
+    b = gpu.Bank.fdn_network(V, n, delays, weights=np.tile(np.array(w, dtype=np.float32), (n, 1)), filter=None, sample_rate=SR)
+    assert a.kind == "fdn" and b.kind == "fdn_network"
+    x = signal(V, 1, T, 41 + n)
+    cuts = [0, 64, 141, 142, T]
+    ya = run(a, x, LAYOUT_PLANAR, mode, cuts)
+    yb = run(b, x, LAYOUT_PLANAR, mode, cuts)
+    assert a.get_option("last_kernel") == 6 and b.get_option("last_kernel") == 6
+    assert np.abs(ya[0]).max() > 1e-3
+    assert_bit_equal(yb, ya, f"fdn<{n}> fir3: filtered kernel without a filter vs generic kernel")
 
 
 @pytest.mark.parametrize("place,filt", [("loop", "lowpole"), ("line", "highshelf")])
