@@ -54,7 +54,7 @@ class Bank:
         """Compile `graph` (fundsp_amd.graph notation) into a fused kernel set at run time and build a bank of `voices`
         instances of it with the graph's parameters applied (scalars to every voice, arrays per voice).
         A graph that IS a Hadamard feedback delay network (graph.fdn_plan: split >> fdn(stacki(delay >> fir)) >> join, uniform parameters,
-        every delay longer than two blocks) becomes a bank of the lane-per-frame FDN kernel instead (fdsp_fdn_create) -- the same samples,
+        every delay at least two blocks, 128 samples) becomes a bank of the lane-per-frame FDN kernel instead (fdsp_fdn_create) -- the same samples,
         two orders of magnitude faster than one lane per voice; `fdn_kernel=False` keeps the run-time compiled form.
         `flush_denormals`: compile the graph with f32 denormals flushed although it has no Feedback node of its own -- the front half of a chain
         whose other half has one (Feedback::new's prevent_denormals() sets FTZ + DAZ for the constructing thread, feedback.rs:96, denormal.rs:18: the

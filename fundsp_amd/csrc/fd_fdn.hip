@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
     for (int st = 0; st < 5; st++) negmask[st] = (k & (1 << st)) ? 0x80000000u : 0u;
 
     // Ring rows and inputs of a block are fetched one block AHEAD into registers (issued before the recurrence of the
-    // current block, consumed after it): every delay exceeds 128 samples, so the rows block b+1 reads are not touched
+    // current block, consumed after it): every delay is at least 128 samples, so the rows block b+1 reads are not touched
     // by block b's writes, and the HBM latency hides behind phase 2.  In these phases lane = frame (all 64 lanes).
     float xr[R], xin[2 * IPW];
     auto fetch = [&](size_t t0n, int wp_now) {
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void k_fdn_render(FdnConst c, FdnState s, size
 }
 
 // ---- lane = FRAME formulation ------------------------------------------------------------------------------------
-// Inside one 64-frame block nothing depends on the feedback: every delay is longer than 128 samples, so the 64 ring
+// Inside one 64-frame block nothing depends on the feedback: every delay is at least 128 samples, so the 64 ring
 // reads of a line -- and with them the FIR outputs, the Hadamard and the new feedback values -- are known up front; the
 // only frame-to-frame coupling is `x[n] = in[n] + fb[n-1]` (the ring write) and the FIR's two-sample history.  So one
 // wave renders one instance with lane = frame: the 32 lines live in 32 registers, the Hadamard is 5 x 32 register
@@ -366,7 +366,7 @@ struct FdnUniformLines {
 // block of a launch that is not a multiple of 64 frames) take the general per-lane path.
 // NSEC = 2 (reverb4_stereo): the 32 lines are TWO 16-line networks in series -- lines 0-15 take the input, their FIR outputs are averaged to
 // two channels (MultiJoin<U2, U8>) and split again (MultiSplit<U2, U8>) into lines 16-31, whose outputs are panned.  Nothing else changes: the
-// ring reads, FIR outputs and Hadamard feedback of BOTH networks are known at the head of the block (every delay is longer than 128
+// ring reads, FIR outputs and Hadamard feedback of BOTH networks are known at the head of the block (every delay is at least 128
 // samples), the butterflies simply stop at stride 8, and the second network's ring write of frame n adds the join of the first one's FIR
 // outputs of the same frame.
 template <int CAP_LOG2, int NSEC>
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState 
 // ---- the generic network, lane = FRAME -----------------------------------------------------------------------------------------------
 // `split::<N>() / multisplit::<M, N/M>() >> fdn::<N, _>(stacki(|i| delay(t_i) >> fir(w))) >> join::<N>() / multijoin::<M, N/M>()`: the Hadamard
 // feedback delay network as the prelude documents it (prelude.rs:1323-1345, the "Mono Reverb" example :1334), N = NL lines of any delays
-// longer than two blocks, FIR order K.  The same formulation as k_fdn_render_frames -- one wave per instance, lane = frame, the lines in
+// of at least two blocks (128 samples), FIR order K.  The same formulation as k_fdn_render_frames -- one wave per instance, lane = frame, the lines in
 // registers, ring rows loaded one block ahead and stored as 256-byte runs -- with the ring capacity a run-time value (a handful of scalar
 // instructions per line and block instead of immediates), no pan fold, and the splitter / joiner the graph names:
 //   in : line k takes input channel k % nin   (Split :559-562, MultiSplit :600-606: output i = input i % M)

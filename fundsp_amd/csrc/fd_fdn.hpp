@@ -7,7 +7,7 @@
 // with fdn = Feedback<U32, _, FrameHadamard> (feedback.rs:18-146), Delay (delay.rs:72-139), Fir<U3> (fir.rs:14-89).
 //
 // Two formulations, identical samples (fdsp_set_option("fdn_kernel", ..)):
-//  * lane = FRAME (default, k_fdn_render_frames): one wave renders one instance.  Every delay is longer than two blocks,
+//  * lane = FRAME (default, k_fdn_render_frames): one wave renders one instance.  Every delay is at least two blocks (128 samples),
 //    so inside a 64-frame block the ring reads -- and with them the FIR outputs, the Hadamard and the feedback values --
 //    do not depend on the block's own writes: the 32 lines sit in 32 registers, the Hadamard is 5 x 32 register
 //    butterflies in the reference's stage order, ring rows are loaded (one block ahead) and stored in the lane = frame

@@ -1,6 +1,6 @@
 // fd_fdn_frames.hpp -- the steps of a 64-frame block that the lane = FRAME Hadamard kernels share: k_fdn_render_frames and
 // k_fdn_frames_generic (fd_fdn.hip) and k_fdn_frames_filtered (fd_fdnx.hip); device functions, and at the end the host-side launch ladder.  One wave renders one instance, lane = frame,
-// the lines of the network in registers; every delay is longer than two blocks, so all ring reads of a block are known at its head.
+// the lines of the network in registers; every delay is at least two blocks (128 samples), so all ring reads of a block are known at its head.
 // These are the steps that have to match the reference bit for bit (the order of the FIR terms, the butterfly stage order, tick against
 // process in the joins, the mirror zone): each is written ONCE here, and a kernel is a sequence of them with its own parts in between (the
 // pan fold and the series join of the reverbs, the filter of the filtered networks).  A step is templated on what the kernels are

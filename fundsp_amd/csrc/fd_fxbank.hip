@@ -186,9 +186,9 @@ class HadamardFx final : public NetFx {
         else if (kind_ == REVERB4) fdn_make_const_reverb4(room_, time_, sr, &c);
         else fdn_make_const(room_, time_, damping_, sr, &c);
         for (int i = 0; i < c.lines; i++)
-            if (c.len[i] <= 128)
-                return api_fail(FDSP_EINVAL, kind_ == GENERIC ? "fdsp_fdn_create: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)"
-                                                               : "reverb_stereo / reverb4_stereo: every delay must exceed 128 samples (room_size * sample_rate too small)");
+            if (c.len[i] <= 128)   // len = delay + 1: a delay of 128 samples is the shortest
+                return api_fail(FDSP_EINVAL, kind_ == GENERIC ? "fdsp_fdn_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)"
+                                                               : "reverb_stereo / reverb4_stereo: every delay must be at least 128 samples (room_size * sample_rate too small)");
         if (kind_ != REVERB && c.cap > (1 << 18))
             return api_fail(FDSP_EINVAL, "reverb4_stereo / fdsp_fdn_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
         FdnState st{};

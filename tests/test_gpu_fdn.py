@@ -23,12 +23,12 @@ def delays_of(n, lo=0.01, hi=0.03):
     return [float(np.float32(np.float32(lo) * (np.float32(1.0) - np.float32(x)) + np.float32(hi) * np.float32(x))) for x in r]
 
 
-def oracle_net(n, delays, w, nin, nout):
+def oracle_net(n, delays, w, nin, nout, sr=SR):
     line = O.stacki(n, lambda i: O.delay(delays[i]) >> O.fir(*w))
     head = O.split(n) if nin == 1 else O.multisplit(2, n // 2)
     tail = O.join(n) if nout == 1 else O.multijoin(2, n // 2)
     net = head >> O.fdn(line) >> tail
-    net.set_sample_rate(SR)
+    net.set_sample_rate(sr)
     return net
 
 

@@ -19,13 +19,18 @@ pytestmark = pytest.mark.gpu
 SR = 48000.0
 
 
-def params(n, V, filt, taps, gain, per_voice, seed, delay_range=None):
+def params(n, V, filt, taps, gain, per_voice, seed, delay_range=None, delay_samples=None):
     """Bank.fdn_network keyword arguments: per-line values, and with per_voice a [V, n] spread of room sizes / cutoffs / gains;
-    delay_range: (lo, hi) seconds in place of the doc example's 0.01 .. 0.03"""
+    delay_range: (lo, hi) seconds in place of the doc example's 0.01 .. 0.03; delay_samples: the delays themselves, [n] or (per_voice)
+    [V, n] whole samples at SR, taken as they are"""
     rng = np.random.default_rng(seed)
     base = np.array(delays_of(n, *delay_range) if delay_range else delays_of(n), dtype=np.float32)
     p = {}
-    if per_voice:
+    if delay_samples is not None:
+        k = np.asarray(delay_samples, dtype=np.float64)
+        assert k.shape == ((V, n) if per_voice else (n,)) and np.all(k == np.round(k))
+        p["delays"] = (k / SR).astype(np.float32).astype(np.float64)   # (the f32 seconds delay(t: f32) takes)
+    elif per_voice:
         room = np.linspace(1.0, 1.6, V, dtype=np.float32)[:, None]
         p["delays"] = (base[None, :] * room).astype(np.float32).astype(np.float64)
     else:
@@ -110,12 +115,16 @@ def device_graph(n, p, place, nin, nout, V):
     return head >> core >> tail
 
 
-def signal(V, nin, T, seed):
+def signal(V, nin, T, seed, impulse=None):
+    """noise that stops at 2T/3; instance 1 in the denormal range; `impulse`: an instance driven by one unit sample instead"""
     rng = np.random.default_rng(seed)
     x = (rng.random((V, nin, T), dtype=np.float32) * 2 - 1).astype(np.float32)
     x[:, :, 2 * T // 3:] = 0.0
     x[1] *= np.float32(1e-30)                            # an instance that lives in the denormal range: Feedback2::new flushes
     x[1, :, 2 * T // 3 - 40:2 * T // 3] = np.float32(3e-39)
+    if impulse is not None:
+        x[impulse] = 0.0
+        x[impulse, 0, 0] = 1.0
     return x
 
 
