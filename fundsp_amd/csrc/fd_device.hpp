@@ -18,11 +18,10 @@
 #pragma once
 
 #include "fd_nodes.hpp"
+#include "fd_plan.hpp"  // LAYOUT_* / MODE_* / MIX_*, GraphTraits
 
 namespace fd {
 
-constexpr int LAYOUT_VOICE_MINOR = 0, LAYOUT_PLANAR = 1;
-constexpr int MODE_PROCESS = 0, MODE_TICK = 1;
 constexpr int TILE_STRIDE = 68;  // floats per voice row in an LDS tile (64 + 4: keeps b128 alignment, breaks bank aliasing)
 
 // ---- visitors --------------------------------------------------------------------------------------------
@@ -865,7 +864,6 @@ FD_HD long long round_index(double x) {  // `round(x) as usize`: half away from 
 // (an odd node at the end of a level passes through).  fdsp_sum_voices / fdsp_mix_stereo of a voice-out render use the same
 // order, so the fused mix equals them bit for bit (tests/test_gpu_mix.py).
 // Reference shape: the Panner / Reduce arithmetic of src/pan.rs:50-76, src/audionode.rs:2406-2462 over a bank of voices.
-constexpr int MIX_NONE = 0, MIX_SUM = 1, MIX_PAN = 2;  // sum every output channel over the voices | pan a mono graph to stereo, then sum
 constexpr int MIX_ROW = 68;  // floats per (channel, frame) row of a mix tile: 64 voices + 4 (16-byte runs stay aligned, lane-per-row b128 reads spread over the banks)
 template <int NM, int GPW, int SUB>
 struct MixGeom {  // frames per chunk: what fits the 32 KiB the pipeline's own tiles leave of a CU's 160 KiB of LDS
@@ -2097,7 +2095,7 @@ __global__ __launch_bounds__((16 * GPW * PipeGeom<G::IN, S>::WAVES)) FD_PIPE_ATT
 //   waves of a workgroup (ONE voice group): NA x stage 0 | NB x stage 1 | 1 x stage 2, stage s one block behind stage s-1;
 //   hand-over tiles [frame pair][lane] v2f, double-buffered: 2 cuts x 2 x 16 KiB = 64 KiB -> two workgroups per CU.
 // Needs: process mode, voice-minor layout, no graph inputs, a 3-stage chain whose first two stages define skip2,
-// T a multiple of 64 (launch_render falls back to the pipeline kernel otherwise).
+// T a multiple of 64 (fd_plan.hpp: the pipeline kernel otherwise).
 template <class SG, class G, bool FIRST, int W>
 FD_D void ts_stage(G& g, int lo, int hi, int lane, v2f (*hin)[32][64], v2f (*hout)[32][64]) {
     constexpr int NI = SG::IN, NO = SG::OUT;
@@ -2581,13 +2579,6 @@ __global__ __launch_bounds__((64 * GPW * PlanarPlan<G>::template Tiles<S, K1>::W
     render_pipe_planar_body<G, MODE, S, K1, GPW>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap);
 }
 
-// Launch policy for the voice-minor layout: voices per wave such that the grid has at least one wave per SIMD.
-inline int voices_per_wave(size_t V, int simds) {
-    int vpw = 64;
-    while (vpw > 16 && (V + vpw - 1) / vpw < (size_t)simds) vpw >>= 1;
-    return vpw;
-}
-
 // LDS the planar path needs per wave, and the workgroup width chosen from it (shared by the AOT and JIT launchers)
 template <class G, int LAYOUT>
 struct RenderGeom {
@@ -2638,28 +2629,6 @@ struct JitPipeSmall {
     static constexpr bool on = P.S >= 1 && Cost<G>::v >= 150;
     template <int GPW> static constexpr int threads() { return on ? 16 * GPW * PipeGeom<G::IN, (P.S >= 1 ? P.S : 1)>::WAVES : 64; }
 };
-template <class G>
-FD_D void describe_body(char* out, int cap, int* meta) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    G g;
-    VDescribeDev d{out, 0, cap, {0}, 0};
-    g.visit(d);
-    out[d.pos] = 0;
-    meta[0] = G::IN;
-    meta[1] = G::OUT;
-    meta[2] = G::RINGS;
-    meta[3] = d.pos;
-    meta[4] = RenderGeom<G, LAYOUT_PLANAR>::WPB;
-    constexpr PipePlan P = pipe_plan<G>(0);  // pipeline kernel plan of run-time compiled graphs (0 stages = not used)
-    meta[5] = P.S;
-    meta[6] = P.S >= 1 ? 64 * PipeGeom<G::IN, (P.S >= 1 ? P.S : 1)>::WAVES : 0;
-    meta[7] = PlanarPlan<G>::S >= 1 ? 256 * PlanarPlan<G>::T::WAVES : 0;  // threads of the planar pipeline kernel (0 = none)
-    meta[8] = SameType<typename FastOf<G>::type, G>::v ? 0 : 1;            // the graph has a tolerance-mode variant
-    meta[9] = JitPipeSmall<G>::on ? 1 : 0;                                 // heavy: jit_pipe_g1 / _g2 exist for small banks
-    meta[10] = PipeMinT<G>::v;                                             // launch length from which the pipeline kernel is taken
-    meta[11] = TsPlan<G>::ok ? 1 : 0;                                      // a three-stage generator chain: small banks take the time-split kernels (jit_ts3_g1 / _g2)
-    meta[12] = WideChain<G>::on ? WideChain<G>::W : 0;                     // a wide sum of generators: waves of the chain kernel (jit_wide_*) small banks take, 0 = none
-}
 // the three-way time-split kernels for run-time compiled graphs (small banks of three-stage generator chains; a module of their own with the
 // mix-down kernels, compiled on first use): empty when the graph does not qualify
 template <class G, int GPW>
@@ -2679,7 +2648,7 @@ FD_D void jit_pipe_body(float* __restrict__ slots, size_t stride, size_t V, cons
     constexpr PipePlan P = pipe_plan<G>(0);
     if constexpr (P.S >= 1) render_pipe_body<G, MODE, P.S, P.K1, P.K2>(slots, stride, V, in, out, T, aux, ring, ring_cap);
 }
-// the same for workgroups of GPW = 1 / 2 voice groups: heavy graphs on small banks (see launch_render_pipe); empty otherwise
+// the same for workgroups of GPW = 1 / 2 voice groups: heavy graphs on small banks (fd_plan.hpp pipe_gpw); empty otherwise
 template <class G, int MODE, int GPW>
 FD_D void jit_pipe_small_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
                               float* __restrict__ out, size_t T, const void* aux, float* ring, uint32_t ring_cap) {
@@ -2722,5 +2691,40 @@ struct JitPipeThreads {
     static constexpr PipePlan P = pipe_plan<G>(0);
     static constexpr int v = P.S >= 1 ? 64 * PipeGeom<G::IN, (P.S >= 1 ? P.S : 1)>::WAVES : 64;
 };
+
+// What the launch policy (fd_plan.hpp) needs to know about G and about the kernels built for it -- the one place it is computed.
+// run_time: the kernel set of a run-time compiled kind (fd_jit.hip jit_source / jit_source_mix) instead of an ahead-of-time kind's.
+template <class G>
+constexpr GraphTraits graph_traits(bool run_time) {
+    constexpr PipePlan P = pipe_plan<G>(0);
+    constexpr bool heavy = Cost<G>::v >= 150, ts = TsPlan<G>::ok;
+    GraphTraits t{};
+    t.nin = G::IN, t.nout = G::OUT, t.nrings = G::RINGS;
+    t.wpb_planar = RenderGeom<G, LAYOUT_PLANAR>::WPB;
+    // (a run-time kind forces its best plan -- except for "pipe_split" 4, loader wave only, on a graph without such a plan: the single wave, as ahead of time)
+    for (int want = 0; want < 4; want++) t.pipe_stages[want] = !run_time ? pipe_plan<G>(want).S : (want == 1 && pipe_plan<G>(1).S < 1) ? 0 : P.S;
+    t.pipe_min_t = PipeMinT<G>::v;
+    t.pipe_threads = P.S >= 1 ? JitPipeThreads<G>::v : 0;
+    t.pipe_planar_threads = PlanarPlan<G>::S >= 1 ? JitPipePlanarThreads<G>::v : 0;
+    t.planar_stages = PlanarPlan<G>::S;
+    t.wide_waves = run_time && WideChain<G>::on ? WideChain<G>::W : 0;
+    t.heavy = heavy;
+    t.small_groups_planar = t.small_groups_mix = heavy && !run_time;
+    t.ts_ok = ts, t.ts_round2 = ts && !run_time, t.ts_mix_ok = ts && (!run_time || G::OUT <= 2);
+    t.mix_sum_ok = !run_time || jit_mix_channels_ok(G::OUT);
+    t.has_fast = !SameType<typename FastOf<G>::type, G>::v;
+    return t;
+}
+// Device-side introspection of a run-time compiled graph: the slot text (NUL-terminated) and the traits of its kernels
+template <class G>
+FD_D void describe_body(char* out, int cap, GraphTraits* traits) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    G g;
+    VDescribeDev d{out, 0, cap, {0}, 0};
+    g.visit(d);
+    out[d.pos] = 0;
+    constexpr GraphTraits t = graph_traits<G>(true);
+    *traits = t;
+}
 
 }  // namespace fd

@@ -3,6 +3,7 @@
 
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fd_device.hpp"
@@ -39,8 +40,6 @@ struct VDescribe {  // host only
     void enter(int i) { path.push_back(i); }
     void leave() { path.pop_back(); }
 };
-
-int simd_count();  // SIMDs of the current device (CUs x 4), fd_capi.hip
 
 // ---- per-kind dispatch table ---------------------------------------------------------------------------------
 struct KindOps {
@@ -96,208 +95,127 @@ void launch_lifecycle(float* slots, size_t stride, size_t first, size_t count, i
                        ring, ring_cap);
 }
 
-template <class G, int MODE, int LAYOUT>
-void launch_render_cfg(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, size_t fstride,
-                       const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
-    // 4-wave workgroups unless the per-wave LDS tiles of the planar path would not fit 4x in the CU's LDS
-    constexpr int WPB = RenderGeom<G, LAYOUT>::WPB;
-    const int vpw = LAYOUT == LAYOUT_VOICE_MINOR ? voices_per_wave(V, simd_count()) : 64;
-    if (LAYOUT == LAYOUT_VOICE_MINOR) fstride = (size_t)vpw;  // see render_body: fstride carries voices-per-wave here
-    const size_t waves = (V + vpw - 1) / vpw;
-    unsigned grid = (unsigned)((waves + WPB - 1) / WPB);
-    hipLaunchKernelGGL((k_render<G, MODE, LAYOUT, WPB>), dim3(grid), dim3(64 * WPB), 0, s, slots, stride, V, in, out, T,
-                       fstride, aux, ring, ring_cap);
+// ---- render: the launch plan (fd_plan.hpp) decides, these launch the kernel it names.  Only the kernels a graph can be planned into
+// are instantiated: the `if constexpr` guards below say as types what graph_traits<G>() tells the plan as values.
+struct RenderArgs {
+    float* slots; size_t stride, V; const float* in; float* out; size_t T, fstride; const void* aux; float* ring; uint32_t ring_cap;
+    const float* panw;  // fused mix-down (`out` is then the partial-mix buffer)
+    hipStream_t s;
+};
+template <int N> using IntC = std::integral_constant<int, N>;
+// f(IntC<GPW>) for the plan's voice groups per workgroup; workgroups of 1 / 2 groups exist for heavy graphs only
+template <class G, class F>
+void with_gpw(int gpw, F&& f) {
+    if constexpr (Cost<G>::v >= 150) {
+        if (gpw == 1) return f(IntC<1>{});
+        if (gpw == 2) return f(IntC<2>{});
+    }
+    f(IntC<4>{});
 }
-
-template <class G, int MODE, int WANT>
-bool launch_render_pipe(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const void* aux,
-                        float* ring, uint32_t ring_cap, hipStream_t s) {
+// the voice-minor stage pipeline of pipe_plan<G>(WANT); MIX != MIX_NONE: with the fused mix-down
+template <class G, int MODE, int WANT, int MIX = MIX_NONE>
+void launch_pipe(const RenderPlan& p, const RenderArgs& a) {
     constexpr PipePlan P = pipe_plan<G>(WANT);
     if constexpr (P.S >= 1) {
         constexpr int WAVES = PipeGeom<G::IN, P.S>::WAVES;  // for 4 voice groups
-        const size_t cus = (size_t)simd_count() / 4;
-        // light graphs keep 4 groups per workgroup; heavy ones (latency-bound waves) are spread so that every CU gets one
-        const size_t groups = (V + 63) / 64;
-        bool done = false;
-        // (a workgroup of 1 or 2 groups spends the LDS of 4 on longer tiles -- PipeTiles -- so it must be alone on its CU)
-        if constexpr (Cost<G>::v >= 150) {
-            if (!done && groups <= cus) {
-                hipLaunchKernelGGL((k_render_pipe<G, MODE, P.S, P.K1, P.K2, 1>), dim3((unsigned)groups), dim3(16 * WAVES), 0, s, slots,
-                                   stride, V, in, out, T, aux, ring, ring_cap);
-                done = true;
-            } else if (!done && groups <= 2 * cus) {
-                hipLaunchKernelGGL((k_render_pipe<G, MODE, P.S, P.K1, P.K2, 2>), dim3((unsigned)((groups + 1) / 2)), dim3(16 * 2 * WAVES), 0,
-                                   s, slots, stride, V, in, out, T, aux, ring, ring_cap);
-                done = true;
-            }
-        }
-        if (!done)
-            hipLaunchKernelGGL((k_render_pipe<G, MODE, P.S, P.K1, P.K2, 4>), dim3((unsigned)((groups + 3) / 4)), dim3(16 * 4 * WAVES), 0, s,
-                               slots, stride, V, in, out, T, aux, ring, ring_cap);
-        return true;
-    } else {
-        return false;
+        with_gpw<G>(p.gpw, [&](auto gpw) {
+            constexpr int GPW = decltype(gpw)::value;
+            if constexpr (MIX == MIX_NONE)
+                hipLaunchKernelGGL((k_render_pipe<G, MODE, P.S, P.K1, P.K2, GPW>), dim3(p.grid), dim3(16 * GPW * WAVES), 0, a.s, a.slots, a.stride, a.V,
+                                   a.in, a.out, a.T, a.aux, a.ring, a.ring_cap);
+            else
+                hipLaunchKernelGGL((k_render_pipe_mix<G, MODE, P.S, P.K1, P.K2, GPW, MIX>), dim3(p.grid), dim3(16 * GPW * WAVES), 0, a.s, a.slots,
+                                   a.stride, a.V, a.in, a.out, a.T, a.aux, a.ring, a.ring_cap, a.panw);
+        });
     }
 }
-template <class G, int MODE>
-bool launch_render_split(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const void* aux,
-                         float* ring, uint32_t ring_cap, hipStream_t s) {
-    if (tl_opts.pipe_split == 4) return launch_render_pipe<G, MODE, 1>(slots, stride, V, in, out, T, aux, ring, ring_cap, s);
-    if (tl_opts.pipe_split == 2) return launch_render_pipe<G, MODE, 2>(slots, stride, V, in, out, T, aux, ring, ring_cap, s);
-    if (tl_opts.pipe_split == 3) return launch_render_pipe<G, MODE, 3>(slots, stride, V, in, out, T, aux, ring, ring_cap, s);
-    return launch_render_pipe<G, MODE, 0>(slots, stride, V, in, out, T, aux, ring, ring_cap, s);
-}
-
-// planar layout through the pipeline kernel (loader / compute stages / storer); false = not applicable
-template <class G, int MODE>
-bool launch_render_pipe_planar(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, size_t fstride,
-                               const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
-    using PP = PlanarPlan<G>;
-    if constexpr (PP::S >= 1) {
-        constexpr int WAVES = PP::T::WAVES;
-        const size_t groups = (V + 63) / 64;
-        const size_t cus = (size_t)simd_count() / 4;
-        // heavy graphs (latency-bound waves) are spread so that every CU gets a workgroup, as in launch_render_pipe
-        bool done = false;
-        if constexpr (Cost<G>::v >= 150) {
-            if (groups < 2 * cus) {
-                hipLaunchKernelGGL((k_render_pipe_planar<G, MODE, PP::S, PP::K1, 1>), dim3((unsigned)groups), dim3(64 * WAVES), 0, s, slots,
-                                   stride, V, in, out, T, fstride, aux, ring, ring_cap);
-                done = true;
-            } else if (groups < 4 * cus) {
-                hipLaunchKernelGGL((k_render_pipe_planar<G, MODE, PP::S, PP::K1, 2>), dim3((unsigned)((groups + 1) / 2)), dim3(128 * WAVES), 0,
-                                   s, slots, stride, V, in, out, T, fstride, aux, ring, ring_cap);
-                done = true;
-            }
+// the time-split kernels of small banks (process mode, voice-minor)
+template <class G, int MIX>
+void launch_ts(const RenderPlan& p, const RenderArgs& a) {
+    auto ts3 = [&](auto gpw) {  // the three-way split, 1 or 2 voice groups per workgroup
+        constexpr int GPW = decltype(gpw)::value, THREADS = 64 * Ts3Roles<GPW>::WAVES;
+        if constexpr (MIX != MIX_NONE)
+            hipLaunchKernelGGL((k_render_ts3_mix<G, GPW, MIX>), dim3(p.grid), dim3(THREADS), 0, a.s, a.slots, a.stride, a.V, a.out, a.T, a.aux, a.panw);
+        else
+            hipLaunchKernelGGL((k_render_ts3<G, GPW>), dim3(p.grid), dim3(THREADS), 0, a.s, a.slots, a.stride, a.V, a.out, a.T, a.aux);
+    };
+    if constexpr (MIX == MIX_NONE)
+        if (p.ts_round2) {  // "time_split" 2: 2 + 2 + 1 waves, or 2 + 1 + 1
+            if (p.ts_round2 == 2) hipLaunchKernelGGL((k_render_ts<G, 2, 2>), dim3(p.grid), dim3(64 * 5), 0, a.s, a.slots, a.stride, a.V, a.out, a.T, a.aux);
+            else hipLaunchKernelGGL((k_render_ts<G, 2, 1>), dim3(p.grid), dim3(64 * 4), 0, a.s, a.slots, a.stride, a.V, a.out, a.T, a.aux);
+            return;
         }
-        if (!done)
-            hipLaunchKernelGGL((k_render_pipe_planar<G, MODE, PP::S, PP::K1, 4>), dim3((unsigned)((groups + 3) / 4)), dim3(256 * WAVES), 0, s,
-                               slots, stride, V, in, out, T, fstride, aux, ring, ring_cap);
-        return true;
+    if (p.gpw == 1) ts3(IntC<1>{});
+    else ts3(IntC<2>{});
+}
+template <class G, int MODE, int LAYOUT>
+void launch_single(const RenderPlan& p, const RenderArgs& a) {
+    constexpr int WPB = RenderGeom<G, LAYOUT>::WPB;  // = p.gpw
+    const size_t fstride = LAYOUT == LAYOUT_VOICE_MINOR ? (size_t)p.vpw : a.fstride;  // see render_body: fstride carries voices-per-wave here
+    hipLaunchKernelGGL((k_render<G, MODE, LAYOUT, WPB>), dim3(p.grid), dim3(64 * WPB), 0, a.s, a.slots, a.stride, a.V, a.in, a.out, a.T, fstride, a.aux,
+                       a.ring, a.ring_cap);
+}
+template <class G, int MODE>
+void launch_render_mode(const RenderPlan& p, const RenderArgs& a, int layout) {
+    if (p.family == LK_PIPELINE_PLANAR) {  // loader / compute stages / storer
+        using PP = PlanarPlan<G>;
+        if constexpr (PP::S >= 1)
+            with_gpw<G>(p.gpw, [&](auto gpw) {
+                constexpr int GPW = decltype(gpw)::value;
+                hipLaunchKernelGGL((k_render_pipe_planar<G, MODE, PP::S, PP::K1, GPW>), dim3(p.grid), dim3(64 * GPW * PP::T::WAVES), 0, a.s, a.slots,
+                                   a.stride, a.V, a.in, a.out, a.T, a.fstride, a.aux, a.ring, a.ring_cap);
+            });
+    } else if (p.family == LK_PIPELINE) {
+        if (p.want == 1) launch_pipe<G, MODE, 1>(p, a);
+        else if (p.want == 2) launch_pipe<G, MODE, 2>(p, a);
+        else if (p.want == 3) launch_pipe<G, MODE, 3>(p, a);
+        else launch_pipe<G, MODE, 0>(p, a);
+    } else if (layout == LAYOUT_VOICE_MINOR) {
+        launch_single<G, MODE, LAYOUT_VOICE_MINOR>(p, a);
     } else {
-        return false;
+        launch_single<G, MODE, LAYOUT_PLANAR>(p, a);
     }
 }
-
-
-// Launch lengths from which a launch leaves the single-wave kernel: PipeMinT<G> (fd_device.hpp) for the stage pipeline, and one whole
-// 64-frame block for the time-split kernels of small banks (config 3's shards: 9.2-9.8 us against 13.5-13.9 at T = 64, 12.5-13.4 against
-// 22 at 128, 15-16 against 30 at 192; profiles/r04_small_t_kernels.txt).  "pipe_split" 2 / 3 force the pipeline at any length, 0 the
-// single-wave kernel.
-#ifndef FD_TS_MIN_T
-#define FD_TS_MIN_T 64
-#endif
-// The planar pipeline (loader waves transpose 16-byte runs of the per-voice rows through LDS, a storer wave transposes back) beats the
-// single-wave kernel's strided row accesses at every measured length and for every graph -- config 3: 9.8 vs 10.9 us at T = 16, 16.2 vs
-// 19.1 at 64; config 4: 18.8 vs 28.0, 30.8 vs 51.9; config 2: 6.5 vs 6.9, 8.5 vs 9.0 (profiles/r04_small_t_kernels.txt, planar table).
-#ifndef FD_PLANAR_PIPE_MIN_T
-#define FD_PLANAR_PIPE_MIN_T 16
-#endif
 template <class G>
 void launch_render(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, size_t fstride,
                    int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
     if (V == 0 || T == 0) return;
-    // banks that leave most SIMDs idle (<= 2 voice groups per CU): split the oscillator stages over time as well
-    if constexpr (TsPlan<G>::ok) {
-        const size_t groups = (V + 63) / 64, cus = (size_t)simd_count() / 4;
-        if (tl_opts.time_split && tl_opts.pipe_split == 1 && layout == LAYOUT_VOICE_MINOR && mode == MODE_PROCESS && T % 64 == 0 && T >= FD_TS_MIN_T &&
-            groups <= 2 * cus) {
-            if (tl_opts.time_split == 1) {  // round 3: both oscillator stages split three ways, the filter wave (nearly) alone on a SIMD
-                if (groups <= cus)
-                    hipLaunchKernelGGL((k_render_ts3<G, 1>), dim3((unsigned)groups), dim3(64 * Ts3Roles<1>::WAVES), 0, s, slots, stride, V, out, T, aux);
-                else
-                    hipLaunchKernelGGL((k_render_ts3<G, 2>), dim3((unsigned)((groups + 1) / 2)), dim3(64 * Ts3Roles<2>::WAVES), 0, s, slots, stride, V, out, T, aux);
-            } else if (groups <= cus)  // time_split = 2: round 2's layouts.  One workgroup per CU: 2 + 2 + 1 waves
-                hipLaunchKernelGGL((k_render_ts<G, 2, 2>), dim3((unsigned)groups), dim3(64 * 5), 0, s, slots, stride, V, out, T, aux);
-            else                // two workgroups per CU: 2 + 1 + 1 waves each, roles rotated between neighbours
-                hipLaunchKernelGGL((k_render_ts<G, 2, 1>), dim3((unsigned)groups), dim3(64 * 4), 0, s, slots, stride, V, out, T, aux);
-            tl_opts.last_kernel = LK_TIME_SPLIT;
-            return;
-        }
-    }
-    // planar rows that allow 16-byte runs go through the planar pipeline (same launch-size rule as below)
-    if (layout == LAYOUT_PLANAR && tl_opts.pipe_split && (T >= FD_PLANAR_PIPE_MIN_T || tl_opts.pipe_split > 1) && fstride % 4 == 0 && ((uintptr_t)in & 15) == 0 &&
-        ((uintptr_t)out & 15) == 0) {
-        const bool done = mode == MODE_PROCESS ? launch_render_pipe_planar<G, MODE_PROCESS>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s)
-                                               : launch_render_pipe_planar<G, MODE_TICK>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s);
-        if (done) { tl_opts.last_kernel = LK_PIPELINE_PLANAR; return; }
-    }
-    // the stage pipeline from PipeMinT<G> frames on (one 64-frame block for chains worth cutting, four for light graphs)
-    if (layout == LAYOUT_VOICE_MINOR && tl_opts.pipe_split && (T >= (size_t)PipeMinT<G>::v || tl_opts.pipe_split > 1)) {
-        const bool done = mode == MODE_PROCESS ? launch_render_split<G, MODE_PROCESS>(slots, stride, V, in, out, T, aux, ring, ring_cap, s)
-                                               : launch_render_split<G, MODE_TICK>(slots, stride, V, in, out, T, aux, ring, ring_cap, s);
-        if (done) { tl_opts.last_kernel = LK_PIPELINE; return; }
-    }
-    tl_opts.last_kernel = LK_SINGLE_WAVE;
-    if (layout == LAYOUT_VOICE_MINOR) {
-        if (mode == MODE_PROCESS)
-            launch_render_cfg<G, MODE_PROCESS, LAYOUT_VOICE_MINOR>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s);
-        else
-            launch_render_cfg<G, MODE_TICK, LAYOUT_VOICE_MINOR>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s);
+    constexpr GraphTraits traits = graph_traits<G>(false);
+    const RenderPlan p = plan_render(traits, tl_opts, (size_t)simd_count() / 4, V, T, layout, mode, fstride, (((uintptr_t)in | (uintptr_t)out) & 15) == 0);
+    tl_opts.last_kernel = p.family;
+    const RenderArgs a{slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, nullptr, s};
+    if (p.family == LK_TIME_SPLIT) {
+        if constexpr (TsPlan<G>::ok) launch_ts<G, MIX_NONE>(p, a);
+    } else if (mode == MODE_PROCESS) {
+        launch_render_mode<G, MODE_PROCESS>(p, a, layout);
     } else {
-        if (mode == MODE_PROCESS)
-            launch_render_cfg<G, MODE_PROCESS, LAYOUT_PLANAR>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s);
-        else
-            launch_render_cfg<G, MODE_TICK, LAYOUT_PLANAR>(slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, s);
+        launch_render_mode<G, MODE_TICK>(p, a, layout);
     }
 }
 
 // ---- render + mix-down in one launch ------------------------------------------------------------------------------
-template <class G, int MODE, int MIX>
-bool launch_render_pipe_mix(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const void* aux,
-                            float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) {
-    constexpr PipePlan P = pipe_plan<G>(0);
-    if constexpr (P.S >= 1) {
-        constexpr int WAVES = PipeGeom<G::IN, P.S>::WAVES;  // for 4 voice groups
-        const size_t cus = (size_t)simd_count() / 4, groups = (V + 63) / 64;
-        // the same workgroup widths as launch_render_pipe: heavy graphs on small banks are spread over the CUs
-        if constexpr (Cost<G>::v >= 150) {
-            if (groups <= cus) {
-                hipLaunchKernelGGL((k_render_pipe_mix<G, MODE, P.S, P.K1, P.K2, 1, MIX>), dim3((unsigned)groups), dim3(16 * WAVES), 0, s, slots,
-                                   stride, V, in, part, T, aux, ring, ring_cap, panw);
-                return true;
-            }
-            if (groups <= 2 * cus) {
-                hipLaunchKernelGGL((k_render_pipe_mix<G, MODE, P.S, P.K1, P.K2, 2, MIX>), dim3((unsigned)((groups + 1) / 2)), dim3(16 * 2 * WAVES), 0,
-                                   s, slots, stride, V, in, part, T, aux, ring, ring_cap, panw);
-                return true;
-            }
-        }
-        hipLaunchKernelGGL((k_render_pipe_mix<G, MODE, P.S, P.K1, P.K2, 4, MIX>), dim3((unsigned)((groups + 3) / 4)), dim3(16 * 4 * WAVES), 0, s,
-                           slots, stride, V, in, part, T, aux, ring, ring_cap, panw);
-        return true;
-    } else {
-        return false;
-    }
-}
-template <class G, int MIX>
-bool launch_render_mix_m(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, int mode, const void* aux,
-                         float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) {
-    if constexpr (TsPlan<G>::ok) {  // small banks of oscillator chains: the three-way time split, as in launch_render
-        const size_t groups = (V + 63) / 64, cus = (size_t)simd_count() / 4;
-        if (tl_opts.time_split == 1 && tl_opts.pipe_split == 1 && mode == MODE_PROCESS && T % 64 == 0 && T >= FD_TS_MIN_T && groups <= 2 * cus) {
-            if (groups <= cus)
-                hipLaunchKernelGGL((k_render_ts3_mix<G, 1, MIX>), dim3((unsigned)groups), dim3(64 * Ts3Roles<1>::WAVES), 0, s, slots, stride, V, part, T, aux, panw);
-            else
-                hipLaunchKernelGGL((k_render_ts3_mix<G, 2, MIX>), dim3((unsigned)((groups + 1) / 2)), dim3(64 * Ts3Roles<2>::WAVES), 0, s, slots, stride, V, part, T, aux, panw);
-            tl_opts.last_kernel = LK_TIME_SPLIT;
-            return true;
-        }
-    }
-    const bool done = mode == MODE_PROCESS ? launch_render_pipe_mix<G, MODE_PROCESS, MIX>(slots, stride, V, in, part, T, aux, ring, ring_cap, panw, s)
-                                           : launch_render_pipe_mix<G, MODE_TICK, MIX>(slots, stride, V, in, part, T, aux, ring, ring_cap, panw, s);
-    if (done) tl_opts.last_kernel = LK_PIPELINE;
-    return done;
-}
 template <class G>
 bool launch_render_mix(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, int mix, int mode,
                        const void* aux, float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) {
     if (V == 0 || T == 0) return true;
-    if (mix == MIX_PAN) {
-        if constexpr (G::OUT == 1) return launch_render_mix_m<G, MIX_PAN>(slots, stride, V, in, part, T, mode, aux, ring, ring_cap, panw, s);
-        else return false;
-    }
-    return launch_render_mix_m<G, MIX_SUM>(slots, stride, V, in, part, T, mode, aux, ring, ring_cap, panw, s);
+    constexpr GraphTraits traits = graph_traits<G>(false);
+    const RenderPlan p = plan_render_mix(traits, tl_opts, (size_t)simd_count() / 4, V, T, mix, mode);
+    if (p.family == LK_NONE) return false;
+    tl_opts.last_kernel = p.family;
+    const RenderArgs a{slots, stride, V, in, part, T, 0, aux, ring, ring_cap, panw, s};
+    auto launch = [&](auto mix_c) {
+        constexpr int MIX = decltype(mix_c)::value;
+        if (p.family == LK_TIME_SPLIT) {
+            if constexpr (TsPlan<G>::ok) launch_ts<G, MIX>(p, a);
+        } else if (mode == MODE_PROCESS) {
+            launch_pipe<G, MODE_PROCESS, 0, MIX>(p, a);
+        } else {
+            launch_pipe<G, MODE_TICK, 0, MIX>(p, a);
+        }
+    };
+    if (mix != MIX_PAN) launch(IntC<MIX_SUM>{});
+    else if constexpr (G::OUT == 1) launch(IntC<MIX_PAN>{});
+    return true;
 }
 template <class G>
 bool launch_render_events_mix(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const double* ev,

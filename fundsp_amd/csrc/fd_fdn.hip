@@ -10,10 +10,6 @@
 #include "fd_math.hpp"
 
 namespace fd {
-int simd_count();          // fd_capi.hip
-}
-
-namespace fd {
 
 static const double RV_DELAYS[32] = {  // prelude.rs:1739-1744
     0.073904, 0.052918, 0.066238, 0.066387, 0.037783, 0.080073, 0.050961, 0.075900, 0.043646,

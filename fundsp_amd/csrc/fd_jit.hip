@@ -155,20 +155,15 @@ struct JitModule {
     std::mutex mu;
     JitFuncs dev[MAXD];
     bool loaded[MAXD] = {false};
-    int pipe_stages = 0, pipe_threads = 0, pipe_planar_threads = 0, pipe_min_t = 256;
-    bool pipe_small = false;                                                 // heavy graph: workgroups of 1 / 2 voice groups for small banks
-    bool ts_ok = false;                                                      // three-stage generator chain: small banks take the time-split kernels
-    int wide_waves = 0;                                                      // a wide sum of generators: waves per voice group of the chain kernel (0 = none)
-    int wpb[2] = {4, 4};                                                     // per layout
+    GraphTraits traits{};                                                    // what the launch plan needs (fd_plan.hpp), as jit_describe reports it
     // the tolerance-mode twin of this graph (FastOf<G>), compiled on first use
     std::string type_expr, prelude;
-    bool has_fast = false, fast_failed = false;
+    bool fast_failed = false;
     std::shared_ptr<JitModule> fast;
     // the fused mix-down kernels (of G, and of FastOf<G>), compiled on first use
     std::shared_ptr<JitMix> mix[2];
     bool mix_failed[2] = {false, false};
     std::mutex mix_mu;
-    int nout = 0;
     ~JitModule() {  // a module is unloaded with ITS device current (it was loaded on that device's context)
         int prev = -1;
         const bool have_prev = hipGetDevice(&prev) == hipSuccess;
@@ -290,73 +285,47 @@ JitMix* jit_extra_module(JitModule* jm, int which) {
 
 // `base` / `which`: the kind's module and which of its variants `jm` is (0 = G itself, 1 = its tolerance-mode twin) -- where the second module lives
 void jit_render(JitModule* jm, float* slots, size_t stride, size_t V, const float* in, float* outp, size_t T, size_t fstride,
-                int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s, JitModule* base = nullptr, int which = 0) {
+                int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s, JitModule* base, int which) {
     if (V == 0 || T == 0) return;
     const JitFuncs* f = jm->get();
     if (!f) return jit_launch_failed();
-    // banks that leave most SIMDs idle (<= 2 voice groups per CU) of three-stage generator chains: the three-way time split, as launch_render
-    // does for the ahead-of-time kinds (its kernels are compiled the first time such a launch happens; no such kernels -> the pipeline below)
-    if (base && base->ts_ok && tl_opts.time_split == 1 && tl_opts.pipe_split == 1 && layout == LAYOUT_VOICE_MINOR && mode == MODE_PROCESS &&
-        T % 64 == 0 && T >= FD_TS_MIN_T) {
-        const size_t groups = (V + 63) / 64, cus = (size_t)simd_count() / 4;
-        if (groups <= 2 * cus) {
-            JitMix* mm = jit_extra_module(base, which);
-            const JitMix::Dev* tf = mm ? mm->get() : nullptr;
-            if (tf) {
-                const int gpw = groups <= cus ? 1 : 2;
-                void* targs[] = {&slots, &stride, &V, &outp, &T, &aux};
-                hipModuleLaunchKernel(tf->ts[gpw - 1], (unsigned)((groups + gpw - 1) / gpw), 1, 1, 64u * (gpw == 1 ? Ts3Roles<1>::WAVES : Ts3Roles<2>::WAVES), 1, 1, 0, s,
-                                      targs, nullptr);
-                tl_opts.last_kernel = LK_TIME_SPLIT;
-                return;
-            }
+    GraphTraits traits = jm->traits;
+    const size_t cus = (size_t)simd_count() / 4;
+    const bool aligned = (((uintptr_t)in | (uintptr_t)outp) & 15) == 0;
+    RenderPlan p = plan_render(traits, tl_opts, cus, V, T, layout, mode, fstride, aligned);
+    const JitMix::Dev* tf = nullptr;
+    if (p.family == LK_TIME_SPLIT) {  // its kernels are compiled the first time such a launch happens; no such kernels -> the plan without them
+        JitMix* mm = jit_extra_module(base, which);
+        tf = mm ? mm->get() : nullptr;
+        if (!tf) {
+            traits.ts_ok = false;
+            p = plan_render(traits, tl_opts, cus, V, T, layout, mode, fstride, aligned);
         }
     }
-    // A wide sum of generators at the root (fd_device.hpp WideSum): its kernels are the branch-major ones, whatever the layout -- the chain of
-    // waves (render_body_wide_chain) for every launch of more than one block: it fills the chip from 256 voice groups on where one wave per
-    // voice group needs 1 024, and at 1 024 groups it still wins by its two waves per SIMD (the reference's 100-sine bench, ms per rendered
-    // second at 64 / 1 024 / 16 384 / 32 768 / 49 152 / 65 536 instances: 41 / 41 / 43 / 85 / 128 / 171 against 169 / 233 / 181 / 180 / 313 / 181,
-    // profiles/r06_wide_chain_probe.txt); one-block launches and "pipe_split" 0: render_body_wide through the single-wave entry point below.
-    // The stage pipelines walk such a graph frame-major with every branch in registers: never.
-    const bool wide = jm->wide_waves > 0;
-    if (wide && tl_opts.pipe_split && T > 64) {
-        void* wargs[] = {&slots, &stride, &V, &in, &outp, &T, &fstride, &aux, &ring, &ring_cap};
-        hipModuleLaunchKernel(f->wide[mode][layout], (unsigned)((V + 63) / 64), 1, 1, 64u * (unsigned)jm->wide_waves, 1, 1, 0, s, wargs, nullptr);
-        tl_opts.last_kernel = LK_WIDE_CHAIN;
+    tl_opts.last_kernel = p.family;
+    const unsigned gpw = (unsigned)p.gpw;
+    if (p.family == LK_TIME_SPLIT) {
+        void* targs[] = {&slots, &stride, &V, &outp, &T, &aux};
+        hipModuleLaunchKernel(tf->ts[gpw - 1], p.grid, 1, 1, 64u * (gpw == 1 ? Ts3Roles<1>::WAVES : Ts3Roles<2>::WAVES), 1, 1, 0, s, targs, nullptr);
         return;
     }
-    // loader wave / stage split; short launches (real-time blocks) are faster through the single-wave kernel, as for
-    // the ahead-of-time kinds (launch_render)
-    if (!wide && layout == LAYOUT_VOICE_MINOR && tl_opts.pipe_split && jm->pipe_stages >= 1 && (T >= (size_t)jm->pipe_min_t || tl_opts.pipe_split > 1)) {
+    if (p.family == LK_PIPELINE) {  // loader wave / stage split
         void* pargs[] = {&slots, &stride, &V, &in, &outp, &T, &aux, &ring, &ring_cap};
-        const size_t groups = (V + 63) / 64, cus = (size_t)simd_count() / 4;
-        if (jm->pipe_small && groups <= 2 * cus) {  // heavy graph, small bank: as launch_render_pipe
-            const unsigned gpw = groups <= cus ? 1 : 2;
-            hipModuleLaunchKernel(f->pipe_small[gpw - 1][mode], (unsigned)((groups + gpw - 1) / gpw), 1, 1,
-                                  (unsigned)jm->pipe_threads / 4 * gpw, 1, 1, 0, s, pargs, nullptr);
-            tl_opts.last_kernel = LK_PIPELINE;
-            return;
-        }
-        hipModuleLaunchKernel(f->pipe[mode], (unsigned)((groups + 3) / 4), 1, 1, (unsigned)jm->pipe_threads, 1, 1, 0, s,
-                              pargs, nullptr);
-        tl_opts.last_kernel = LK_PIPELINE;
+        hipModuleLaunchKernel(gpw == 4 ? f->pipe[mode] : f->pipe_small[gpw - 1][mode], p.grid, 1, 1, (unsigned)traits.pipe_threads / 4 * gpw, 1, 1, 0, s, pargs,
+                              nullptr);
         return;
     }
-    if (!wide && layout == LAYOUT_PLANAR && tl_opts.pipe_split && jm->pipe_planar_threads > 0 && (T >= FD_PLANAR_PIPE_MIN_T || tl_opts.pipe_split > 1) && fstride % 4 == 0 &&
-        ((uintptr_t)in & 15) == 0 && ((uintptr_t)outp & 15) == 0) {  // loader / stages / storer (see launch_render)
-        void* pargs[] = {&slots, &stride, &V, &in, &outp, &T, &fstride, &aux, &ring, &ring_cap};
-        hipModuleLaunchKernel(f->pipe_planar[mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, (unsigned)jm->pipe_planar_threads, 1, 1,
-                              0, s, pargs, nullptr);
-        tl_opts.last_kernel = LK_PIPELINE_PLANAR;
-        return;
-    }
-    tl_opts.last_kernel = LK_SINGLE_WAVE;
-    const int wpb = jm->wpb[layout];
-    const int vpw = layout == LAYOUT_VOICE_MINOR ? voices_per_wave(V, simd_count()) : 64;
-    if (layout == LAYOUT_VOICE_MINOR) fstride = (size_t)vpw;
-    const size_t waves = (V + vpw - 1) / vpw;
+    // A wide sum of generators at the root (fd_device.hpp WideSum) runs branch-major: the chain of waves (render_body_wide_chain) from two blocks on
+    // -- 41 / 43 / 171 ms per rendered second at 64 / 16 384 / 65 536 instances against 169 / 181 / 181, profiles/r06_wide_chain_probe.txt --, else
+    // render_body_wide through the single-wave entry point; never a stage pipeline (fd_plan.hpp).
+    if (p.family == LK_SINGLE_WAVE && layout == LAYOUT_VOICE_MINOR) fstride = (size_t)p.vpw;  // see render_body: fstride carries voices-per-wave here
     void* args[] = {&slots, &stride, &V, &in, &outp, &T, &fstride, &aux, &ring, &ring_cap};
-    hipModuleLaunchKernel(f->render[mode][layout], (unsigned)((waves + wpb - 1) / wpb), 1, 1, 64 * wpb, 1, 1, 0, s, args, nullptr);
+    if (p.family == LK_WIDE_CHAIN)
+        hipModuleLaunchKernel(f->wide[mode][layout], p.grid, 1, 1, 64u * (unsigned)traits.wide_waves, 1, 1, 0, s, args, nullptr);
+    else if (p.family == LK_PIPELINE_PLANAR)  // loader / stages / storer
+        hipModuleLaunchKernel(f->pipe_planar[mode], p.grid, 1, 1, (unsigned)traits.pipe_planar_threads, 1, 1, 0, s, args, nullptr);
+    else
+        hipModuleLaunchKernel(f->render[mode][layout], p.grid, 1, 1, 64 * gpw, 1, 1, 0, s, args, nullptr);
 }
 
 }  // namespace
@@ -420,7 +389,7 @@ std::string jit_source(const std::string& type_expr, const std::string& prelude)
              "float* ring, uint32_t cap) {\n"
              "  fd::render_events_body<JitG, " + m + ">(slots, stride, V, in, out, T, ev, fade, time0, sr, aux, ring, cap); }\n";
     }
-    s += "extern \"C\" __global__ void jit_describe(char* out, int cap, int* meta) { fd::describe_body<JitG>(out, cap, meta); }\n";
+    s += "extern \"C\" __global__ void jit_describe(char* out, int cap, fd::GraphTraits* traits) { fd::describe_body<JitG>(out, cap, traits); }\n";
     return s;
 }
 
@@ -503,8 +472,8 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
             }
         }
     }
-    static const char* const names[3] = {"fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp"};
-    return compile_program(src, "graph type `" + type_expr + "`", names, 3, ftz, wide_ilp, code, log);
+    static const char* const names[5] = {"fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_plan.hpp", "fd_opts.hpp"};
+    return compile_program(src, "graph type `" + type_expr + "`", names, 5, ftz, wide_ilp, code, log);
 }
 
 // The process module of a resynthesizer bank's closure (fd_resynth_fn.hpp): the functor's source in namespace fd and rs_process around it.
@@ -603,40 +572,31 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
     // slot introspection on the device (the AOT kinds run the same visit() on the host)
     const int cap = 1 << 16;
     char* d_txt = nullptr;
-    int* d_meta = nullptr;
-    if (hipMalloc((void**)&d_txt, cap) != hipSuccess || hipMalloc((void**)&d_meta, 16 * sizeof(int)) != hipSuccess) {
+    GraphTraits* d_traits = nullptr;
+    if (hipMalloc((void**)&d_txt, cap) != hipSuccess || hipMalloc((void**)&d_traits, sizeof(GraphTraits)) != hipSuccess) {
         *err = "hipMalloc failed";
         return -1;
     }
     int cap_arg = cap;
-    void* dargs[] = {&d_txt, &cap_arg, &d_meta};
+    void* dargs[] = {&d_txt, &cap_arg, &d_traits};
     hipError_t e = hipModuleLaunchKernel(f0->describe, 1, 1, 1, 1, 1, 1, 0, nullptr, dargs, nullptr);
     std::vector<char> txt(cap);
-    int meta[16] = {0};
     if (e == hipSuccess) e = hipMemcpy(txt.data(), d_txt, cap, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&jm->traits, d_traits, sizeof(GraphTraits), hipMemcpyDeviceToHost);
     hipFree(d_txt);
-    hipFree(d_meta);
+    hipFree(d_traits);
     if (e != hipSuccess) {
         *err = std::string("describe kernel failed: ") + hipGetErrorString(e);
         return -1;
     }
     out->name = name;
-    out->nin = meta[0];
-    out->nout = meta[1];
-    out->nrings = meta[2];
-    jm->wpb[LAYOUT_VOICE_MINOR] = 4;
-    jm->wpb[LAYOUT_PLANAR] = meta[4];
-    jm->pipe_stages = meta[5];
-    jm->pipe_threads = meta[6];
-    jm->pipe_planar_threads = meta[7];
-    jm->has_fast = meta[8] != 0;
-    jm->pipe_small = meta[9] != 0;
-    jm->pipe_min_t = meta[10] > 0 ? meta[10] : 256;
-    jm->ts_ok = meta[11] != 0;
-    jm->wide_waves = meta[12];
+    const GraphTraits& traits = jm->traits;
+    out->nin = traits.nin;
+    out->nout = traits.nout;
+    out->nrings = traits.nrings;
     out->slots.clear();
-    std::istringstream lines(std::string(txt.data(), (size_t)meta[3]));
+    txt.back() = 0;
+    std::istringstream lines(std::string(txt.data()));
     std::string line;
     while (std::getline(lines, line)) {
         size_t sp = line.find_last_of(' ');
@@ -663,14 +623,7 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
             auto fm = std::make_shared<JitModule>();
             std::string log;
             if (jit_compile_code("typename fd::FastOf<" + jm->type_expr + ">::type", jm->prelude, &fm->code, &log) == 0) {
-                fm->pipe_stages = jm->pipe_stages;   // FastOf keeps arities, chain shape and tile plan
-                fm->pipe_min_t = jm->pipe_min_t;
-                fm->pipe_threads = jm->pipe_threads;
-                fm->pipe_planar_threads = jm->pipe_planar_threads;
-                fm->pipe_small = jm->pipe_small;
-                fm->wide_waves = jm->wide_waves;
-                fm->wpb[0] = jm->wpb[0];
-                fm->wpb[1] = jm->wpb[1];
+                fm->traits = jm->traits;   // FastOf keeps arities, chain shape and tile plan
                 jm->fast = fm;
             } else {
                 jm->fast_failed = true;
@@ -682,48 +635,41 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
     // Whatever a bank of `voices` voices still has to compile and load before its first render: the tolerance-mode module of a FAST bank, and
     // for small banks of a three-stage generator chain the second module with the time-split kernels (of G, or of FastOf<G> when that twin
     // exists -- the `which` jit_render will ask for).  Called when the bank is created / switched, not in its first render.
-    if (jm->ts_ok || jm->has_fast)
+    if (traits.ts_ok || traits.has_fast)
         out->prepare_render = [jm, fast_module](size_t voices, bool fast) {
-            JitModule* fm = (fast && jm->has_fast) ? fast_module() : nullptr;
+            JitModule* fm = (fast && jm->traits.has_fast) ? fast_module() : nullptr;
             if (fm) fm->get();
-            if (jm->ts_ok && (voices + 63) / 64 <= 2 * (size_t)simd_count() / 4)
+            if (wants_time_split_module(jm->traits, (size_t)simd_count() / 4, voices))
                 if (JitMix* mm = jit_extra_module(jm.get(), fm ? 1 : 0)) mm->get();
         };
-    if (jm->has_fast)
+    if (traits.has_fast)
         out->render_fast = [jm, fast_module](float* slots, size_t stride, size_t V, const float* in, float* outp, size_t T, size_t fstride,
                                              int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
             JitModule* fm = fast_module();
             jit_render(fm ? fm : jm.get(), slots, stride, V, in, outp, T, fstride, layout, mode, aux, ring, ring_cap, s, jm.get(), fm ? 1 : 0);
         };
     // render + mix-down in one launch (fdsp_bank_process_mix): graphs with a pipeline plan; the kernels are compiled on first use
-    jm->nout = meta[1];
     auto mix_module = [jm](int which) -> JitMix* { return jit_extra_module(jm.get(), which); };
     auto mix_launch = [jm, mix_module](int which, float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, int mix, int mode,
                            const void* aux, float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) -> bool {
         if (V == 0 || T == 0) return true;
-        if (jm->pipe_stages < 1 || (mix == MIX_PAN && jm->nout != 1) || (mix == MIX_SUM && !jit_mix_channels_ok(jm->nout))) return false;
+        const RenderPlan p = plan_render_mix(jm->traits, tl_opts, (size_t)simd_count() / 4, V, T, mix, mode);
+        if (p.family == LK_NONE) return false;
         JitMix* mm = mix_module(which);
         if (!mm) return false;
         const JitMix::Dev* f = mm->get();
         if (!f) { jit_launch_failed(); return true; }
-        // small banks of three-stage generator chains: the time-split kernels with the fused mix-down, as launch_render_mix_m
-        if (jm->ts_ok && jm->nout <= 2 && tl_opts.time_split == 1 && tl_opts.pipe_split == 1 && mode == MODE_PROCESS && T % 64 == 0 && T >= FD_TS_MIN_T) {
-            const size_t groups = (V + 63) / 64, cus = (size_t)simd_count() / 4;
-            if (groups <= 2 * cus) {
-                const int gpw = groups <= cus ? 1 : 2;
-                void* targs[] = {&slots, &stride, &V, &part, &T, &aux, &panw};
-                hipModuleLaunchKernel(f->tsm[gpw - 1][mix - 1], (unsigned)((groups + gpw - 1) / gpw), 1, 1, 64u * (gpw == 1 ? Ts3Roles<1>::WAVES : Ts3Roles<2>::WAVES), 1, 1, 0, s,
-                                      targs, nullptr);
-                tl_opts.last_kernel = LK_TIME_SPLIT;
-                return true;
-            }
+        tl_opts.last_kernel = p.family;
+        if (p.family == LK_TIME_SPLIT) {  // small banks of three-stage generator chains
+            void* targs[] = {&slots, &stride, &V, &part, &T, &aux, &panw};
+            hipModuleLaunchKernel(f->tsm[p.gpw - 1][mix - 1], p.grid, 1, 1, 64u * (p.gpw == 1 ? Ts3Roles<1>::WAVES : Ts3Roles<2>::WAVES), 1, 1, 0, s, targs, nullptr);
+            return true;
         }
         void* pargs[] = {&slots, &stride, &V, &in, &part, &T, &aux, &ring, &ring_cap, &panw};
-        hipModuleLaunchKernel(f->fn[mix - 1][mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, (unsigned)jm->pipe_threads, 1, 1, 0, s, pargs, nullptr);
-        tl_opts.last_kernel = LK_PIPELINE;
+        hipModuleLaunchKernel(f->fn[mix - 1][mode], p.grid, 1, 1, (unsigned)jm->traits.pipe_threads, 1, 1, 0, s, pargs, nullptr);
         return true;
     };
-    if (jm->pipe_stages >= 1 && (jm->nout == 1 || jit_mix_channels_ok(jm->nout))) {   // ("has_fused_mix" follows: no kernels, no entry)
+    if (traits.pipe_stages[0] >= 1 && (traits.nout == 1 || traits.mix_sum_ok)) {   // ("has_fused_mix" follows: no kernels, no entry)
         out->prepare_mix = [mix_module](bool fast) {   // compile + load ahead of the real-time loop / stream capture
             if (JitMix* mm = mix_module(fast ? 1 : 0)) mm->get();
         };
@@ -731,13 +677,13 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
                                        const void* aux, float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) {
             return mix_launch(0, slots, stride, V, in, part, T, mix, mode, aux, ring, ring_cap, panw, s);
         };
-        if (jm->has_fast)
+        if (traits.has_fast)
             out->render_mix_fast = [mix_launch](float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, int mix, int mode,
                                                 const void* aux, float* ring, uint32_t ring_cap, const float* panw, hipStream_t s) {
                 return mix_launch(1, slots, stride, V, in, part, T, mix, mode, aux, ring, ring_cap, panw, s);
             };
     }
-    if (jm->nout <= 2)  // the Sequencer's mixed output in one launch (fdsp_bank_process_events_mix)
+    if (traits.nout <= 2)  // the Sequencer's mixed output in one launch (fdsp_bank_process_events_mix)
         out->render_events_mix = [mix_module](float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const double* ev,
                                               const int* fade, double time0, double sr, int mode, const void* aux, float* ring,
                                               uint32_t ring_cap, hipStream_t s) -> bool {

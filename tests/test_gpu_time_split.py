@@ -135,7 +135,7 @@ def test_time_split_in_tolerance_mode(gpu, time_split):
 @pytest.mark.parametrize("V", [64 * 10 + 37, 64 * 300 + 5])
 def test_real_time_blocks_take_the_time_split_and_pipeline_kernels(gpu, time_split, V):
     """Launches of ONE to three 64-frame blocks (a real-time host's AudioNode::process calls): small banks of oscillator chains take the
-    time-split kernels from one block on, every other launch of a chain worth cutting the stage pipeline (fd_engine.hpp FD_TS_MIN_T,
+    time-split kernels from one block on, every other launch of a chain worth cutting the stage pipeline (fd_plan.hpp FD_TS_MIN_T,
     fd_device.hpp PipeMinT), shorter launches the single-wave kernel -- one state, one stream of samples whichever kernel ran: a run of
     mixed launch lengths equals the oracle's continuous render bit for bit (one group per CU and the 14-wave two-group layout)."""
     time_split(1)
