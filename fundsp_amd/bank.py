@@ -615,6 +615,26 @@ class Bank:
         check(lib().fdsp_bank_set_events(self._h, ev.ctypes.data_as(C.POINTER(C.c_double)),
                                          fd.ctypes.data_as(C.POINTER(C.c_int)), first, n))
 
+    # --- scores: a pool of voices, each playing one note after another (fdsp_bank_set_score)
+    def set_score(self, voice, start, end, fade_in=0.0, fade_out=0.0, fade=FADE_SMOOTH, params=None):
+        """A score of N notes: note k plays on voice[k] from start[k] to end[k] (seconds on the sequencer clock; fades and curve as in
+        set_events, scalars broadcast) as a FRESH unit with the voice's seed and parameters and `params` = {slot name: [N] f32 values}
+        written over the named slots.  The notes of a voice must not overlap (fundsp_amd.score.assign_voices allots voices); any order.
+        process_events / process_events_mix then play the score; an empty score removes it."""
+        voice = np.ascontiguousarray(np.atleast_1d(np.asarray(voice)), dtype=np.int32)
+        n = voice.size
+        ev = np.empty((n, 4), dtype=np.float64)
+        for k, x in enumerate((start, end, fade_in, fade_out)):
+            ev[:, k] = np.broadcast_to(np.asarray(x, dtype=np.float64), (n,))
+        fd = np.ascontiguousarray(np.broadcast_to(np.asarray(fade, dtype=np.int32), (n,)))
+        params = dict(params or {})
+        names = (C.c_char_p * max(len(params), 1))(*[k.encode() for k in params])
+        rows = np.empty((n, len(params)), dtype=np.float32)
+        for j, x in enumerate(params.values()):
+            rows[:, j] = np.broadcast_to(np.asarray(x, dtype=np.float32), (n,))
+        check(lib().fdsp_bank_set_score(self._h, n, voice.ctypes.data_as(C.POINTER(C.c_int)), ev.ctypes.data_as(C.POINTER(C.c_double)),
+                                        fd.ctypes.data_as(C.POINTER(C.c_int)), len(params), names, _fptr(rows)))
+
     def events_rewind(self, time=0.0):
         check(lib().fdsp_bank_events_rewind(self._h, float(time)))
 

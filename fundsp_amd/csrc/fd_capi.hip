@@ -25,6 +25,7 @@ thread_local std::string g_err;
 }
 namespace fd {
 std::string jit_source_mix(const std::string& type_expr, const std::string& prelude);  // fd_jit.hip: the second module of a run-time compiled graph
+std::string jit_source_score(const std::string& type_expr, const std::string& prelude);  // ... and the third: its score kernels
 int jit_compile_src(const std::string& src, const std::string& type_expr, std::vector<char>* code, std::string* log);
 const char* jit_compiler_origin();
 }  // namespace fd
@@ -426,6 +427,11 @@ struct fdsp_bank {
     std::vector<double> ev_host;
     bool ev_dirty = true;
     double ev_max_start = 0.0, ev_min_end = 0.0, ev_max_fade_in_end = 0.0, ev_min_fade_out_start = 0.0;
+    // a score (fdsp_bank_set_score): ONE device allocation -- ev[4][N] f64, then note_begin[V + 1], fade[N], param_slot[nparams] and
+    // params[nparams][N] -- and the pointers into it the kernels take; N = 0: no score
+    void* score_mem = nullptr;
+    size_t score_bytes = 0;
+    fd::ScoreData score{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     // fdsp_bank_process_host staging, grown on demand and kept: a real-time host calls once per 64-frame block
     float *st_in = nullptr, *st_out = nullptr;     // device
     float *pin_in = nullptr, *pin_out = nullptr;   // pinned host (small transfers only)
@@ -840,6 +846,8 @@ int fdsp_graph_check(const char* type_expr) {
     // must not fail there either
     code.clear();
     if (fd::jit_compile_src(fd::jit_source_mix(type_expr, ""), type_expr, &code, &log) != 0) return fail(FDSP_EINVAL, "second module (mix-down / time-split kernels): " + log);
+    code.clear();  // ... nor in the third, which fdsp_bank_set_score builds
+    if (fd::jit_compile_src(fd::jit_source_score(type_expr, ""), type_expr, &code, &log) != 0) return fail(FDSP_EINVAL, "third module (score kernels): " + log);
     return FDSP_OK;
 }
 
@@ -1204,6 +1212,7 @@ void fdsp_bank_destroy(fdsp_bank* b) {
     if (b->ring) hipFree(b->ring);
     if (b->ev) hipFree(b->ev);
     if (b->ev_fade) hipFree(b->ev_fade);
+    if (b->score_mem) hipFree(b->score_mem);
     if (b->mix_part) hipFree(b->mix_part);
     if (b->panw) hipFree(b->panw);
     if (b->st_in) hipFree(b->st_in);
@@ -1255,6 +1264,15 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
             if (e == hipSuccess) e = hipMemcpyAsync(b->ev, src->ev, 4 * src->stride * sizeof(double), hipMemcpyDeviceToDevice, b->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(b->ev_fade, src->ev_fade, src->stride * sizeof(int), hipMemcpyDeviceToDevice, b->stream);
             if (e != hipSuccess) return bail(e, "events");
+        }
+        if (src->score_mem) {  // the same layout at another address
+            e = hipMalloc(&b->score_mem, src->score_bytes);
+            if (e == hipSuccess) e = hipMemcpyAsync(b->score_mem, src->score_mem, src->score_bytes, hipMemcpyDeviceToDevice, b->stream);
+            if (e != hipSuccess) return bail(e, "score");
+            b->score_bytes = src->score_bytes;
+            auto moved = [&](const auto* p) { return reinterpret_cast<decltype(p)>((const char*)b->score_mem + ((const char*)p - (const char*)src->score_mem)); };
+            b->score = fd::ScoreData{moved(src->score.note_begin), moved(src->score.ev), moved(src->score.fade), moved(src->score.params),
+                                     moved(src->score.param_slot), src->score.N, src->score.nparams};
         }
         b->seq_time = src->seq_time;
         b->ev_host = src->ev_host;
@@ -1725,6 +1743,19 @@ int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t f
     return FDSP_OK;
 }
 
+namespace {
+int drop_score(fdsp_bank* b) {
+    if (!b->score_mem) return FDSP_OK;
+    HIPCHK(sync_bank_stream(b));
+    if (b->ext_pending && b->e1) HIPCHK(hipEventSynchronize(b->e1));  // a render on a caller's stream may still read it
+    HIPCHK(hipFree(b->score_mem));
+    b->score_mem = nullptr;
+    b->score_bytes = 0;
+    b->score = fd::ScoreData{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    return FDSP_OK;
+}
+}  // namespace
+
 int fdsp_bank_set_events(fdsp_bank* b, const double* events, const int* fade, size_t first, size_t count) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     if (int rc = render_only(b)) return rc;
@@ -1740,6 +1771,7 @@ int fdsp_bank_set_events(fdsp_bank* b, const double* events, const int* fade, si
         if (fade && fade[i] != FDSP_FADE_POWER && fade[i] != FDSP_FADE_SMOOTH) return fail(FDSP_EINVAL, "bad fade curve");
     }
     HIPCHK(await_last_render(b));
+    if (int rc = drop_score(b)) return rc;  // events replace a score
     if (!b->ev) {
         HIPCHK(hipMalloc((void**)&b->ev, 4 * b->stride * sizeof(double)));
         HIPCHK(hipMalloc((void**)&b->ev_fade, b->stride * sizeof(int)));
@@ -1770,6 +1802,112 @@ int fdsp_bank_set_events(fdsp_bank* b, const double* events, const int* fade, si
     return FDSP_OK;
 }
 
+int fdsp_bank_set_score(fdsp_bank* b, size_t notes, const int* voice, const double* events, const int* fade, int nparams,
+                        const char* const* names, const float* params) {
+    if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (b->fx) return fail(FDSP_EINVAL, "fdsp_bank_set_score: effect banks (reverb, network, resynthesizer, convolver) play no scores");
+    if (nparams < 0 || nparams > fd::SCORE_MAX_PARAMS)
+        return fail(FDSP_EINVAL, "fdsp_bank_set_score: nparams = " + std::to_string(nparams) + ", a score names 0 to " + std::to_string(fd::SCORE_MAX_PARAMS) + " slots");
+    if (notes > 0 && (!voice || !events)) return fail(FDSP_EINVAL, "fdsp_bank_set_score: voice or events is NULL");
+    if (nparams > 0 && (!names || (notes > 0 && !params))) return fail(FDSP_EINVAL, "fdsp_bank_set_score: names or params is NULL");
+    if (notes > (size_t)0x7fffffff) return fail(FDSP_EINVAL, "fdsp_bank_set_score: more than 2^31 - 1 notes");
+    DeviceGuard guard(b->device);
+    // ---- everything is checked before the bank is touched
+    std::vector<int> slot(nparams > 0 ? nparams : 0);
+    for (int j = 0; j < nparams; j++) {
+        const std::string name = names[j] ? names[j] : "(null)";
+        const int s = find_slot(b, names[j]);
+        if (s < 0) return fail(FDSP_EINVAL, "fdsp_bank_set_score: unknown slot: " + name);
+        // f32 parameter slots only.  SlotInfo carries no word type, so the integer words are told by name: the halves of a u64 field end in
+        // .lo / .hi (fdsp_bank_set_param_u64), and the u32 parameters of the inventory are the wave player's channel and loop points
+        const std::string field = name.substr(name.find(':') == std::string::npos ? 0 : name.find(':') + 1);
+        const bool half = name.size() > 3 && (name.compare(name.size() - 3, 3, ".lo") == 0 || name.compare(name.size() - 3, 3, ".hi") == 0);
+        const bool word = field == "channel" || field == "start_point" || field == "end_point" || field == "loop_point";
+        if (half || word || b->ops->slots[s].kind != fd::PARAM)
+            return fail(FDSP_EINVAL, "fdsp_bank_set_score: slot '" + name + "' is no f32 parameter (a score writes f32 parameter slots only)");
+        slot[j] = s;
+    }
+    for (size_t i = 0; i < notes; i++) {
+        const double* e = events + 4 * i;
+        const std::string nk = "note " + std::to_string(i);
+        if (voice[i] < 0 || (size_t)voice[i] >= b->V)
+            return fail(FDSP_EINVAL, "fdsp_bank_set_score: " + nk + ": voice " + std::to_string(voice[i]) + " is out of range (the bank has " + std::to_string(b->V) + " voices)");
+        const double duration = e[1] - e[0];
+        if (!(duration >= 0.0)) return fail(FDSP_EINVAL, "fdsp_bank_set_score: " + nk + " ends before it starts (or a time is NaN)");
+        if (!(e[2] <= duration && e[3] <= duration) || e[2] < 0.0 || e[3] < 0.0)  // Sequencer::push asserts (sequencer.rs:366-367)
+            return fail(FDSP_EINVAL, "fdsp_bank_set_score: " + nk + ": fade times must be >= 0 and may not exceed the note's duration");
+        if (fade && fade[i] != FDSP_FADE_POWER && fade[i] != FDSP_FADE_SMOOTH) return fail(FDSP_EINVAL, "fdsp_bank_set_score: " + nk + ": bad fade curve");
+    }
+    std::vector<size_t> order(notes);
+    for (size_t i = 0; i < notes; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t c) {
+        return voice[a] != voice[c] ? voice[a] < voice[c] : events[4 * a] < events[4 * c];
+    });
+    for (size_t i = 1; i < notes; i++) {
+        const size_t p = order[i - 1], q = order[i];
+        if (voice[p] == voice[q] && !(events[4 * p + 1] <= events[4 * q]))
+            return fail(FDSP_EINVAL, "fdsp_bank_set_score: note " + std::to_string(q) + " overlaps note " + std::to_string(p) + " on voice " + std::to_string(voice[q]) +
+                                         " (a voice plays one note at a time: end <= the next start)");
+    }
+    if (notes > 0 && b->ops->prepare_score) {  // run-time compiled kinds: the kernels are built now, never inside a render
+        std::string err;
+        if (!b->ops->prepare_score(&err)) return fail(FDSP_EDEVICE, "fdsp_bank_set_score: " + err);
+    }
+    // ---- one allocation: ev[4][N] f64 | note_begin[V + 1] | fade[N] | param_slot[nparams] | params[nparams][N]
+    const size_t N = notes, np = (size_t)nparams;
+    const size_t o_ev = 0, o_nb = o_ev + 4 * N * sizeof(double), o_fade = o_nb + (b->V + 1) * sizeof(int), o_slot = o_fade + N * sizeof(int),
+                 o_par = o_slot + np * sizeof(int), bytes = o_par + np * N * sizeof(float);
+    std::vector<char> host(bytes);
+    double* h_ev = reinterpret_cast<double*>(host.data() + o_ev);
+    int* h_nb = reinterpret_cast<int*>(host.data() + o_nb);
+    int* h_fade = reinterpret_cast<int*>(host.data() + o_fade);
+    int* h_slot = reinterpret_cast<int*>(host.data() + o_slot);
+    float* h_par = reinterpret_cast<float*>(host.data() + o_par);
+    for (size_t v = 0; v <= b->V; v++) h_nb[v] = 0;
+    for (size_t i = 0; i < N; i++) {
+        const size_t src = order[i];
+        for (int k = 0; k < 4; k++) h_ev[(size_t)k * N + i] = events[4 * src + k];
+        h_fade[i] = fade ? fade[src] : FDSP_FADE_SMOOTH;
+        for (size_t j = 0; j < np; j++) h_par[j * N + i] = params[src * np + j];
+        h_nb[voice[src] + 1]++;
+    }
+    for (size_t v = 0; v < b->V; v++) h_nb[v + 1] += h_nb[v];
+    for (size_t j = 0; j < np; j++) h_slot[j] = slot[j];
+    HIPCHK(await_last_render(b));
+    void* mem = nullptr;
+    if (N > 0) {
+        if (hipMalloc(&mem, bytes) != hipSuccess) return fail(FDSP_ENOMEM, "fdsp_bank_set_score: hipMalloc of " + std::to_string(bytes) + " bytes failed");
+        hipError_t e = hipMemcpyAsync(mem, host.data(), bytes, hipMemcpyHostToDevice, b->stream);
+        if (e == hipSuccess) e = sync_bank_stream(b);
+        if (e != hipSuccess) {
+            hipFree(mem);
+            return fail(FDSP_EDEVICE, std::string("fdsp_bank_set_score: upload: ") + hipGetErrorString(e));
+        }
+    }
+    // ---- the bank changes from here on: the score replaces whatever events or score it had
+    if (int rc = drop_score(b)) {
+        if (mem) hipFree(mem);
+        return rc;
+    }
+    if (b->ev) {
+        HIPCHK(sync_bank_stream(b));
+        hipFree(b->ev);
+        hipFree(b->ev_fade);
+        b->ev = nullptr;
+        b->ev_fade = nullptr;
+    }
+    b->ev_host.clear();
+    b->ev_dirty = true;
+    if (N > 0) {
+        const char* base = static_cast<const char*>(mem);
+        b->score_mem = mem;
+        b->score_bytes = bytes;
+        b->score = fd::ScoreData{reinterpret_cast<const int*>(base + o_nb), reinterpret_cast<const double*>(base + o_ev), reinterpret_cast<const int*>(base + o_fade),
+                                 reinterpret_cast<const float*>(base + o_par), reinterpret_cast<const int*>(base + o_slot), (int)N, nparams};
+    }
+    return FDSP_OK;
+}
+
 int fdsp_bank_events_rewind(fdsp_bank* b, double time) {
     if (!b) return fail(FDSP_EINVAL, "bank is NULL");
     b->seq_time = time;
@@ -1787,11 +1925,12 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
     DeviceGuard guard(b->device);
     if (frames == 0) return FDSP_OK;
     const bool mixing = d_out == nullptr;
-    if (!b->ev) return fail(FDSP_EINVAL, "no events set (fdsp_bank_set_events)");
+    const bool scored = b->score_mem != nullptr;  // a score plays instead of events
+    if (!b->ev && !scored) return fail(FDSP_EINVAL, "no events set (fdsp_bank_set_events) and no score (fdsp_bank_set_score)");
     if (!d_out && !d_mix) return fail(FDSP_EINVAL, mixing ? "d_mix is NULL" : "d_out is NULL");
     if (fdsp_bank_inputs(b) > 0 && !d_in) return fail(FDSP_EINVAL, "d_in is NULL but the graph has inputs");
     if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
-    if (mixing && !b->ops->render_events_mix)
+    if (mixing && !(scored ? (bool)b->ops->render_score_mix : (bool)b->ops->render_events_mix))
         return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' has no fused Sequencer mix: call fdsp_bank_process_events and fdsp_sum_voices");
     hipStream_t s = stream ? (hipStream_t)stream : b->stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1814,7 +1953,7 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
         for (size_t t0 = 0; t0 < frames; t0 += 64) t_end += sd * (double)(frames - t0 < 64 ? frames - t0 : 64);
     else
         for (size_t t = 0; t < frames; t++) t_end += sd;
-    if (b->ev_dirty) {
+    if (!scored && b->ev_dirty) {
         const double inf = std::numeric_limits<double>::infinity();
         b->ev_max_start = -inf; b->ev_min_end = inf; b->ev_max_fade_in_end = -inf; b->ev_min_fade_out_start = inf;
         for (size_t v = 0; v < b->V; v++) {
@@ -1829,14 +1968,17 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
     // Every voice inside its event for the whole launch and no fade running in any of its blocks (the kernel's own
     // per-block conditions, evaluated for the first and the last block): the scheduler's output is the units' plain
     // process / tick -- same arithmetic -- so the launch takes the (pipeline) render kernel.
-    const bool sustained = !b->ev_host.empty() && b->ev_max_start <= t_begin && b->ev_min_end >= t_end &&
+    const bool sustained = !scored && !b->ev_host.empty() && b->ev_max_start <= t_begin && b->ev_min_end >= t_end &&
                            b->ev_max_fade_in_end <= t_begin && b->ev_min_fade_out_start >= t_end;
     resolve_opts(b);
     if (mixing) {
         bool done = false;
         if (sustained && b->ops->render_mix)  // (the exact type: the voice scheduler renders exactly, like fdsp_bank_process_events)
             done = b->ops->render_mix(b->slots, b->stride, b->V, d_in, b->mix_part, frames, FDSP_MIX_SUM, mode, b->aux, b->ring, b->ring_cap, b->panw, s);
-        if (!done)
+        if (scored)
+            done = b->ops->render_score_mix(b->slots, b->stride, b->V, d_in, b->mix_part, frames, b->score, b->seq_time, b->sr, mode, b->aux, b->ring,
+                                            b->ring_cap, s);
+        else if (!done)
             done = b->ops->render_events_mix(b->slots, b->stride, b->V, d_in, b->mix_part, frames, b->ev, b->ev_fade, b->seq_time, b->sr, mode,
                                              b->aux, b->ring, b->ring_cap, s);
         if (!done) {
@@ -1844,7 +1986,9 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
             return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "': more than two outputs -- no fused Sequencer mix; call fdsp_bank_process_events and fdsp_sum_voices");
         }
         launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, s);
-    } else if (sustained)
+    } else if (scored)
+        b->ops->render_score(b->slots, b->stride, b->V, d_in, d_out, frames, b->score, b->seq_time, b->sr, mode, b->aux, b->ring, b->ring_cap, s);
+    else if (sustained)
         b->ops->render(b->slots, b->stride, b->V, d_in, d_out, frames, 0, FDSP_LAYOUT_VOICE_MINOR, mode, b->aux, b->ring,
                        b->ring_cap, s);
     else

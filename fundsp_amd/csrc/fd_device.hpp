@@ -19,6 +19,7 @@
 
 #include "fd_nodes.hpp"
 #include "fd_plan.hpp"  // LAYOUT_* / MODE_* / MIX_*, GraphTraits
+#include "fd_seq.hpp"   // the Sequencer's clock arithmetic (host + device)
 
 namespace fd {
 
@@ -840,18 +841,7 @@ __global__ __launch_bounds__(64 * WPB) void k_render(float* __restrict__ slots, 
 // over voices is fdsp_sum_voices.  Exactly as in the reference, a unit is processed in the part of each 64-frame
 // sequencer block that its event overlaps -- a SHORTER process() block at its start and end -- and the fade factors
 // are re-derived per block from the f64 clock and accumulated in f32 inside the block.
-FD_HD float smooth5f(float x) { return ((x * 6.0f - 15.0f) * x + 10.0f) * x * x * x; }
-FD_HD float sine_easef(float x) {  // Bhaskara's approximation, math.rs:453-458
-    constexpr float PI_F = (float)3.14159265358979323846, HALF_PI_F = (float)(3.14159265358979323846 * 0.5);
-    constexpr float D = (float)(5.0 * 3.14159265358979323846 * 3.14159265358979323846);
-    x = x * HALF_PI_F;
-    return 16.0f * x * (PI_F - x) / (D - 4.0f * x * (PI_F - x));
-}
-FD_HD float fade_at(int ease, float x) { return ease == 0 ? sine_easef(x) : smooth5f(x); }
-FD_HD long long round_index(double x) {  // `round(x) as usize`: half away from zero, negative / NaN -> 0
-    double r = __builtin_round(x);
-    return r > 0.0 ? (r < 4.0e18 ? (long long)r : (long long)4.0e18) : 0;
-}
+// (the clock arithmetic -- block windows, fade phases, Fade::at -- is fd_seq.hpp, shared with the score kernels below)
 
 // ---- fused mix-down ("mode B" of SURVEY.md 8(d): on-device reduction of the voices to [channels][frames]) ------------
 // The LAST stage of a voice group does not store its samples to HBM; it parks them in a small LDS tile
@@ -992,43 +982,13 @@ FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V,
         for (size_t t0 = 0; t0 < T; t0 += 64) {
             const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
             const double end_time = time + sd * (double)size;
-            const double threshold = end_time - sd * 0.5;                       // ready_to_active :586
-            bool act = e_start < threshold && !(e_end <= time + 0.5 * sd);      // :588, :861
-            long long start_index = e_start <= time ? 0 : round_index((e_start - time) * sample_rate);
-            long long end_index = size;
-            if (!(e_end >= end_time)) {
-                long long r = round_index((e_end - time) * sample_rate);
-                end_index = r < size ? r : size;
-            }
-            act = act && end_index > start_index;
+            const SeqBlock w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
+            const bool act = w.act, fin_on = w.fin_on, fout_on = w.fout_on;
+            const long long start_index = w.start_index, end_index = w.end_index, fin_end_i = w.fin_end_i, fout_i = w.fout_i;
             const int n = act ? (int)(end_index - start_index) : 0;
             const int full = n & ~7;
-            // fade_in :122-167
-            bool fin_on = false;
-            long long fin_end_i = 0;
-            float fin_cur = 0.0f, fin_d = 0.0f;
-            {
-                const double fade_end = e_start + e_fin;
-                if (act && e_fin > 0.0 && fade_end > time) {
-                    fin_on = true;
-                    fin_end_i = fade_end >= end_time ? end_index : round_index((fade_end - time) / sd);
-                    fin_cur = (float)(((time + (double)start_index * sd) - e_start) / (fade_end - e_start));
-                    fin_d = (float)(sd / e_fin);
-                }
-            }
-            // fade_out :169-216
-            bool fout_on = false;
-            long long fout_i = 0;
-            float fout_cur = 0.0f, fout_d = 0.0f;
-            {
-                const double fade_start = e_end - e_fout;
-                if (act && e_fout > 0.0 && fade_start < end_time) {
-                    fout_on = true;
-                    fout_i = fade_start <= time ? 0 : round_index((fade_start - time) / sd);
-                    fout_cur = (float)(((time + (double)fout_i * sd) - fade_start) / (e_end - fade_start));
-                    fout_d = (float)(sd / e_fout);
-                }
-            }
+            float fin_cur = w.fin_cur, fout_cur = w.fout_cur;
+            const float fin_d = w.fin_d, fout_d = w.fout_d;
             // Steady state -- every voice of the wave inside its event for the whole block, no fade running: the block is a
             // plain process(size) of the unit, so it takes the packed two-frame path of render_body (same arithmetic).
             const bool steady = act && start_index == 0 && end_index == size && !fin_on && !fout_on;
@@ -1168,6 +1128,250 @@ __global__ __launch_bounds__(256) void k_render_events(float* __restrict__ slots
                                                       double time0, double sample_rate, const void* aux, float* ring,
                                                       uint32_t ring_cap) {
     render_events_body<G, MODE>(slots, stride, V, in, out, T, ev, fade, time0, sample_rate, aux, ring, ring_cap);
+}
+
+// ---- scores: a pool of voices, each playing one note after another (fdsp_bank_set_score) ---------------------------------
+// The Sequencer with MANY events per voice: lane = voice, and the lane walks its voice's notes (fd_seq.hpp ScoreData; sorted,
+// end_k <= start_{k+1}, so their frame windows never overlap).  Note k plays exactly like a Sequencer event whose unit is a
+// fresh unit with the voice's hash and parameters and the note's row written over the named slots: in the first block (tick)
+// in which the note is active the lane writes the row into its node, runs update(sr) and reset() -- what lifecycle ops 1 and 2
+// do.  Where a voice stands is a function of the clock alone (seq_first_live / seq_note_begun): nothing but the clock carries
+// over between launches, a note that straddles a launch boundary continues with the state it has.  Parameters and
+// coefficients therefore go back to the slots with the state at the end of the launch.
+// A block in which every lane of the wave is inside its current note for the whole block, no fade running, takes the packed
+// two-frame path like render_events_body; in any other block the wave goes frame by frame and a lane may finish note k and start
+// notes k+1, k+2 ... -- each with its own begin_block(n) -- with +0.0 between them.
+struct VSetRow {  // counts slots like VLoad / VStore and overwrites the score's
+    const float* params;
+    const int* param_slot;
+    int nparams;
+    size_t N, note;
+    int slot;
+    FD_D void put(float& x) {
+        for (int j = 0; j < nparams; j++)
+            if (param_slot[j] == slot) x = params[(size_t)j * N + note];
+        slot++;
+    }
+    FD_D void f(float& x, FieldKind, const char*) { put(x); }
+    FD_D void fi(float& x, FieldKind, const char*, int) { put(x); }
+    FD_D void u32(uint32_t&, FieldKind, const char*) { slot++; }
+    FD_D void u64(uint64_t&, FieldKind, const char*) { slot += 2; }
+    FD_D void enter(int) {}
+    FD_D void leave() {}
+};
+
+template <class G, int MODE, bool MIXE = false>
+FD_D void render_score_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
+                            float* __restrict__ out, size_t T, const ScoreData sc, double time0, double sample_rate,
+                            const void* aux, float* ring, uint32_t ring_cap) {
+    constexpr int NI = G::IN, NO = G::OUT;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t v0 = ((size_t)blockIdx.x * 4 + wib) * 64;
+    const size_t v = v0 + lane;
+    if (v0 >= stride) return;
+    const bool voice = v < V;
+    if (!MIXE && !voice) return;
+    __shared__ __attribute__((aligned(16))) float etile[MIXE ? 4 : 1][MIXE ? NO * 64 * MIX_ROW : 4];
+    float* tile = &etile[MIXE ? wib : 0][0];
+    float* part = MIXE ? out + (v0 / 64) * (size_t)NO * T : nullptr;  // this group's partial mix [channel][T]
+    G g;
+    Ctx ctx{static_cast<const Aux*>(aux), ring + v, ring_cap, stride, 0};
+    g.bind(ctx);
+    {
+        VLoad ld{slots + v, stride, 0};
+        g.visit(ld);
+    }
+    const double inf_ = __builtin_huge_val();
+    const double sd = 1.0 / sample_rate;  // Sequencer::set_sample_rate :752-753
+    const size_t N = (size_t)sc.N;
+    const int ne = voice ? sc.note_begin[v + 1] : 0;  // a padded voice of the last group has no notes
+    int k = voice ? seq_first_live(sc.ev + N, sc.note_begin[v], ne, time0, sd) : 0;
+    double e_start, e_end, e_fin, e_fout;
+    int ease;
+    auto load_note = [&](int j) {  // the lane's current note; behind the voice's last one: a note that never plays
+        const bool on = j < ne;
+        e_start = on ? sc.ev[j] : inf_;
+        e_end = on ? sc.ev[N + j] : -inf_;
+        e_fin = on ? sc.ev[2 * N + j] : 0.0;
+        e_fout = on ? sc.ev[3 * N + j] : 0.0;
+        ease = on ? sc.fade[j] : 1;
+    };
+    auto begin_note = [&](int j) {  // a fresh unit with the note's parameters
+        VSetRow row{sc.params, sc.param_slot, sc.nparams, N, (size_t)j, 0};
+        g.visit(row);
+        g.update(sample_rate);
+        g.reset();
+    };
+    load_note(k);
+    double time = time0;
+    const float* inv = in + v;
+    float* outv = out + v;
+    auto put = [&](int c, size_t t, float x) {  // frame t of the launch, channel c
+        if constexpr (MIXE) tile[(c * 64 + (int)(t & 63)) * MIX_ROW + lane] = x;
+        else outv[((size_t)c * T + t) * V] = x;
+    };
+    if (MODE == MODE_PROCESS) {
+        for (size_t t0 = 0; t0 < T; t0 += 64) {
+            const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
+            const double end_time = time + sd * (double)size;
+            while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
+            SeqBlock w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
+            // Steady state -- every voice of the wave inside a note it has begun, for the whole block, no fade running
+            const bool steady = w.act && w.start_index == 0 && w.end_index == size && !w.fin_on && !w.fout_on && seq_note_begun(e_start, time, sd);
+            if (__builtin_amdgcn_ballot_w64(steady) == __builtin_amdgcn_ballot_w64(true)) {
+                const int full = size & ~7;
+                g.begin_block(size);
+                const G snap = g;
+                for (int i = 0; i < full; i += 2) {
+                    const size_t t = t0 + i;
+                    v2f pi[NI > 0 ? NI : 1], po[NO];
+#pragma unroll
+                    for (int c = 0; c < NI; c++) pi[c] = v2f{inv[((size_t)c * T + t) * V], inv[((size_t)c * T + t + 1) * V]};
+                    g.template step2<PH_SIMD>(pi, po);
+#pragma unroll
+                    for (int c = 0; c < NO; c++) {
+                        put(c, t, po[c].x);
+                        put(c, t + 1, po[c].y);
+                    }
+                }
+                if (__builtin_expect(g.tripped(), 0)) {  // a packed-path shortcut left its exact domain: redo the block
+                    g = snap;
+                    for (int i = 0; i < full; i++) {
+                        const size_t t = t0 + i;
+                        float fi[NI > 0 ? NI : 1], fo[NO];
+#pragma unroll
+                        for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
+                        g.template step<PH_SIMD>(fi, fo);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) put(c, t, fo[c]);
+                    }
+                }
+                g.end_simd();
+                for (int i = full; i < size; i++) {
+                    const size_t t = t0 + i;
+                    float fi[NI > 0 ? NI : 1], fo[NO];
+#pragma unroll
+                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
+                    g.template step<PH_REM>(fi, fo);
+#pragma unroll
+                    for (int c = 0; c < NO; c++) put(c, t, fo[c]);
+                }
+                if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
+                time = end_time;
+                continue;
+            }
+            // Frame by frame, the wave in step: a lane crosses from one note to the next where its window ends.  [si, ei) is the window of the
+            // lane's current note in this block (empty: the note does not play in it); behind it the NEXT note joins the block only if it is
+            // ready in it -- then the current one is over by the next block, so the lane's one set of note registers can move on.
+            int si = w.act ? (int)w.start_index : 0, ei = w.act ? (int)w.end_index : 0, full = 0;
+            bool look = true;
+            float fin_cur = 0.0f, fout_cur = 0.0f;
+            for (int i = 0; i < size; i++) {
+                const size_t t = t0 + i;
+                while (look && i >= ei) {
+                    const double next_start = k + 1 < ne ? sc.ev[k + 1] : inf_;
+                    look = seq_note_ready(next_start, end_time, sd);
+                    if (!look) break;
+                    load_note(++k);
+                    w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
+                    si = w.act ? (int)w.start_index : 0;
+                    ei = w.act ? (int)w.end_index : 0;
+                }
+                float fo[NO];
+#pragma unroll
+                for (int c = 0; c < NO; c++) fo[c] = 0.0f;
+                if (i >= si && i < ei) {
+                    if (i == si) {  // the note's own process() block begins
+                        if (!seq_note_begun(e_start, time, sd)) begin_note(k);
+                        full = (ei - si) & ~7;
+                        g.begin_block(ei - si);
+                        if (full == 0) g.end_simd();
+                        fin_cur = w.fin_cur;
+                        fout_cur = w.fout_cur;
+                    }
+                    const int kk = i - si;  // index in the note's own sub-block buffer
+                    float fi[NI > 0 ? NI : 1];
+#pragma unroll
+                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
+                    if (kk < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
+                    if (kk + 1 == full) g.end_simd();
+                    if (w.fin_on && kk < w.fin_end_i) {
+                        const float e = fade_at(ease, fin_cur);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                        fin_cur += w.fin_d;
+                    }
+                    if (w.fout_on && kk >= w.fout_i && kk < w.end_index) {
+                        const float e = fade_at(ease, 1.0f - fout_cur);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                        fout_cur += w.fout_d;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NO; c++) put(c, t, fo[c]);
+            }
+            if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
+            time = end_time;
+        }
+    } else {
+        for (size_t t = 0; t < T; t++) {  // Sequencer::tick :769-836
+            const double end_time = time + sd;
+            while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
+            const bool act = seq_note_ready(e_start, end_time, sd) && !seq_note_over(e_end, time, sd);
+            float fo[NO];
+#pragma unroll
+            for (int c = 0; c < NO; c++) fo[c] = 0.0f;
+            if (act) {
+                if (!seq_note_begun(e_start, time, sd)) begin_note(k);
+                float fi[NI > 0 ? NI : 1];
+#pragma unroll
+                for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
+                g.template step<PH_TICK>(fi, fo);
+                if (e_fin > 0.0) {
+                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
+                    if (f < 1.0f) {
+                        const float e = fade_at(ease, f);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                    }
+                }
+                if (e_fout > 0.0) {
+                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
+                    if (f > 0.0f) {
+                        const float e = fade_at(ease, 1.0f - f);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NO; c++) put(c, t, fo[c]);
+            if constexpr (MIXE) {
+                if ((t & 63) == 63 || t + 1 == T) mix_flush<NO, 64>(tile, part + (t & ~(size_t)63), T, (int)(t & 63) + 1, lane);
+            }
+            time = end_time;
+        }
+    }
+    if (voice) {  // everything: a note's row and the coefficients derived from it belong to the note that goes on in the next launch
+        VStore<true> st{slots + v, stride, 0};
+        g.visit(st);
+    }
+}
+
+template <class G, int MODE>
+__global__ __launch_bounds__(256) void k_render_score_mix(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
+                                                         float* __restrict__ part, size_t T, const ScoreData sc, double time0,
+                                                         double sample_rate, const void* aux, float* ring, uint32_t ring_cap) {
+    static_assert(G::OUT * 64 * MIX_ROW * 4 * 4 <= 160 * 1024, "the block tiles of four waves must fit the CU's LDS");
+    render_score_body<G, MODE, true>(slots, stride, V, in, part, T, sc, time0, sample_rate, aux, ring, ring_cap);
+}
+template <class G, int MODE>
+__global__ __launch_bounds__(256) void k_render_score(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
+                                                     float* __restrict__ out, size_t T, const ScoreData sc, double time0,
+                                                     double sample_rate, const void* aux, float* ring, uint32_t ring_cap) {
+    render_score_body<G, MODE>(slots, stride, V, in, out, T, sc, time0, sample_rate, aux, ring, ring_cap);
 }
 
 #ifdef FD_PIPE_WPE        // A/B switch: tell the compiler how many waves per SIMD the pipeline kernel runs with
@@ -2675,6 +2879,11 @@ FD_D void jit_events_mix_body(float* __restrict__ slots, size_t stride, size_t V
                               const double* __restrict__ ev, const int* __restrict__ fade, double time0, double sr, const void* aux, float* ring,
                               uint32_t ring_cap) {
     if constexpr (G::OUT <= 2) render_events_body<G, MODE, true>(slots, stride, V, in, part, T, ev, fade, time0, sr, aux, ring, ring_cap);
+}
+template <class G, int MODE>
+FD_D void jit_score_mix_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ part, size_t T,
+                             const ScoreData sc, double time0, double sr, const void* aux, float* ring, uint32_t ring_cap) {
+    if constexpr (G::OUT <= 2) render_score_body<G, MODE, true>(slots, stride, V, in, part, T, sc, time0, sr, aux, ring, ring_cap);
 }
 template <class G, int MODE>
 FD_D void jit_pipe_planar_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,

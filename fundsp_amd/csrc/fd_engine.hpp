@@ -84,6 +84,17 @@ struct KindOps {
                        const int* fade, double time0, double sr, int mode, const void* aux, float* ring,
                        uint32_t ring_cap, hipStream_t s)>
         render_events;
+    // ... and scores (fd_device.hpp render_score_body, fdsp_bank_set_score): sc = the score on the device; the mix variant like
+    // render_events_mix (false / empty: more than two outputs, or a kind built without the mix kernels)
+    std::function<void(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const ScoreData& sc, double time0,
+                       double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s)>
+        render_score;
+    std::function<bool(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const ScoreData& sc, double time0,
+                       double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s)>
+        render_score_mix;
+    // whatever the score kernels of this kind still need before their first launch (run-time compiled graphs: compile and load
+    // them) -- called by fdsp_bank_set_score, never by a render; false + *err: they cannot be built.  Empty for ahead-of-time kinds.
+    std::function<bool(std::string* err)> prepare_score;
 };
 
 template <class G>
@@ -236,6 +247,24 @@ bool launch_render_events_mix(float* slots, size_t stride, size_t V, const float
         return false;
     }
 }
+template <class G>
+bool launch_render_score_mix(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const ScoreData& sc, double time0,
+                             double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
+    if (V == 0 || T == 0) return true;
+    if constexpr (G::OUT <= 2) {
+        tl_opts.last_kernel = LK_SCORE;
+        const unsigned grid = (unsigned)(((V + 63) / 64 + 3) / 4);
+        if (mode == MODE_PROCESS)
+            hipLaunchKernelGGL((k_render_score_mix<G, MODE_PROCESS>), dim3(grid), dim3(256), 0, s, slots, stride, V, in, part, T, sc, time0, sr,
+                               aux, ring, ring_cap);
+        else
+            hipLaunchKernelGGL((k_render_score_mix<G, MODE_TICK>), dim3(grid), dim3(256), 0, s, slots, stride, V, in, part, T, sc, time0, sr,
+                               aux, ring, ring_cap);
+        return true;
+    } else {
+        return false;
+    }
+}
 // gives a kind its fused mix-down kernels (opt-in per kind: every instantiation is compile time and code size)
 template <class G>
 void attach_mix(std::vector<KindOps>& kinds, const char* name) {
@@ -243,6 +272,7 @@ void attach_mix(std::vector<KindOps>& kinds, const char* name) {
         if (k.name == name) {
             k.render_mix = &launch_render_mix<G>;
             k.render_events_mix = &launch_render_events_mix<G>;
+            k.render_score_mix = &launch_render_score_mix<G>;
             using GF = typename FastOf<G>::type;
             if constexpr (!SameType<GF, G>::v) k.render_mix_fast = &launch_render_mix<GF>;
         }
@@ -264,6 +294,20 @@ void launch_render_events(float* slots, size_t stride, size_t V, const float* in
 }
 
 template <class G>
+void launch_render_score(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const ScoreData& sc, double time0,
+                         double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
+    if (V == 0 || T == 0) return;
+    tl_opts.last_kernel = LK_SCORE;
+    const unsigned grid = (unsigned)(((V + 63) / 64 + 3) / 4);
+    if (mode == MODE_PROCESS)
+        hipLaunchKernelGGL((k_render_score<G, MODE_PROCESS>), dim3(grid), dim3(256), 0, s, slots, stride, V, in, out, T, sc, time0, sr, aux,
+                           ring, ring_cap);
+    else
+        hipLaunchKernelGGL((k_render_score<G, MODE_TICK>), dim3(grid), dim3(256), 0, s, slots, stride, V, in, out, T, sc, time0, sr, aux,
+                           ring, ring_cap);
+}
+
+template <class G>
 KindOps make_kind(const char* name) {
     KindOps k;
     k.name = name;
@@ -278,6 +322,7 @@ KindOps make_kind(const char* name) {
     using GF = typename FastOf<G>::type;
     if constexpr (!SameType<GF, G>::v) k.render_fast = &launch_render<GF>;
     k.render_events = &launch_render_events<G>;
+    k.render_score = &launch_render_score<G>;
     return k;
 }
 

@@ -30,6 +30,7 @@ namespace fd {
 
 int jit_compile_src(const std::string& src, const std::string& type_expr, std::vector<char>* code, std::string* log);
 std::string jit_source_mix(const std::string& type_expr, const std::string& prelude);
+std::string jit_source_score(const std::string& type_expr, const std::string& prelude);
 
 namespace {
 
@@ -136,6 +137,7 @@ const Rtc& rtc() {
 }
 
 struct JitMix;
+struct JitScore;
 
 // One compiled graph: the code object plus, per HIP device, the module loaded on it (hipModule_t belongs to a device;
 // a process may keep banks of the same kind on several GPUs, fdsp_bank_create_on).  Loaded lazily under a mutex.
@@ -164,6 +166,10 @@ struct JitModule {
     std::shared_ptr<JitMix> mix[2];
     bool mix_failed[2] = {false, false};
     std::mutex mix_mu;
+    // the score kernels (fdsp_bank_set_score), compiled when a bank of the kind first gets a score
+    std::shared_ptr<JitScore> score;
+    std::string score_error;
+    std::mutex score_mu;
     ~JitModule() {  // a module is unloaded with ITS device current (it was loaded on that device's context)
         int prev = -1;
         const bool have_prev = hipGetDevice(&prev) == hipSuccess;
@@ -255,6 +261,37 @@ struct JitMix {
                 const std::string fm = "jit_ts3_mix_g" + std::to_string(g + 1) + "_" + std::to_string(x + 1);
                 ok = hipModuleGetFunction(&f.tsm[g][x], f.mod, fm.c_str()) == hipSuccess;
             }
+        }
+        if (!ok) { hipModuleUnload(f.mod); f.mod = nullptr; return nullptr; }
+        return &f;
+    }
+};
+
+// The score kernels of a compiled graph (jit_score_<mode>, and jit_score_mix_<mode> for graphs of at most two outputs): a module of their
+// own, like JitMix
+struct JitScore {
+    std::vector<char> code;
+    std::mutex mu;
+    struct Dev { hipModule_t mod = nullptr; hipFunction_t fn[2] = {nullptr, nullptr}; hipFunction_t mix[2] = {nullptr, nullptr}; bool loaded = false; } dev[JitModule::MAXD];
+    ~JitScore() {
+        int prev = -1;
+        const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+        for (int d = 0; d < JitModule::MAXD; d++)
+            if (dev[d].loaded && dev[d].mod && hipSetDevice(d) == hipSuccess) hipModuleUnload(dev[d].mod);
+        if (have_prev) hipSetDevice(prev);
+    }
+    const Dev* get() {
+        int d = 0;
+        if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= JitModule::MAXD) return nullptr;
+        std::lock_guard<std::mutex> lock(mu);
+        Dev& f = dev[d];
+        if (f.loaded) return f.mod ? &f : nullptr;
+        f.loaded = true;
+        if (hipModuleLoadData(&f.mod, code.data()) != hipSuccess) { f.mod = nullptr; return nullptr; }
+        bool ok = true;
+        for (int m = 0; m < 2 && ok; m++) {
+            ok = hipModuleGetFunction(&f.fn[m], f.mod, ("jit_score_" + std::to_string(m)).c_str()) == hipSuccess;
+            ok = ok && hipModuleGetFunction(&f.mix[m], f.mod, ("jit_score_mix_" + std::to_string(m)).c_str()) == hipSuccess;
         }
         if (!ok) { hipModuleUnload(f.mod); f.mod = nullptr; return nullptr; }
         return &f;
@@ -431,6 +468,26 @@ std::string jit_source_mix(const std::string& type_expr, const std::string& prel
     return s;
 }
 
+// the score kernels of a graph (fdsp_bank_set_score): a module of their own, compiled when a bank of the kind first gets a score
+std::string jit_source_score(const std::string& type_expr, const std::string& prelude) {
+    std::string s;
+    s += "#include \"fd_device.hpp\"\n";
+    if (!prelude.empty()) s += "namespace fd {\n" + prelude + "\n}\n";
+    s += "namespace fd { using JitG = " + type_expr + "; }\nusing fd::JitG;\n";
+    for (int mode = 0; mode < 2; mode++) {
+        std::string m = std::to_string(mode);
+        s += "extern \"C\" __global__ __launch_bounds__(256) void jit_score_" + m +
+             "(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ out, "
+             "size_t T, const fd::ScoreData sc, double time0, double sr, const void* aux, float* ring, uint32_t cap) {\n"
+             "  fd::render_score_body<JitG, " + m + ">(slots, stride, V, in, out, T, sc, time0, sr, aux, ring, cap); }\n";
+        s += "extern \"C\" __global__ __launch_bounds__(256) void jit_score_mix_" + m +
+             "(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ part, "
+             "size_t T, const fd::ScoreData sc, double time0, double sr, const void* aux, float* ring, uint32_t cap) {\n"
+             "  fd::jit_score_mix_body<JitG, " + m + ">(slots, stride, V, in, part, T, sc, time0, sr, aux, ring, cap); }\n";  // (more than two outputs: an empty body)
+    }
+    return s;
+}
+
 // Compile only (no device needed): returns the code object or an error log.
 int jit_compile_code(const std::string& type_expr, const std::string& prelude, std::vector<char>* code, std::string* log) {
     return jit_compile_src(jit_source(type_expr, prelude), type_expr, code, log);
@@ -472,8 +529,8 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
             }
         }
     }
-    static const char* const names[5] = {"fd_math.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_plan.hpp", "fd_opts.hpp"};
-    return compile_program(src, "graph type `" + type_expr + "`", names, 5, ftz, wide_ilp, code, log);
+    static const char* const names[6] = {"fd_math.hpp", "fd_seq.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_plan.hpp", "fd_opts.hpp"};
+    return compile_program(src, "graph type `" + type_expr + "`", names, 6, ftz, wide_ilp, code, log);
 }
 
 // The process module of a resynthesizer bank's closure (fd_resynth_fn.hpp): the functor's source in namespace fd and rs_process around it.
@@ -695,6 +752,42 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
             void* args[] = {&slots, &stride, &V, &in, &part, &T, &ev, &fade, &time0, &sr, &aux, &ring, &ring_cap};
             hipModuleLaunchKernel(f->ev[mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, 256, 1, 1, 0, s, args, nullptr);
             tl_opts.last_kernel = LK_EVENTS;
+            return true;
+        };
+    // scores: the third module, built by fdsp_bank_set_score (prepare_score); a render only looks it up
+    auto score_module = [jm](bool build, std::string* err) -> const JitScore::Dev* {
+        std::lock_guard<std::mutex> lock(jm->score_mu);
+        if (!jm->score && build && jm->score_error.empty()) {
+            auto sm = std::make_shared<JitScore>();
+            std::string log;
+            if (jit_compile_src(jit_source_score(jm->type_expr, jm->prelude), jm->type_expr, &sm->code, &log) == 0) jm->score = sm;
+            else jm->score_error = "the score kernels of this graph failed to compile: " + log;
+        }
+        const JitScore::Dev* f = jm->score ? jm->score->get() : nullptr;
+        if (!f && err) *err = jm->score ? "the score kernels of this graph could not be loaded on this device" : jm->score_error;
+        return f;
+    };
+    out->prepare_score = [score_module](std::string* err) { return score_module(true, err) != nullptr; };
+    out->render_score = [score_module](float* slots, size_t stride, size_t V, const float* in, float* outp, size_t T, const ScoreData& sc,
+                                       double time0, double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
+        if (V == 0 || T == 0) return;
+        const JitScore::Dev* f = score_module(false, nullptr);
+        if (!f) return jit_launch_failed();
+        ScoreData scv = sc;
+        void* args[] = {&slots, &stride, &V, &in, &outp, &T, &scv, &time0, &sr, &aux, &ring, &ring_cap};
+        hipModuleLaunchKernel(f->fn[mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, 256, 1, 1, 0, s, args, nullptr);
+        tl_opts.last_kernel = LK_SCORE;
+    };
+    if (traits.nout <= 2)
+        out->render_score_mix = [score_module](float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const ScoreData& sc,
+                                               double time0, double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) -> bool {
+            if (V == 0 || T == 0) return true;
+            const JitScore::Dev* f = score_module(false, nullptr);
+            if (!f) { jit_launch_failed(); return true; }
+            ScoreData scv = sc;
+            void* args[] = {&slots, &stride, &V, &in, &part, &T, &scv, &time0, &sr, &aux, &ring, &ring_cap};
+            hipModuleLaunchKernel(f->mix[mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, 256, 1, 1, 0, s, args, nullptr);
+            tl_opts.last_kernel = LK_SCORE;
             return true;
         };
     out->render_events = [jm](float* slots, size_t stride, size_t V, const float* in, float* outp, size_t T,

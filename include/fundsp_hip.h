@@ -127,7 +127,8 @@ int fdsp_bank_get_option(const fdsp_bank* bank, const char* name);
  * the pair -- a real-time host rendering one 64-frame block per call saves two event records per launch.
  * fdsp_bank_get_option(bank, "last_kernel") (read-only): the kernel family the most recent render launch took --
  * 1 single-wave, 2 pipeline, 3 planar pipeline, 4 time-split, 5 voice scheduler, 6 / 7 reverb lane-per-frame / -line,
- * 8 the chain of waves that renders a wide sum of generators (sumi / busi of >= 8 oscillators) on a small bank. */
+ * 8 the chain of waves that renders a wide sum of generators (sumi / busi of >= 8 oscillators) on a small bank,
+ * 9 the voice scheduler playing a score (fdsp_bank_set_score). */
 /* fdsp_bank_get_option(bank, "has_fused_mix") (read-only): 1 if fdsp_bank_process_mix has kernels for the bank's kind (voice banks), or
  * the bank is a reverb / network bank (their mix-down renders into a scratch: "the stereo mix-down" below); 0 for resynthesizer and convolver banks. */
 /* "fx_mix_chunk_frames" (default 0 = automatic, from a 256 MiB budget): frames per chunk of the mix scratch of a reverb / network bank, a
@@ -479,7 +480,7 @@ int fdsp_bank_last_kernel_ms(fdsp_bank* bank, float* ms);
 int fdsp_bank_set_ring(fdsp_bank* bank, int ring_index, const float* data, size_t frames, size_t first_voice,
                        size_t count);
 
-/* ---- on-device voice scheduler: the reference's Sequencer with one event per voice ---------------------------
+/* ---- on-device voice scheduler: the reference's Sequencer with one event per voice (many: "scores" below) ------
  * Replaces Sequencer::push + process / tick (src/sequencer.rs:355-398, 838-951, 769-836; ReplayMode::None, no loop
  * point) for a bank whose voices are the events' units.  `events` holds 4 doubles per voice -- start_time, end_time,
  * fade_in_time, fade_out_time, seconds on the sequencer clock -- and `fade` the curve per voice (NULL = Smooth).
@@ -500,6 +501,29 @@ int fdsp_bank_process_events(fdsp_bank* bank, size_t frames, const float* d_in, 
  * fdsp_bank_process_events' output bit for bit; the per-event samples never exist in HBM.  Graphs of at most two outputs whose kind
  * has the fused kernels (FDSP_ENOTSUP otherwise); the clock advances as in fdsp_bank_process_events. */
 int fdsp_bank_process_events_mix(fdsp_bank* bank, size_t frames, const float* d_in, float* d_mix, int mode, void* stream);
+/* ---- scores: many notes per voice ------------------------------------------------------------------------------
+ * A pool of voices that each play one note after another, scheduled on the device, sample-exact, in one launch: the cost is
+ * voices x frames however many notes the score has.  Note k has a voice index voice[k] < voices, four doubles events[4 k ..] =
+ * start, end, fade_in, fade_out (seconds on the sequencer clock, the rules of Sequencer::push), a fade curve (fade == NULL:
+ * FDSP_FADE_SMOOTH) and a row params[nparams k ..] of f32 values for the `nparams` (0 .. 16) per-voice f32 slots `names`.
+ * The notes of one voice must not overlap (end <= next start after sorting by start; legato and several notes inside one
+ * 64-frame block are fine); the input may come in any order.
+ * Note k on voice v plays exactly like a Sequencer event whose unit is a FRESH unit of the bank's graph with voice v's hash
+ * and voice v's parameters as they stand, the note's row written over the named slots: in the first block (tick) in which
+ * the note is active the device writes the row, runs update(sample rate) and reset() -- delay rings and hashed nodes
+ * included.  Everything else is the scheduler above: 64-frame blocks, the shorter first and last process() block of each
+ * note, fades per block from the f64 clock, FDSP_MODE_TICK, always the exact arithmetic.
+ * Where a voice stands is a function of the clock alone: its current note at clock t is the first with end > t + half a
+ * sample, and a note has begun iff start < t - half a sample.  So fdsp_bank_events_rewind keeps its meaning and a note that
+ * straddles a launch boundary (or a rewind) continues with the state the voice has.
+ * Everything is validated before the bank is touched (FDSP_EINVAL names the offending note or slot).  The score replaces
+ * any events or score of the bank; notes == 0 removes it, and so does fdsp_bank_set_events afterwards.  With a score
+ * installed fdsp_bank_process_events and fdsp_bank_process_events_mix play it: output layout, clock, capture rules and the
+ * fdsp_bank_mix_reserve requirement are unchanged; "last_kernel" reads 9.  Run-time compiled kinds build their score kernels
+ * here, never inside a render.  The slots named in the score keep the last started note's values afterwards.  Effect banks
+ * answer FDSP_EINVAL; fdsp_bank_clone copies the score. */
+int fdsp_bank_set_score(fdsp_bank* bank, size_t notes, const int* voice, const double* events, const int* fade, int nparams,
+                        const char* const* names, const float* params);
 int fdsp_bank_events_rewind(fdsp_bank* bank, double time); /* set the sequencer clock (Sequencer::reset -> 0.0) */
 double fdsp_bank_events_time(const fdsp_bank* bank);       /* Sequencer::time() */
 

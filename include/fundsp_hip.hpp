@@ -707,6 +707,16 @@ class Bank {
     void process_events_mix(size_t frames, const float* d_in, float* d_mix, int mode = FDSP_MODE_PROCESS, void* stream = nullptr) {
         check(fdsp_bank_process_events_mix(h_, frames, d_in, d_mix, mode, stream));
     }
+    // ... and with many notes per voice (fundsp_hip.h "scores"): note k plays on voice[k] from events_x4[4 k ..] = start, end, fade_in,
+    // fade_out as a fresh unit with the voice's hash and parameters and params[k * names.size() ..] written over the f32 slots `names`;
+    // process_events / process_events_mix then play the score.  An empty score removes it.
+    void set_score(const std::vector<int>& voice, const std::vector<double>& events_x4, const std::vector<std::string>& names = {},
+                   const std::vector<float>& params = {}, const int* fade = nullptr) {
+        if (events_x4.size() != 4 * voice.size() || params.size() != names.size() * voice.size()) throw Error(FDSP_EINVAL, "set_score: voice, events and params must describe the same notes");
+        std::vector<const char*> ptrs;
+        for (const std::string& n : names) ptrs.push_back(n.c_str());
+        check(fdsp_bank_set_score(h_, voice.size(), voice.data(), events_x4.data(), fade, (int)names.size(), ptrs.data(), params.data()));
+    }
     void events_rewind(double time) { check(fdsp_bank_events_rewind(h_, time)); }
     double events_time() const { return fdsp_bank_events_time(h_); }
 

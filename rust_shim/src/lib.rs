@@ -152,6 +152,8 @@ pub mod ffi {
         pub fn fdsp_bank_process_mix_planar(bank: *mut FdspBank, frames: usize, d_in: *const f32, frame_stride: usize, d_mix: *mut f32, mix: c_int,
                                             mode: c_int, stream: *mut c_void) -> c_int; // effect banks: the same from a planar input
         pub fn fdsp_bank_process_events_mix(bank: *mut FdspBank, frames: usize, d_in: *const f32, d_mix: *mut f32, mode: c_int, stream: *mut c_void) -> c_int; // Sequencer output
+        pub fn fdsp_bank_set_score(bank: *mut FdspBank, notes: usize, voice: *const c_int, events: *const f64, fade: *const c_int, nparams: c_int,
+                                   names: *const *const c_char, params: *const f32) -> c_int; // many notes per voice
         pub fn fdsp_bank_set_pan(bank: *mut FdspBank, pan: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_mix_reserve(bank: *mut FdspBank, frames: usize) -> c_int; // AudioNode::allocate for the mix path
         pub fn fdsp_bank_synchronize(bank: *mut FdspBank) -> c_int;
@@ -557,6 +559,22 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
     /// Pan position (-1 .. 1) per voice for `render_mix(.., pan = true, ..)`; every voice starts in the centre (`pan(0.0)`).
     pub fn set_pan(&mut self, pan: &[f32]) -> Result<(), String> {
         check(unsafe { fdsp_bank_set_pan(self.bank, pan.as_ptr(), 0, pan.len()) })
+    }
+
+    /// A score for the pool of voices (`Sequencer::push` once per note, `include/fundsp_hip.h` "scores"): note `k` plays on `voice[k]` from
+    /// `events[k] = [start, end, fade_in, fade_out]` (seconds) as a fresh unit with the voice's hash and parameters and `params[k * names.len() ..]`
+    /// written over the f32 slots `names`.  `fade`: `FDSP_FADE_POWER` / `FDSP_FADE_SMOOTH` per note, or empty for smooth.  `render_events_mix`
+    /// (`fdsp_bank_process_events_mix`) then plays it; an empty score removes it.
+    pub fn set_score(&mut self, voice: &[i32], events: &[[f64; 4]], fade: &[i32], names: &[&str], params: &[f32]) -> Result<(), String> {
+        if events.len() != voice.len() || (!fade.is_empty() && fade.len() != voice.len()) || params.len() != voice.len() * names.len() {
+            return Err("set_score: voice, events, fade and params must describe the same notes".into());
+        }
+        let names: Vec<CString> = names.iter().map(|n| CString::new(*n).map_err(|e| e.to_string())).collect::<Result<_, _>>()?;
+        let ptrs: Vec<*const c_char> = names.iter().map(|n| n.as_ptr()).collect();
+        check(unsafe {
+            fdsp_bank_set_score(self.bank, voice.len(), voice.as_ptr(), events.as_ptr() as *const f64, if fade.is_empty() { core::ptr::null() } else { fade.as_ptr() },
+                                ptrs.len() as c_int, ptrs.as_ptr(), params.as_ptr())
+        })
     }
 
     /// `AudioNode::allocate` for the mix path: size the bank's partial-mix buffer for launches of up to `frames` frames, so that
