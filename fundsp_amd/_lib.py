@@ -13,6 +13,7 @@ OK, EINVAL, ENOMEM, EDEVICE, ENOTSUP = 0, -1, -2, -3, -4
 LAYOUT_VOICE_MINOR, LAYOUT_PLANAR = 0, 1
 MODE_PROCESS, MODE_TICK = 0, 1
 MATH_EXACT, MATH_FAST = 0, 1
+SCORE_VOICES, SCORE_NOTES = 0, 1  # the "score_exec" option: a lane is a voice / a lane is a note
 BUS_NONE, BUS_WET, BUS_DRY_WET = 0, 1, 2  # fdsp_bank_set_bus: the node alone | wet * node | dry * multipass() & wet * node
 MIX_SUM, MIX_PAN = 1, 2  # fdsp_bank_process_mix: sum the output channels over the voices | pan a mono graph per voice, then sum
 FADE_POWER, FADE_SMOOTH = 0, 1  # sequencer.rs Fade::Power / Fade::Smooth

@@ -620,7 +620,8 @@ class Bank:
         """A score of N notes: note k plays on voice[k] from start[k] to end[k] (seconds on the sequencer clock; fades and curve as in
         set_events, scalars broadcast) as a FRESH unit with the voice's seed and parameters and `params` = {slot name: [N] f32 values}
         written over the named slots.  The notes of a voice must not overlap (fundsp_amd.score.assign_voices allots voices); any order.
-        process_events / process_events_mix then play the score; an empty score removes it."""
+        process_events / process_events_mix then play the score; an empty score removes it.  set_option("score_exec", SCORE_NOTES)
+        renders the notes in parallel, one lane per note -- the executor for long launches over many short notes; same bits."""
         voice = np.ascontiguousarray(np.atleast_1d(np.asarray(voice)), dtype=np.int32)
         n = voice.size
         ev = np.empty((n, 4), dtype=np.float64)

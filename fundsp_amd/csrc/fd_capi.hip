@@ -34,6 +34,7 @@ namespace fd {
 // hosts drive banks from several threads.  The launch code never reads these: it reads the thread-local block below.
 std::atomic<int> g_pipe_split{1}, g_fdn_kernel{0}, g_time_split{1};
 std::atomic<int> g_math{FDSP_MATH_EXACT};  // default arithmetic of banks created from now on (fdsp_set_option("math", ..))
+std::atomic<int> g_score_chunk{0};        // mixed score launches, one lane per note: frames per scratch chunk, 0 = from the byte budget (events_render)
 std::atomic<int> g_fx_mix_chunk{0};       // effect banks' fused mix-down: frames per scratch chunk, 0 = from the byte budget (fd_fxbank.hip)
 std::atomic<int> g_timing{1};              // default of the per-launch HIP event pair (fdsp_bank_last_kernel_ms)
 std::atomic<long> g_zero_copy_max{1 << 18};  // floats; fdsp_bank_process_host reads/writes pinned host memory directly below this
@@ -409,7 +410,7 @@ struct fdsp_bank {
     mutable bool async_param_pending = false;
     int math = FDSP_MATH_EXACT;  // FDSP_MATH_FAST: renders take the kind's tolerance-mode variant when it has one
     // per-bank launch options (fdsp_bank_set_option); -1 = follow the process-wide default at every launch
-    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1, opt_fx_mix_chunk = -1;
+    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1, opt_fx_mix_chunk = -1, opt_score_chunk = -1;
     size_t ring_frames = 0;      // as given at creation (fdsp_bank_clone)
     int last_kernel = 0;         // fd::LastKernel of the most recent render launch (fdsp_bank_get_option "last_kernel")
     bool ring_check_pending = false;  // a lifecycle launch may have changed a delay length: verify capacity before rendering
@@ -441,6 +442,14 @@ struct fdsp_bank {
     float* mix_part = nullptr;
     size_t mix_part_n = 0;
     float* panw = nullptr;
+    // scores with one lane per note ("score_exec" = FDSP_SCORE_NOTES, a property of the bank: a score or events coming or going leave it).
+    // score_stage: the staging image [nslots][stride] the write-back owners store to, then stride flags (ints) -- allocated when the option
+    // or a score is set.  score_scratch: the voice-out chunk [outputs][chunk frames][V] a MIXED launch renders into before the voices are
+    // added up; it follows mix_part's rule (fdsp_bank_mix_reserve sizes it, an uncaptured launch may grow it).  Clones start without either.
+    int score_exec = FDSP_SCORE_VOICES;
+    float* score_stage = nullptr;
+    float* score_scratch = nullptr;
+    size_t score_scratch_n = 0;
 };
 
 namespace {
@@ -552,9 +561,12 @@ FD_D float quad_swap(float x, int ctrl) {
 // x: [rows][V] voice-minor.  PAN = false: part[group][row] = partial sum of the row.  PAN = true (rows = frames of a mono render):
 // part[group][c][row], c = left / right, every sample weighted by its voice's pan weights first.
 // One workgroup = one voice group x 256 rows: thread (row, quarter) reads its quarter's 16 consecutive floats.
-template <bool PAN, bool VEC4>
+// MAP (a chunk of a longer mixed launch, PAN = false): row r = channel * ch_rows + frame of the chunk goes to
+// part[group * part_stride + channel * ch_stride + col0 + frame] -- the columns col0 ... of a [groups][channels][frames] buffer; the sums are the same.
+struct PartMap { size_t part_stride, ch_rows, ch_stride, col0; };
+template <bool PAN, bool VEC4, bool MAP = false>
 __global__ __launch_bounds__(256) void k_group_partials(const float* __restrict__ x, const float* __restrict__ wl,
-                                                        const float* __restrict__ wr, float* __restrict__ part, size_t rows, size_t V) {
+                                                        const float* __restrict__ wr, float* __restrict__ part, size_t rows, size_t V, PartMap map = PartMap{}) {
     const size_t g = blockIdx.x, r0 = (size_t)blockIdx.y * 256;
     const int q = threadIdx.x & 3, rl = threadIdx.x >> 2;
     const size_t vq = g * 64 + (size_t)q * 16;
@@ -604,7 +616,10 @@ __global__ __launch_bounds__(256) void k_group_partials(const float* __restrict_
                 part[(g * 2 + 0) * rows + r] = ul;
                 part[(g * 2 + 1) * rows + r] = ur;
             }
-        } else if (on && q == 0) part[g * rows + r] = ul;
+        } else if (on && q == 0) {
+            if constexpr (MAP) part[g * map.part_stride + (r / map.ch_rows) * map.ch_stride + map.col0 + r % map.ch_rows] = ul;
+            else part[g * rows + r] = ul;
+        }
     }
 }
 
@@ -692,6 +707,18 @@ hipError_t launch_mix_rows(const float* x, const float* wl, const float* wr, flo
     return hipGetLastError();
 }
 
+
+// ---- scores with one lane per note: the second half of the write-back ------------------------------------------------------
+// slots[s][v] = stage[s][v] for the voices whose owning note raised flag[v] in the note kernel before (fd_device.hpp
+// render_score_notes_body); the flags go back to 0.  In stream order behind the note kernel: every lane has loaded its voice by then.
+__global__ __launch_bounds__(256) void k_score_commit(float* __restrict__ slots, const float* __restrict__ stage, int* __restrict__ flag, size_t stride,
+                                                     size_t V, int nslots) {
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= V || !flag[v]) return;
+    for (int s = 0; s < nslots; s++) slots[(size_t)s * stride + v] = stage[(size_t)s * stride + v];
+    flag[v] = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -728,6 +755,8 @@ const OptSpec LAUNCH_OPTS[] = {
     {"timing", 0, 1, "timing takes 0 (no per-launch event pair) or 1 (fdsp_bank_last_kernel_ms available)", &fd::g_timing, &fdsp_bank::opt_timing},
     {"fx_mix_chunk_frames", 0, 1 << 21, "fx_mix_chunk_frames takes 0 (automatic: from the scratch budget) or a multiple of 64 up to 2 097 152 (frames per chunk of an effect bank's mix scratch)",
      &fd::g_fx_mix_chunk, &fdsp_bank::opt_fx_mix_chunk, 64},
+    {"score_chunk_frames", 0, 1 << 21, "score_chunk_frames takes 0 (automatic: from the scratch budget) or a multiple of 64 up to 2 097 152 (frames per chunk of a mixed score launch with one lane per note)",
+     &fd::g_score_chunk, &fdsp_bank::opt_score_chunk, 64},
 };
 const OptSpec* launch_opt(const char* name) {
     if (!name) return nullptr;
@@ -745,6 +774,48 @@ void resolve_opts(const fdsp_bank* b) {
     fd::tl_opts.last_kernel = fd::LK_NONE;
 }
 bool timing_on(const fdsp_bank* b) { return (b->opt_timing >= 0 ? b->opt_timing : fd::g_timing.load(std::memory_order_relaxed)) != 0; }
+
+// ---- scores with one lane per note: what the bank owns for them ----------------------------------------------------------------
+bool score_notes_kind(const fdsp_bank* b) { return !b->fx && b->ops && b->ops->render_score_notes; }
+// the staging image and its flags; never called by a captured launch
+int ensure_score_stage(fdsp_bank* b) {
+    if (b->score_stage || !score_notes_kind(b)) return FDSP_OK;
+    const size_t floats = (size_t)(b->nslots > 0 ? b->nslots : 1) * b->stride, bytes = floats * sizeof(float) + b->stride * sizeof(int);
+    hipError_t e = hipMalloc((void**)&b->score_stage, bytes);
+    if (e != hipSuccess) {
+        b->score_stage = nullptr;
+        return fail(FDSP_ENOMEM, std::string("hipMalloc(score staging image): ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipMemsetAsync(b->score_stage, 0, bytes, b->stream));
+    HIPCHK(sync_bank_stream(b));
+    return FDSP_OK;
+}
+int* score_flags(const fdsp_bank* b) { return reinterpret_cast<int*>(b->score_stage + (size_t)(b->nslots > 0 ? b->nslots : 1) * b->stride); }
+// frames per chunk of a mixed launch of `frames` frames: whole 64-frame blocks; "score_chunk_frames", or what 256 MiB of scratch hold
+// (the effect banks' and the convolver's figure), and no more than the launch needs
+size_t score_chunk_frames(const fdsp_bank* b, size_t frames) {
+    const size_t nm = (size_t)fdsp_bank_outputs(b);
+    const int opt = b->opt_score_chunk >= 0 ? b->opt_score_chunk : fd::g_score_chunk.load(std::memory_order_relaxed);
+    size_t chunk = (size_t)opt;
+    if (chunk == 0) {
+        chunk = (((size_t)256 << 20) / sizeof(float) / (nm * b->V)) & ~(size_t)63;
+        if (chunk < 64) chunk = 64;
+    }
+    const size_t whole = (frames + 63) & ~(size_t)63;
+    return chunk < whole ? chunk : whole;
+}
+int score_scratch_reserve(fdsp_bank* b, size_t floats) {
+    if (floats <= b->score_scratch_n) return FDSP_OK;
+    HIPCHK(sync_bank_stream(b));
+    if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));  // a render on a caller's stream may still use the old buffer
+    if (b->score_scratch) hipFree(b->score_scratch);
+    b->score_scratch = nullptr;
+    b->score_scratch_n = 0;
+    hipError_t e = hipMalloc((void**)&b->score_scratch, floats * sizeof(float));
+    if (e != hipSuccess) return fail(FDSP_ENOMEM, std::string("hipMalloc(score scratch): ") + hipGetErrorString(e));
+    b->score_scratch_n = floats;
+    return FDSP_OK;
+}
 }  // namespace
 
 int fdsp_set_option(const char* name, int value) {
@@ -779,6 +850,16 @@ int fdsp_bank_set_option(fdsp_bank* b, const char* name, int value) {
         }
         return FDSP_OK;
     }
+    if (name && std::strcmp(name, "score_exec") == 0) {  // a request, like "pipe_split": a kind that cannot take the note path keeps today's kernel
+        if (b->fx) return fail(FDSP_EINVAL, "score_exec: effect banks (reverb, network, resynthesizer, convolver) play no scores");
+        if (value != FDSP_SCORE_VOICES && value != FDSP_SCORE_NOTES) return fail(FDSP_EINVAL, "score_exec takes FDSP_SCORE_VOICES (0: a lane is a voice) or FDSP_SCORE_NOTES (1: a lane is a note)");
+        if (value == FDSP_SCORE_NOTES) {  // the staging image exists before any render
+            DeviceGuard guard(b->device);
+            if (int rc = ensure_score_stage(b)) return rc;
+        }
+        b->score_exec = value;
+        return FDSP_OK;
+    }
     if (const OptSpec* o = launch_opt(name)) {  // -1 = back to the process-wide default
         if (value != -1 && !opt_in_range(*o, value)) return fail(FDSP_EINVAL, std::string(o->what) + "; -1 = follow the process-wide default");
         b->*(o->field) = value;
@@ -793,6 +874,12 @@ int fdsp_bank_get_option(const fdsp_bank* b, const char* name) {
     if (const OptSpec* o = launch_opt(name)) return b->*(o->field) >= 0 ? b->*(o->field) : o->global->load();
     if (name && std::strcmp(name, "has_fused_mix") == 0) return b->fx ? (b->fx->has_mix() ? 1 : 0) : ((b->ops && b->ops->render_mix) ? 1 : 0);
     if (name && std::strcmp(name, "last_kernel") == 0) return b->last_kernel;
+    if (name && std::strcmp(name, "score_exec") == 0) return b->score_exec;
+    if (name && std::strcmp(name, "has_score_notes") == 0) return score_notes_kind(b) ? 1 : 0;
+    if (name && std::strcmp(name, "score_scratch_frames") == 0) {  // frames the mixed note path's scratch holds now (read-only)
+        const size_t per = (size_t)fdsp_bank_outputs(b) * b->V;
+        return per ? (int)(b->score_scratch_n / per) : 0;
+    }
     return fail(FDSP_EINVAL, "unknown bank option");
 }
 
@@ -1214,6 +1301,8 @@ void fdsp_bank_destroy(fdsp_bank* b) {
     if (b->ev_fade) hipFree(b->ev_fade);
     if (b->score_mem) hipFree(b->score_mem);
     if (b->mix_part) hipFree(b->mix_part);
+    if (b->score_stage) hipFree(b->score_stage);
+    if (b->score_scratch) hipFree(b->score_scratch);
     if (b->panw) hipFree(b->panw);
     if (b->st_in) hipFree(b->st_in);
     if (b->st_out) hipFree(b->st_out);
@@ -1293,6 +1382,8 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     b->opt_fdn_kernel = src->opt_fdn_kernel;
     b->opt_timing = src->opt_timing;
     b->opt_fx_mix_chunk = src->opt_fx_mix_chunk;
+    b->opt_score_chunk = src->opt_score_chunk;
+    b->score_exec = src->score_exec;  // (no staging image, no scratch: the clone's first uncaptured scored launch, or its fdsp_bank_mix_reserve, makes them)
     e = sync_bank_stream(b);
     if (e != hipSuccess) return bail(e, "copy");
     *out = b;
@@ -1618,7 +1709,12 @@ int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
         resolve_opts(b);  // ("fx_mix_chunk_frames")
         return b->fx->mix_reserve(frames);  // (the bank is idle: mix_reserve above waited)
     }
-    return mix_reserve(b, (b->stride / 64) * nm * frames);
+    if (int rc = mix_reserve(b, (b->stride / 64) * nm * frames)) return rc;
+    if (b->score_exec == FDSP_SCORE_NOTES && score_notes_kind(b) && fdsp_bank_outputs(b) <= 2) {  // the mixed note path's staging image and scratch
+        if (int rc = ensure_score_stage(b)) return rc;
+        return score_scratch_reserve(b, (size_t)fdsp_bank_outputs(b) * score_chunk_frames(b, frames) * b->V);
+    }
+    return FDSP_OK;
 }
 
 namespace {
@@ -1849,6 +1945,10 @@ int fdsp_bank_set_score(fdsp_bank* b, size_t notes, const int* voice, const doub
             return fail(FDSP_EINVAL, "fdsp_bank_set_score: note " + std::to_string(q) + " overlaps note " + std::to_string(p) + " on voice " + std::to_string(voice[q]) +
                                          " (a voice plays one note at a time: end <= the next start)");
     }
+    if (notes > 0 && b->score_exec == FDSP_SCORE_NOTES) {  // ... and so is the note path's staging image
+        DeviceGuard guard(b->device);
+        if (int rc = ensure_score_stage(b)) return rc;
+    }
     if (notes > 0 && b->ops->prepare_score) {  // run-time compiled kinds: the kernels are built now, never inside a render
         std::string err;
         if (!b->ops->prepare_score(&err)) return fail(FDSP_EDEVICE, "fdsp_bank_set_score: " + err);
@@ -1937,9 +2037,17 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
     if (s != b->stream) hipStreamIsCapturing(s, &cap);
     const bool capturing = cap != hipStreamCaptureStatusNone;  // a captured launch leaves the timing events alone
     const size_t nm = (size_t)fdsp_bank_outputs(b), groups = b->stride / 64, R = nm * frames;
-    if (mixing && groups * R > b->mix_part_n) {
+    // one lane per note: asked for, and the kind can (otherwise today's kernel, silently); mixed: through a chunked voice-out scratch
+    const bool notes = scored && b->score_exec == FDSP_SCORE_NOTES && score_notes_kind(b) && (!mixing || nm <= 2);
+    const size_t chunk = notes && mixing ? score_chunk_frames(b, frames) : 0;
+    if (mixing && (groups * R > b->mix_part_n || nm * chunk * b->V > b->score_scratch_n)) {
         if (capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_events_mix during a stream capture: call fdsp_bank_mix_reserve before capturing");
         if (int rc = mix_reserve(b, groups * R)) return rc;
+        if (int rc = score_scratch_reserve(b, nm * chunk * b->V)) return rc;
+    }
+    if (notes && !b->score_stage) {  // a clone: it starts without the staging image
+        if (capturing) return fail(FDSP_EINVAL, "a scored launch with score_exec = FDSP_SCORE_NOTES during a stream capture: call fdsp_bank_mix_reserve before capturing");
+        if (int rc = ensure_score_stage(b)) return rc;
     }
     if (int rc = order_after_bank_stream(b, s)) return rc;
     if (int rc = check_ring_need(b, capturing)) return rc;
@@ -1971,7 +2079,36 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
     const bool sustained = !scored && !b->ev_host.empty() && b->ev_max_start <= t_begin && b->ev_min_end >= t_end &&
                            b->ev_max_fade_in_end <= t_begin && b->ev_min_fade_out_start >= t_end;
     resolve_opts(b);
-    if (mixing) {
+    const unsigned commit_grid = (unsigned)((b->V + 255) / 256);
+    if (notes && mixing) {
+        // Chunks of whole blocks: memset, notes, commit, the groups' partials into columns t0 ... of mix_part; then one tree.  Splitting a
+        // launch at a block boundary changes no bit (the score contract), and the sums are fdsp_sum_voices' (= the fused mix, bit for bit).
+        double tc = t_begin;
+        for (size_t t0 = 0; t0 < frames; t0 += chunk) {
+            const size_t n = frames - t0 < chunk ? frames - t0 : chunk;
+            HIPCHK(hipMemsetAsync(b->score_scratch, 0, nm * n * b->V * sizeof(float), s));
+            b->ops->render_score_notes(b->slots, b->score_stage, score_flags(b), b->stride, b->V, d_in ? d_in + t0 * b->V : nullptr, frames, b->score_scratch, n,
+                                       b->score, tc, b->sr, mode, b->aux, s);
+            hipLaunchKernelGGL(k_score_commit, dim3(commit_grid), dim3(256), 0, s, b->slots, (const float*)b->score_stage, score_flags(b), b->stride, b->V, b->nslots);
+            const PartMap map{R, n, frames, t0};
+            const dim3 pgrid((unsigned)((b->V + 63) / 64), (unsigned)((nm * n + 255) / 256));
+            if (b->V % 4 == 0)  // (the scratch is 256-byte aligned)
+                hipLaunchKernelGGL((k_group_partials<false, true, true>), pgrid, dim3(256), 0, s, (const float*)b->score_scratch, (const float*)nullptr, (const float*)nullptr,
+                                   b->mix_part, nm * n, b->V, map);
+            else
+                hipLaunchKernelGGL((k_group_partials<false, false, true>), pgrid, dim3(256), 0, s, (const float*)b->score_scratch, (const float*)nullptr, (const float*)nullptr,
+                                   b->mix_part, nm * n, b->V, map);
+            if (mode == FDSP_MODE_PROCESS)
+                for (size_t t = 0; t < n; t += 64) tc += sd * (double)(n - t < 64 ? n - t : 64);
+            else
+                for (size_t t = 0; t < n; t++) tc += sd;
+        }
+        launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, s);
+    } else if (notes) {
+        HIPCHK(hipMemsetAsync(d_out, 0, nm * frames * b->V * sizeof(float), s));  // frames no note plays are +0.0
+        b->ops->render_score_notes(b->slots, b->score_stage, score_flags(b), b->stride, b->V, d_in, frames, d_out, frames, b->score, b->seq_time, b->sr, mode, b->aux, s);
+        hipLaunchKernelGGL(k_score_commit, dim3(commit_grid), dim3(256), 0, s, b->slots, (const float*)b->score_stage, score_flags(b), b->stride, b->V, b->nslots);
+    } else if (mixing) {
         bool done = false;
         if (sustained && b->ops->render_mix)  // (the exact type: the voice scheduler renders exactly, like fdsp_bank_process_events)
             done = b->ops->render_mix(b->slots, b->stride, b->V, d_in, b->mix_part, frames, FDSP_MIX_SUM, mode, b->aux, b->ring, b->ring_cap, b->panw, s);

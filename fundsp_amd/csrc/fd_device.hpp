@@ -1374,7 +1374,164 @@ __global__ __launch_bounds__(256) void k_render_score(float* __restrict__ slots,
     render_score_body<G, MODE>(slots, stride, V, in, out, T, sc, time0, sample_rate, aux, ring, ring_cap);
 }
 
-#ifdef FD_PIPE_WPE        // A/B switch: tell the compiler how many waves per SIMD the pipeline kernel runs with
+// ---- scores, one lane per NOTE ("score_exec" = FDSP_SCORE_NOTES) ------------------------------------------------------------
+// The score's contract makes the notes of a voice independent: each starts from the voice's slots as they stand, its row written
+// over them, update(sr), reset().  So lane j of the grid is note j of the sorted score, and it walks only the launch blocks its
+// note lives in -- the frame-by-frame part of render_score_body restricted to one note: the same seq_block windows, the same
+// begin_block(n) / PH_SIMD / PH_REM / end_simd sequence, the fades accumulated in f32, hence the same bits.  The lanes of a wave
+// stand in DIFFERENT blocks of the launch at the same instruction; they share nothing (no LDS, no atomics, no cross-lane traffic).
+// The block clock is the serial kernel's: the lane walks the f64 additions from time0 (1 500 of them for 96 000 frames -- a few
+// microseconds next to the note's frames; tick mode pays one per sample).  Frames no note plays are zeroed by the host before the launch.
+// Only for graphs without rings whose reset() leaves nothing of earlier rendering behind (note_fresh, fd_nodes.hpp note_stale).
+// Write-back: the slots must end as the serial kernel leaves them -- the VStore<true> image of the last note of the voice that
+// rendered a frame in this launch (seq_note_owns_state).  Other lanes of the voice may not have loaded the launch-start slots yet
+// (a carried-in note needs them), so the owner writes to the staging image `stage` and raises stage_flag[voice]; k_score_commit
+// copies the flagged voices over in stream order.  `in` / in_T: the voice's input rows [channel][in_T][V], already at the launch's first
+// frame (a chunk of a longer mixed launch renders T < in_T frames); out: [channel][T][V].
+template <class G, int MODE>
+FD_D void render_score_notes_body(const float* __restrict__ slots, float* __restrict__ stage, int* __restrict__ stage_flag, size_t stride,
+                                  size_t V, const float* __restrict__ in, size_t in_T, float* __restrict__ out, size_t T, const ScoreData sc,
+                                  double time0, double sample_rate, const void* aux) {
+    constexpr int NI = G::IN, NO = G::OUT;
+    constexpr bool TICK = MODE != MODE_PROCESS;
+    const size_t N = (size_t)sc.N;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const double sd = 1.0 / sample_rate;
+    const double e_start = sc.ev[j], e_end = sc.ev[N + j], e_fin = sc.ev[2 * N + j], e_fout = sc.ev[3 * N + j];
+    if (seq_note_over(e_end, time0, sd)) return;
+    // the launch's clock up to the first block the note is ready in
+    double time = time0;
+    size_t t0 = 0;
+    for (;;) {
+        if (t0 >= T) return;  // not ready before the launch's last block ends
+        const int size = TICK ? 1 : (int)((T - t0) < 64 ? (T - t0) : 64);
+        const double end_time = time + sd * (double)size;
+        if (seq_note_ready(e_start, end_time, sd)) break;
+        time = end_time;
+        t0 += (size_t)size;
+    }
+    size_t v;  // the note's voice: note_begin[v] <= j < note_begin[v + 1]
+    {
+        size_t lo = 0, hi = V;
+        while (hi - lo > 1) {
+            const size_t mid = lo + ((hi - lo) >> 1);
+            if ((size_t)sc.note_begin[mid] <= j) lo = mid;
+            else hi = mid;
+        }
+        v = lo;
+    }
+    const int ease = sc.fade[j];
+    G g;
+    Ctx ctx{static_cast<const Aux*>(aux), nullptr, 0, stride, 0};
+    g.bind(ctx);
+    {
+        VLoad ld{slots + v, stride, 0};
+        g.visit(ld);
+    }
+    auto begin_note = [&]() {  // a fresh unit with the note's parameters
+        VSetRow row{sc.params, sc.param_slot, sc.nparams, N, j, 0};
+        g.visit(row);
+        g.update(sample_rate);
+        g.reset();
+    };
+    const float* inv = in + v;
+    float* outv = out + v;
+    bool rendered = false;
+    double time_last = time;  // the block of the note's last frame so far
+    size_t t_last = t0;
+    if constexpr (!TICK) {
+        for (; t0 < T && !seq_note_over(e_end, time, sd); t0 += 64) {
+            const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
+            const double end_time = time + sd * (double)size;
+            const SeqBlock w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
+            if (w.act) {  // the note's own process() block: [si, ei) of this block
+                const int si = (int)w.start_index, ei = (int)w.end_index;
+                if (!seq_note_begun(e_start, time, sd)) begin_note();
+                const int full = (ei - si) & ~7;
+                g.begin_block(ei - si);
+                if (full == 0) g.end_simd();
+                float fin_cur = w.fin_cur, fout_cur = w.fout_cur;
+                for (int kk = 0; kk < ei - si; kk++) {
+                    const size_t t = t0 + (size_t)(si + kk);
+                    float fi[NI > 0 ? NI : 1], fo[NO];
+#pragma unroll
+                    for (int c = 0; c < NO; c++) fo[c] = 0.0f;
+#pragma unroll
+                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * in_T + t) * V];
+                    if (kk < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
+                    if (kk + 1 == full) g.end_simd();
+                    if (w.fin_on && kk < w.fin_end_i) {
+                        const float e = fade_at(ease, fin_cur);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                        fin_cur += w.fin_d;
+                    }
+                    if (w.fout_on && kk >= w.fout_i && kk < w.end_index) {
+                        const float e = fade_at(ease, 1.0f - fout_cur);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                        fout_cur += w.fout_d;
+                    }
+#pragma unroll
+                    for (int c = 0; c < NO; c++) outv[((size_t)c * T + t) * V] = fo[c];
+                }
+                rendered = true;
+                time_last = time;
+                t_last = t0;
+            }
+            time = end_time;
+        }
+    } else {
+        for (; t0 < T && !seq_note_over(e_end, time, sd); t0++) {  // Sequencer::tick :769-836
+            const double end_time = time + sd;
+            if (seq_note_ready(e_start, end_time, sd)) {
+                if (!seq_note_begun(e_start, time, sd)) begin_note();
+                float fi[NI > 0 ? NI : 1], fo[NO];
+#pragma unroll
+                for (int c = 0; c < NO; c++) fo[c] = 0.0f;
+#pragma unroll
+                for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * in_T + t0) * V];
+                g.template step<PH_TICK>(fi, fo);
+                if (e_fin > 0.0) {
+                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
+                    if (f < 1.0f) {
+                        const float e = fade_at(ease, f);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                    }
+                }
+                if (e_fout > 0.0) {
+                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
+                    if (f > 0.0f) {
+                        const float e = fade_at(ease, 1.0f - f);
+#pragma unroll
+                        for (int c = 0; c < NO; c++) fo[c] *= e;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < NO; c++) outv[((size_t)c * T + t0) * V] = fo[c];
+                rendered = true;
+                time_last = time;
+                t_last = t0;
+            }
+            time = end_time;
+        }
+    }
+    if (rendered && seq_note_owns_state(sc.ev, N, (int)j, sc.note_begin[v + 1], time_last, t_last, T, TICK, sd, sample_rate)) {
+        VStore<true> st{stage + v, stride, 0};
+        g.visit(st);
+        stage_flag[v] = 1;
+    }
+}
+template <class G, int MODE>
+__global__ __launch_bounds__(256) void k_render_score_notes(const float* __restrict__ slots, float* __restrict__ stage, int* __restrict__ stage_flag,
+                                                           size_t stride, size_t V, const float* __restrict__ in, size_t in_T, float* __restrict__ out,
+                                                           size_t T, const ScoreData sc, double time0, double sample_rate, const void* aux) {
+    render_score_notes_body<G, MODE>(slots, stage, stage_flag, stride, V, in, in_T, out, T, sc, time0, sample_rate, aux);
+}
+
+#ifdef FD_PIPE_WPE       // A/B switch: tell the compiler how many waves per SIMD the pipeline kernel runs with
 #define FD_PIPE_ATTR __attribute__((amdgpu_waves_per_eu(FD_PIPE_WPE, FD_PIPE_WPE)))
 #else
 #define FD_PIPE_ATTR
@@ -2825,6 +2982,8 @@ struct VDescribeDev {
     FD_D void u64(uint64_t&, FieldKind k, const char* name) { line(name, -1, ".lo", (int)k); line(name, -1, ".hi", (int)k); }
     FD_D void enter(int i) { if (depth < 32) path[depth] = i; depth++; }
     FD_D void leave() { depth--; }
+    bool keeps = false;  // fd_nodes.hpp note_stale
+    FD_D void stale() { keeps = true; }
 };
 // heavy run-time compiled graphs also get the pipeline kernel for workgroups of 1 / 2 voice groups (small banks)
 template <class G>
@@ -2885,6 +3044,13 @@ FD_D void jit_score_mix_body(float* __restrict__ slots, size_t stride, size_t V,
                              const ScoreData sc, double time0, double sr, const void* aux, float* ring, uint32_t ring_cap) {
     if constexpr (G::OUT <= 2) render_score_body<G, MODE, true>(slots, stride, V, in, part, T, sc, time0, sr, aux, ring, ring_cap);
 }
+// one lane per note ("score_exec" = FDSP_SCORE_NOTES); empty for a graph with rings, whose notes would share the voice's ring
+template <class G, int MODE>
+FD_D void jit_score_notes_body(const float* __restrict__ slots, float* __restrict__ stage, int* __restrict__ flag, size_t stride, size_t V,
+                               const float* __restrict__ in, size_t in_T, float* __restrict__ out, size_t T, const ScoreData sc, double time0, double sr,
+                               const void* aux) {
+    if constexpr (G::RINGS == 0) render_score_notes_body<G, MODE>(slots, stage, flag, stride, V, in, in_T, out, T, sc, time0, sr, aux);
+}
 template <class G, int MODE>
 FD_D void jit_pipe_planar_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
                                float* __restrict__ out, size_t T, size_t fstride, const void* aux, float* ring, uint32_t ring_cap) {
@@ -2932,7 +3098,8 @@ FD_D void describe_body(char* out, int cap, GraphTraits* traits) {
     VDescribeDev d{out, 0, cap, {0}, 0};
     g.visit(d);
     out[d.pos] = 0;
-    constexpr GraphTraits t = graph_traits<G>(true);
+    GraphTraits t = graph_traits<G>(true);
+    t.note_fresh = G::RINGS == 0 && !d.keeps;
     *traits = t;
 }
 

@@ -39,6 +39,8 @@ struct VDescribe {  // host only
     }
     void enter(int i) { path.push_back(i); }
     void leave() { path.pop_back(); }
+    bool keeps = false;  // a node said that its reset() keeps something of earlier rendering (fd_nodes.hpp note_stale)
+    void stale() { keeps = true; }
 };
 
 // ---- per-kind dispatch table ---------------------------------------------------------------------------------
@@ -95,6 +97,14 @@ struct KindOps {
     // whatever the score kernels of this kind still need before their first launch (run-time compiled graphs: compile and load
     // them) -- called by fdsp_bank_set_score, never by a render; false + *err: they cannot be built.  Empty for ahead-of-time kinds.
     std::function<bool(std::string* err)> prepare_score;
+    // ... and scores with one lane per note (fd_device.hpp render_score_notes_body, "score_exec" = FDSP_SCORE_NOTES): voice-out only;
+    // the owner of a voice's write-back stores to `stage` [slots][stride] and raises flag[voice], the host commits afterwards.
+    // note_fresh: the kind can take that path -- no rings and no node whose reset() keeps earlier state; empty / false otherwise.
+    bool note_fresh = false;
+    // in: the input rows [channel][in_T][V] from the launch's first frame on (a chunk of a longer launch renders T < in_T frames).
+    std::function<void(const float* slots, float* stage, int* flag, size_t stride, size_t V, const float* in, size_t in_T, float* out, size_t T,
+                       const ScoreData& sc, double time0, double sr, int mode, const void* aux, hipStream_t s)>
+        render_score_notes;
 };
 
 template <class G>
@@ -308,6 +318,20 @@ void launch_render_score(float* slots, size_t stride, size_t V, const float* in,
 }
 
 template <class G>
+void launch_render_score_notes(const float* slots, float* stage, int* flag, size_t stride, size_t V, const float* in, size_t in_T, float* out, size_t T,
+                               const ScoreData& sc, double time0, double sr, int mode, const void* aux, hipStream_t s) {
+    if (V == 0 || T == 0 || sc.N == 0) return;
+    tl_opts.last_kernel = LK_SCORE_NOTES;
+    const unsigned grid = (unsigned)(((size_t)sc.N + 255) / 256);  // lane = note
+    if (mode == MODE_PROCESS)
+        hipLaunchKernelGGL((k_render_score_notes<G, MODE_PROCESS>), dim3(grid), dim3(256), 0, s, slots, stage, flag, stride, V, in, in_T, out, T, sc,
+                           time0, sr, aux);
+    else
+        hipLaunchKernelGGL((k_render_score_notes<G, MODE_TICK>), dim3(grid), dim3(256), 0, s, slots, stage, flag, stride, V, in, in_T, out, T, sc, time0,
+                           sr, aux);
+}
+
+template <class G>
 KindOps make_kind(const char* name) {
     KindOps k;
     k.name = name;
@@ -323,6 +347,10 @@ KindOps make_kind(const char* name) {
     if constexpr (!SameType<GF, G>::v) k.render_fast = &launch_render<GF>;
     k.render_events = &launch_render_events<G>;
     k.render_score = &launch_render_score<G>;
+    if constexpr (G::RINGS == 0) {  // notes of one voice would share the voice's ring
+        k.note_fresh = !d.keeps;
+        if (k.note_fresh) k.render_score_notes = &launch_render_score_notes<G>;
+    }
     return k;
 }
 

@@ -267,12 +267,12 @@ struct JitMix {
     }
 };
 
-// The score kernels of a compiled graph (jit_score_<mode>, and jit_score_mix_<mode> for graphs of at most two outputs): a module of their
-// own, like JitMix
+// The score kernels of a compiled graph (jit_score_<mode>, jit_score_mix_<mode> for graphs of at most two outputs, and jit_score_notes_<mode>,
+// one lane per note, for graphs without rings): a module of their own, like JitMix
 struct JitScore {
     std::vector<char> code;
     std::mutex mu;
-    struct Dev { hipModule_t mod = nullptr; hipFunction_t fn[2] = {nullptr, nullptr}; hipFunction_t mix[2] = {nullptr, nullptr}; bool loaded = false; } dev[JitModule::MAXD];
+    struct Dev { hipModule_t mod = nullptr; hipFunction_t fn[2] = {nullptr, nullptr}; hipFunction_t mix[2] = {nullptr, nullptr}; hipFunction_t notes[2] = {nullptr, nullptr}; bool loaded = false; } dev[JitModule::MAXD];
     ~JitScore() {
         int prev = -1;
         const bool have_prev = hipGetDevice(&prev) == hipSuccess;
@@ -292,6 +292,7 @@ struct JitScore {
         for (int m = 0; m < 2 && ok; m++) {
             ok = hipModuleGetFunction(&f.fn[m], f.mod, ("jit_score_" + std::to_string(m)).c_str()) == hipSuccess;
             ok = ok && hipModuleGetFunction(&f.mix[m], f.mod, ("jit_score_mix_" + std::to_string(m)).c_str()) == hipSuccess;
+            ok = ok && hipModuleGetFunction(&f.notes[m], f.mod, ("jit_score_notes_" + std::to_string(m)).c_str()) == hipSuccess;
         }
         if (!ok) { hipModuleUnload(f.mod); f.mod = nullptr; return nullptr; }
         return &f;
@@ -484,6 +485,10 @@ std::string jit_source_score(const std::string& type_expr, const std::string& pr
              "(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ part, "
              "size_t T, const fd::ScoreData sc, double time0, double sr, const void* aux, float* ring, uint32_t cap) {\n"
              "  fd::jit_score_mix_body<JitG, " + m + ">(slots, stride, V, in, part, T, sc, time0, sr, aux, ring, cap); }\n";  // (more than two outputs: an empty body)
+        s += "extern \"C\" __global__ __launch_bounds__(256) void jit_score_notes_" + m +
+             "(const float* __restrict__ slots, float* __restrict__ stage, int* __restrict__ flag, size_t stride, size_t V, "
+             "const float* __restrict__ in, size_t in_T, float* __restrict__ out, size_t T, const fd::ScoreData sc, double time0, double sr, const void* aux) {\n"
+             "  fd::jit_score_notes_body<JitG, " + m + ">(slots, stage, flag, stride, V, in, in_T, out, T, sc, time0, sr, aux); }\n";  // (a graph with rings: an empty body)
     }
     return s;
 }
@@ -789,6 +794,18 @@ int jit_make_kind(const std::string& name, const std::string& type_expr, const s
             hipModuleLaunchKernel(f->mix[mode], (unsigned)(((V + 63) / 64 + 3) / 4), 1, 1, 256, 1, 1, 0, s, args, nullptr);
             tl_opts.last_kernel = LK_SCORE;
             return true;
+        };
+    out->note_fresh = traits.note_fresh;
+    if (traits.note_fresh)
+        out->render_score_notes = [score_module](const float* slots, float* stage, int* flag, size_t stride, size_t V, const float* in, size_t in_T, float* outp,
+                                                 size_t T, const ScoreData& sc, double time0, double sr, int mode, const void* aux, hipStream_t s) {
+            if (V == 0 || T == 0 || sc.N == 0) return;
+            const JitScore::Dev* f = score_module(false, nullptr);
+            if (!f) return jit_launch_failed();
+            ScoreData scv = sc;
+            void* args[] = {&slots, &stage, &flag, &stride, &V, &in, &in_T, &outp, &T, &scv, &time0, &sr, &aux};
+            hipModuleLaunchKernel(f->notes[mode], (unsigned)(((size_t)sc.N + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr);
+            tl_opts.last_kernel = LK_SCORE_NOTES;
         };
     out->render_events = [jm](float* slots, size_t stride, size_t V, const float* in, float* outp, size_t T,
                               const double* ev, const int* fade, double time0, double sr, int mode, const void* aux,

@@ -24,6 +24,14 @@ namespace fd {
 
 enum FieldKind { PARAM = 0, COEF = 1, STATE = 2 };
 
+// A node whose reset() leaves something of what it rendered before behind (AdsrLive's closure state, a follower that keeps its
+// level) says so at the top of its visit(): note_stale(v).  A describing visitor that has a stale() member hears it (VDescribe,
+// VDescribeDev); the loading and storing visitors have none and the call is nothing.  A graph without such a node -- and without
+// rings -- is NOTE-FRESH: after a score's row, update(sr) and reset() no field depends on earlier rendering, so the notes of a
+// voice may be rendered independently of each other (fd_device.hpp render_score_notes_body).  DESIGN.md 6.18 lists the audit.
+template <class V> FD_HD auto note_stale(V& v, int) -> decltype(v.stale(), void()) { v.stale(); }
+template <class V> FD_HD void note_stale(V&, long) {}
+
 // Which reference path a sample belongs to (template argument of step / step2):
 //   PH_SIMD  process mode, sample inside a full 8-sample SIMD item of the block  -> a node's `process` arithmetic
 //   PH_REM   process mode, one of the trailing `size & 7` samples: nodes that end their `process` with
@@ -1369,6 +1377,7 @@ struct AdsrLive {
     int fb;      // sample of the block at which the prepared segment takes over; -1: the current chunk covers the block
     float f_cb;  // the gate at that sample
     template <class V> FD_HD void visit(V& v) {
+        note_stale(v, 0);  // reset() keeps the closure state
         v.f(attack, PARAM, "attack"); v.f(decay, PARAM, "decay"); v.f(sustain, PARAM, "sustain");
         v.f(release, PARAM, "release"); v.f(interval, PARAM, "interval");
         v.f(sd, COEF, "sample_duration");

@@ -17,7 +17,7 @@ struct LaunchOpts {
     int last_kernel = 0;
 };
 enum LastKernel { LK_NONE = 0, LK_SINGLE_WAVE = 1, LK_PIPELINE = 2, LK_PIPELINE_PLANAR = 3, LK_TIME_SPLIT = 4, LK_EVENTS = 5,
-                  LK_FDN_FRAMES = 6, LK_FDN_LINES = 7, LK_WIDE_CHAIN = 8, LK_SCORE = 9 };
+                  LK_FDN_FRAMES = 6, LK_FDN_LINES = 7, LK_WIDE_CHAIN = 8, LK_SCORE = 9, LK_SCORE_NOTES = 10 };
 extern thread_local LaunchOpts tl_opts;  // fd_capi.hip
 int simd_count();  // SIMDs of the current device (CUs x 4), fd_capi.hip
 }  // namespace fd

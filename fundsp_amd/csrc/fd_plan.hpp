@@ -50,6 +50,8 @@ struct GraphTraits {
     bool ts_mix_ok;           // time-split kernels with the fused mix-down: ahead-of-time kinds = ts_ok, run-time kinds ts_ok && nout <= 2
     bool mix_sum_ok;          // MIX_SUM of nout channels fits beside the pipeline's tiles: run-time kinds jit_mix_channels_ok(nout)
     bool has_fast;            // the graph has a tolerance-mode twin (FastOf<G> is another type)
+    bool note_fresh;          // scores may render the notes of a voice independently (no rings, no node marked note_stale); set where the graph is
+                              // described (make_kind / describe_body), not by graph_traits: the answer comes from a visit()
 };
 
 struct RenderPlan {

@@ -96,6 +96,43 @@ FD_HD int seq_first_live(const double* ends, int lo, int hi, double time, double
     return lo;
 }
 
+// ---- scores, one lane per note (render_score_notes_body): which note of a voice owns the write-back ------------------------
+// The launch's blocks are 64 frames long (1 in tick mode), counted from the launch start and ragged at the end; the clock of a
+// block is the launch's clock advanced by ONE f64 addition of sd * size per block before it -- never time0 + b * 64 * sd, which
+// differs in the last bits.  These walk it that way from a block [t, ...) whose clock is `time`.
+// Does the note render a frame in the rest of the launch?  *late: it is not ready before the launch's last block ends (then
+// neither is any later note of its voice).  A note renders in a block iff seq_block says so; in tick mode iff it is ready and
+// not over at the tick.
+FD_HD bool seq_note_renders(double e_start, double e_end, double time, size_t t, size_t T, bool tick, double sd, double sample_rate,
+                            bool* late) {
+    *late = false;
+    bool ready = false;
+    while (t < T) {
+        if (seq_note_over(e_end, time, sd)) return false;  // ... and stays over
+        const int size = tick ? 1 : (int)((T - t) < 64 ? (T - t) : 64);
+        const double end_time = time + sd * (double)size;
+        if (seq_note_ready(e_start, end_time, sd)) {
+            if (tick || seq_block(e_start, e_end, 0.0, 0.0, time, size, sample_rate).act) return true;
+            ready = true;
+        }
+        time = end_time;
+        t += (size_t)size;
+    }
+    *late = !ready;
+    return false;
+}
+// Note j of a voice whose range ends at hi rendered its last frame in the block [t, ...) with clock `time`: is it the LAST note of the
+// voice to render in this launch?  One look at note j + 1 in practice; the loop exists for notes of zero length, which never render.
+FD_HD bool seq_note_owns_state(const double* ev, size_t N, int j, int hi, double time, size_t t, size_t T, bool tick, double sd,
+                               double sample_rate) {
+    for (int q = j + 1; q < hi; q++) {
+        bool late;
+        if (seq_note_renders(ev[q], ev[N + q], time, t, T, tick, sd, sample_rate, &late)) return false;
+        if (late) break;
+    }
+    return true;
+}
+
 // A score on the device (fdsp_bank_set_score), sorted by (voice, start): note_begin[V + 1] is the CSR index of the voices'
 // ranges, ev[4][N] = start, end, fade_in, fade_out (f64 seconds), fade[N] the curves, params[nparams][N] the notes' rows for
 // the nparams slots param_slot[] (f32 slots, indices in visit order).  Passed to the kernels by value.

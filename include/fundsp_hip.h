@@ -128,11 +128,31 @@ int fdsp_bank_get_option(const fdsp_bank* bank, const char* name);
  * fdsp_bank_get_option(bank, "last_kernel") (read-only): the kernel family the most recent render launch took --
  * 1 single-wave, 2 pipeline, 3 planar pipeline, 4 time-split, 5 voice scheduler, 6 / 7 reverb lane-per-frame / -line,
  * 8 the chain of waves that renders a wide sum of generators (sumi / busi of >= 8 oscillators) on a small bank,
- * 9 the voice scheduler playing a score (fdsp_bank_set_score). */
+ * 9 the voice scheduler playing a score (fdsp_bank_set_score), 10 a score rendered with one lane per note ("score_exec"). */
 /* fdsp_bank_get_option(bank, "has_fused_mix") (read-only): 1 if fdsp_bank_process_mix has kernels for the bank's kind (voice banks), or
  * the bank is a reverb / network bank (their mix-down renders into a scratch: "the stereo mix-down" below); 0 for resynthesizer and convolver banks. */
 /* "fx_mix_chunk_frames" (default 0 = automatic, from a 256 MiB budget): frames per chunk of the mix scratch of a reverb / network bank, a
  * multiple of 64 (FDSP_EINVAL otherwise).  The chunking changes no bit of the mix. */
+/* "score_exec" (per bank, default FDSP_SCORE_VOICES): how fdsp_bank_process_events / _mix execute a score (fdsp_bank_set_score).
+ *   FDSP_SCORE_VOICES  a lane is a VOICE and walks the launch frame by frame: the cost is voices x frames however many notes there
+ *                      are.  For scores whose notes are long next to the launch (sustained voices, a real-time host's 64-frame blocks).
+ *   FDSP_SCORE_NOTES   a lane is a NOTE and walks only the blocks its note lives in; the output is zeroed first and the voices' state
+ *                      is committed by a small second kernel.  The cost is (longest note) x (waves of notes / chip): for long launches
+ *                      over many short notes.  Same samples, same state, same clock, bit for bit.
+ * A request, like "pipe_split": setting it always succeeds on a voice bank (effect banks: FDSP_EINVAL), a kind that cannot take the
+ * note path keeps the voice path silently ("last_kernel" then reads 9, otherwise 10).  It is a property of the bank: setting or
+ * dropping a score or events leaves it alone, fdsp_bank_clone copies it.  The bank's staging image (one copy of the slots) is allocated
+ * when the option or the score is set, never in a render; a clone makes its own at its first uncaptured scored launch or in
+ * fdsp_bank_mix_reserve.
+ * "has_score_notes" (read-only): 1 if the bank's kind can take the note path -- a voice graph without delay rings (the notes of a voice
+ * would share the ring) and without a node whose reset() keeps state (adsr_live); run-time compiled graphs answer per graph.
+ * "score_chunk_frames" (default 0 = automatic, from a 256 MiB budget): fdsp_bank_process_events_mix under FDSP_SCORE_NOTES renders
+ * voice-out into a scratch [outputs][chunk][voices] the bank owns and adds the voices up in the mix-down's order, chunk by chunk; this
+ * is the frames per chunk, a multiple of 64 (FDSP_EINVAL otherwise).  The chunking changes no bit.  The scratch follows the partial-mix
+ * buffer's rule: fdsp_bank_mix_reserve(bank, frames) sizes it, an uncaptured launch may grow it, a captured one that finds it too
+ * small is refused.  "score_scratch_frames" (read-only): the frames the scratch holds now. */
+#define FDSP_SCORE_VOICES 0
+#define FDSP_SCORE_NOTES 1
 /* "host_zero_copy_max" (default 262144): fdsp_bank_process_host calls moving at most this many floats per direction
  * let the kernel read/write pinned host memory directly instead of staging through HBM (lower per-block latency). */
 /* "fdn_kernel" (default 0): reverb banks render with one lane per FRAME (0) or one lane per DELAY LINE (1); identical
@@ -519,7 +539,8 @@ int fdsp_bank_process_events_mix(fdsp_bank* bank, size_t frames, const float* d_
  * Everything is validated before the bank is touched (FDSP_EINVAL names the offending note or slot).  The score replaces
  * any events or score of the bank; notes == 0 removes it, and so does fdsp_bank_set_events afterwards.  With a score
  * installed fdsp_bank_process_events and fdsp_bank_process_events_mix play it: output layout, clock, capture rules and the
- * fdsp_bank_mix_reserve requirement are unchanged; "last_kernel" reads 9.  Run-time compiled kinds build their score kernels
+ * fdsp_bank_mix_reserve requirement are unchanged; "last_kernel" reads 9 (10 with "score_exec" = FDSP_SCORE_NOTES, the executor for
+ * long launches over many short notes: see the options above).  Run-time compiled kinds build their score kernels
  * here, never inside a render.  The slots named in the score keep the last started note's values afterwards.  Effect banks
  * answer FDSP_EINVAL; fdsp_bank_clone copies the score. */
 int fdsp_bank_set_score(fdsp_bank* bank, size_t notes, const int* voice, const double* events, const int* fade, int nparams,

@@ -3,6 +3,8 @@ and what the note-switch code costs a sustained launch.  Run on the GPU box:
 
     python tools/score_bench.py --out profiles/score_bench.json
     FUNDSP_HIP_LIB=<an older build's libfundsp_hip.so> python tools/score_bench.py --skip-score --out <file>    # the events legs alone
+    FUNDSP_HIP_LIB=<the parent commit's library> python tools/score_bench.py --skip-notes --out parent.json       # the serial legs of a build
+    python tools/score_bench.py --serial-from parent.json --out profiles/score_bench.json                        #   without "score_exec", carried along
 
 Method: the FM + SVF kind (BASELINE config 3), fdsp_bank_process_events_mix, the launch's own HIP event pair (fdsp_bank_last_kernel_ms:
 kernel plus the partial-mix tree), one warm-up launch, then 20 timed launches -- median, min and max -- with the clock rewound before each.
@@ -16,7 +18,10 @@ Notes: 64 lanes of back-to-back notes over 96 000 frames (2 s at 48 kHz), 60 .. 
 Sustained: 65 536 voices x 12 000 frames, one note per voice covering the launch.  As events the launch is sustained and
 fdsp_bank_process_events_mix hands it to the pipeline render kernel; `events_kernel` is the same bank with ONE voice fading through the
 launch, which keeps it in the scheduler kernel (that one wave goes frame by frame) -- the like-for-like partner of the score kernel,
-which has no such shortcut and whose first block runs frame by frame (every note begins there)."""
+which has no such shortcut and whose first block runs frame by frame (every note begins there).
+Note path ("score_exec" = SCORE_NOTES, key "score_notes"): score (a) on pools of 64 and 8 192 voices (the second renders through the
+chunked scratch: 8 192 frames per chunk) and the sustained score, same method, same run; before anything is timed the [1][96 000] mix of
+the two executors is compared bit for bit.  `spread_ms` = max - min of the serial leg: the note path counts as faster only beyond it."""
 import argparse
 import json
 import os
@@ -94,6 +99,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-score", action="store_true", help="the events legs alone (a library without fdsp_bank_set_score)")
+    ap.add_argument("--skip-notes", action="store_true", help="no note-path legs (a library without the score_exec option)")
+    ap.add_argument("--serial-from", default=None, help="a result file of an earlier build (--skip-notes), kept under score_notes.serial_of_other_build")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "score_bench needs a HIP device"
     from fundsp_amd.score import assign_voices
@@ -113,6 +120,29 @@ def main():
             r.update(voices_used=int(voice.max()) + 1, packed_share_of_wave_blocks=packed_share(voice, start, end, pool))
             res["score"][str(pool)] = r
             print("score", pool, r, flush=True)
+            del b
+    if not a.skip_score and not a.skip_notes:
+        nt = res["score_notes"] = {}
+        for pool in (64, 8192):
+            voice = assign_voices(start, end, pool)
+            b = W.make_fm_svf_bank(pool, SR)
+            b.set_score(voice, start / SR, end / SR, FADE / SR, FADE / SR, F.FADE_SMOOTH, params=fm_rows(rows))
+            if pool == 64:                                             # the two executors at the bench's own size, before anything is timed
+                want = b.clone().process_events_mix(T_NOTES).cpu().numpy()
+                c = b.clone()
+                c.set_option("score_exec", F.SCORE_NOTES)
+                got = c.process_events_mix(T_NOTES).cpu().numpy()
+                nt["mix_bit_equal_to_serial"] = bool(np.array_equal(got.view(np.uint32), want.view(np.uint32)))
+                assert nt["mix_bit_equal_to_serial"], "score_exec 1 and 0 differ at the bench's size"
+                del c
+            b.set_option("score_exec", F.SCORE_NOTES)
+            b.mix_reserve(T_NOTES)
+            r = timed(b, T_NOTES, mix)
+            serial = res["score"][str(pool)]
+            r.update(chunk_frames=b.get_option("score_scratch_frames"), serial_median_ms=serial["median_ms"], serial_spread_ms=serial["max_ms"] - serial["min_ms"],
+                     speedup=serial["median_ms"] / r["median_ms"])
+            nt[str(pool)] = r
+            print("score, one lane per note", pool, r, flush=True)
             del b
     b = F.Bank("fm_svf", n)                                            # (b) one voice per note
     for name, values in fm_rows(rows).items():
@@ -136,7 +166,19 @@ def main():
     if not a.skip_score:
         b.set_score(np.arange(V_SUS), np.full(V_SUS, 0.0), np.full(V_SUS, 10.0))
         res["sustained"]["score"] = timed(b, T_SUS, mix)
+        if not a.skip_notes:                                            # one note per voice: nothing to parallelise, and the voice-out scratch to fill
+            b.set_option("score_exec", F.SCORE_NOTES)
+            b.mix_reserve(T_SUS)
+            res["score_notes"]["sustained"] = timed(b, T_SUS, mix)
+            res["score_notes"]["sustained"]["chunk_frames"] = b.get_option("score_scratch_frames")
     print("sustained", res["sustained"], flush=True)
+    if "score_notes" in res:
+        res["score_notes"]["one_voice_per_note_median_ms"] = res["one_voice_per_note"]["median_ms"]
+        if a.serial_from:
+            with open(a.serial_from) as fh:
+                other = json.load(fh)
+            res["score_notes"]["serial_of_other_build"] = dict(score=other.get("score"), one_voice_per_note=other.get("one_voice_per_note"),
+                                                               sustained=other.get("sustained"))
     line = json.dumps(res)
     if a.out:
         with open(a.out, "w") as fh:
