@@ -1614,8 +1614,11 @@ struct VGate {  // forwards to a slot visitor only while enabled; always advance
     template <class V> struct W {
         V* v;
         bool on;
-        FD_D void f(float& x, FieldKind k, const char* n) { if (on) v->f(x, k, n); else v->slot++; }
-        FD_D void fi(float& x, FieldKind k, const char* n, int i) { if (on) v->fi(x, k, n, i); else v->slot++; }
+        // ... or, for PARAM fields, while `par` is set: in a kernel whose loops run HoistOf<G> (`bounds`, set by the kernel body) a segment that
+        // starts behind a producer with an output bound reads the producer's parameters -- the bound is computed from them (Seg<Pipe>::visit).
+        bool bounds = false, par = false;
+        FD_D void f(float& x, FieldKind k, const char* n) { if (on || (par && k == PARAM)) v->f(x, k, n); else v->slot++; }
+        FD_D void fi(float& x, FieldKind k, const char* n, int i) { if (on || (par && k == PARAM)) v->fi(x, k, n, i); else v->slot++; }
         FD_D void u32(uint32_t& x, FieldKind k, const char* n) { if (on) v->u32(x, k, n); else v->slot++; }
         FD_D void u64(uint64_t& x, FieldKind k, const char* n) { if (on) v->u64(x, k, n); else v->slot += 2; }
         FD_D void enter(int) {}
@@ -1836,7 +1839,15 @@ struct Seg<Pipe<X, Y>, A, B, HEAD> {
     }
     static FD_D void begin(G& g, int n) {
         if constexpr (HX) SX::begin(g.x, n);
-        if constexpr (HY) SY::begin(g.y, n);
+        if constexpr (HY) {
+            // (a leaf: its one stage is this segment's.)  When x runs in another wave (!HX) this wave holds of x only what visit() below
+            // loaded for it: x's PARAM fields.  So OutBound<X>::get may read PARAM fields of x and nothing else -- no COEF, no STATE -- which
+            // holds for every specialisation in fd_nodes.hpp (Constant::value, Unop::scalar, constants).  A bounded node type that needs more
+            // must extend the gate in visit() with it.  The elided-constants form of a cut loads other fields and is excluded outright.
+            static_assert(!TakesBound<Y>::v || !ELIDE_IN, "a bound consumer behind a cut with elided constants: x's parameters are not loaded there");
+            if constexpr (TakesBound<Y>::v) begin_block_behind(g.x, g.y, n);
+            else SY::begin(g.y, n);
+        }
     }
     static FD_D void end(G& g) {
         if constexpr (HX) SX::end(g.x);
@@ -1849,7 +1860,9 @@ struct Seg<Pipe<X, Y>, A, B, HEAD> {
         return t;
     }
     template <class W> static FD_D void visit(G& g, W& w) {
-        if constexpr (HX) SX::visit(g.x, w); else if constexpr (ELIDE_IN) ConstTail<X>::visit(g.x, w); else { w.on = false; g.x.visit(w); }
+        // (y = a node that HoistOf turns into a consumer of x's output bound: the segment reads x's parameters although x runs elsewhere)
+        constexpr bool BOUND_IN = HY && OutBound<X>::has && WantsBound<Y>::v;
+        if constexpr (HX) SX::visit(g.x, w); else if constexpr (ELIDE_IN) ConstTail<X>::visit(g.x, w); else { w.on = false; w.par = BOUND_IN && w.bounds; g.x.visit(w); w.par = false; }
         if constexpr (HY) SY::visit(g.y, w); else { w.on = false; g.y.visit(w); }
     }
 };
@@ -2319,6 +2332,7 @@ FD_D void render_pipe_body(float* __restrict__ slots, size_t stride, size_t V, c
     if (live) {
         VLoad ld{slots + v, stride, 0};
         VGate::W<VLoad> gate{&ld, true};
+        gate.bounds = true;  // the rounds below run HoistOf<G>
         if (stage == 0) S0::visit(g, gate); else if (stage == 1) S1::visit(g, gate); else S2::visit(g, gate);
     }
     if constexpr (MIX != MIX_NONE) {
@@ -2339,7 +2353,8 @@ FD_D void render_pipe_body(float* __restrict__ slots, size_t stride, size_t V, c
         }
     }
     // The rounds, for the graph type GG: G itself, or its lowpass-specialised twin LpOf<G> (same registers, the
-    // packed SVF path 5 operations shorter) when every lane of THIS wave qualifies.  A wave that does not hold the SVF
+    // packed SVF path 5 operations shorter) when every lane of THIS wave qualifies -- either of them as HoistOf<..>: pipe_stage
+    // announces its items, so a Sine / FixedSvf behind a bounded producer checks its guard per block / per item (fd_nodes.hpp).  A wave that does not hold the SVF
     // segment sees zeroed coefficients, takes the generic type and runs the same arithmetic for its own segment.
     constexpr bool PFK = FD_PIPE_PREFETCH != 0 && GPW < 4;  // see pipe_stage: prefetch pays when the consumer wave is (nearly) alone on its SIMD
     // the stages' shapes: the LAST one owns the output (HBM rows, or the mix tile of a fused mix-down)
@@ -2418,7 +2433,7 @@ FD_D void render_pipe_body(float* __restrict__ slots, size_t stride, size_t V, c
         constexpr int heavy = (w0 >= w1 && w0 >= w2) ? 0 : (w1 >= w2 ? 1 : 2);
         if (S > 1 && stage == heavy) __builtin_amdgcn_s_setprio(1);
     }
-    if (lp) rounds_of((GL*)nullptr); else rounds_of((G*)nullptr);
+    if (lp) rounds_of((typename HoistOf<GL>::type*)nullptr); else rounds_of((typename HoistOf<G>::type*)nullptr);
     if (live && active) {
         VStore<false> st{slots + v, stride, 0};
         VGate::W<VStore<false>> gate{&st, true};

@@ -708,7 +708,10 @@ FD_HD float wide_sinf(float self) {
 // `tmax` accumulates the largest quadrant argument seen (one v_max3_f32): the shortcuts below are exact only while
 // it stays < 8192; the caller checks it once per 64-sample block and, if it tripped, re-renders that block with the
 // fully general scalar wide_sinf (optimistic execution + rollback keeps the hot loop branch-free).
-FD_HD v2f wide_sin2(v2f self, float& tmax) {
+// The form WITHOUT the tmax operand is for callers that have already established |quadrant index| < 8192 for every argument
+// they will pass (SineB::begin_block, fd_nodes.hpp: one check per block from a bound of the node's input); the form WITH it
+// is the same evaluation plus the v_max3_f32.
+FD_HD v2f wide_sin2(v2f self) {
     constexpr float DP1F = 0.78515625f * 2.0f;                 //  8 significant bits
     constexpr float DP2F = 2.4187564849853515625E-4f * 2.0f;   // 11 significant bits
     constexpr float DP3F = 3.77489497744594108E-8f * 2.0f;
@@ -727,7 +730,6 @@ FD_HD v2f wide_sin2(v2f self, float& tmax) {
     // Out-of-domain arguments (|quadrant index| >= 8192: more than ~2000 cycles of phase inside one 64-sample block,
     // where the exact-FMA shortcuts and wide's q > 2^25 overflow rule would matter) only raise tmax here.
     v2f t = self * TWO_OVER_PI;
-    tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, __builtin_fabsf(t.x)), __builtin_fabsf(t.y));  // one v_max3_f32 per pair
     // round(t) and its low integer bits from one add: for |t| < 2^13 the sum lies in [2^23, 2^24) where ulp = 1, so
     // ym = RNE(t) + MAGIC exactly, y = ym - MAGIC is exact, and mantissa(ym) = 0x400000 + RNE(t) (two's complement).
     v2f ym = t + MAGIC;
@@ -760,6 +762,12 @@ FD_HD v2f wide_sin2(v2f self, float& tmax) {
     uint32_t r1 = (f2u(c.y) & m1) | (f2u(s.y) & ~m1);
 #endif
     return v2f{u2f(r0 ^ ((b0 << 30) & 0x80000000u)), u2f(r1 ^ ((b1 << 30) & 0x80000000u))};
+}
+FD_HD v2f wide_sin2(v2f self, float& tmax) {
+    constexpr float TWO_OVER_PI = 2.0f / 3.14159274101257324f;
+    v2f t = self * TWO_OVER_PI;  // (the same product as in wide_sin2(self): one instruction after CSE)
+    tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, __builtin_fabsf(t.x)), __builtin_fabsf(t.y));  // one v_max3_f32 per pair
+    return wide_sin2(self);
 }
 
 // Scalar twin of wide_sin2 (same signed evaluation, same guard): used where two plain VALU ops beat one packed op.

@@ -296,6 +296,76 @@ struct Sine {
     }
 };
 
+// ---- output bounds: what lets a packed path check its guard once per block / item instead of once per frame ---------------
+// OutBound<T>::get(node) is a per-voice upper bound of |out| of a one-output node, computed from its PARAMETERS alone, valid
+// for every frame of every path (packed, rollback, remainder, tick) as long as the output is finite; `has` says at compile
+// time whether the node type states one (everything not listed below: no).  A consumer treats a NaN or infinite bound as
+// "no bound" at run time (its block check then fails and the tile is rendered by the scalar path, as the per-frame guard
+// would have had it).  Every operation carries a margin for its own rounding and for the rounding of the bound's own
+// arithmetic (round-to-nearest is monotonic -- |x| <= b implies |fl(x*s)| <= fl(b*|s|) -- so the margin is slack, not need).
+constexpr float BOUND_MARGIN = 1.0000005f;  // 1 + 4 ulp
+template <class T> struct OutBound {
+    static constexpr bool has = false;
+    static FD_HD float get(const T&) { return __builtin_inff(); }
+};
+template <> struct OutBound<Constant<1>> {
+    static constexpr bool has = true;
+    static FD_HD float get(const Constant<1>& c) { return __builtin_fabsf(c.value[0]); }
+};
+// |Sine's output| for ANY finite argument, in-domain or not.  The obvious "|x| <= pi/4 after the reduction, so |s|, |c| <= 1
+// plus an ulp" holds only while the Cody-Waite reduction is accurate: exhaustively over all 2^31 finite non-negative f32
+// arguments (wide_sinf is odd in its argument's sign bit) the host build of wide_sinf gives
+//     max |wide_sinf(x)| = 1.0 exactly         for |x * 2/pi| < 8192   (the packed path's domain; wide_sin2 == wide_sinf there),
+//     max |wide_sinf(x)| = 0x1.a1266ap+3 = 13.04  at x = 0x1.91b8d4p+25  overall
+// -- with quadrant indices near 2^25 the product y*DP1F and the index itself are off by whole units and the polynomials are
+// evaluated at |x| ~ 5.  (Past q = 2^25 wide's overflow rule returns 0 or +-1; an infinite or NaN argument gives NaN.)  The
+// rollback path and the process path's scalar frames use wide_sinf, the remainder and tick paths sinf_musl (|.| <= 1), so
+// the constant that holds for all of them is 16.  It costs nothing: the consumers' thresholds are 1.5 MHz of input
+// (SineB) and 2^96 (FixedSvfB).
+constexpr float SINE_OUT_BOUND = 16.0f;
+template <> struct OutBound<Sine> {
+    static constexpr bool has = true;
+    static FD_HD float get(const Sine&) { return SINE_OUT_BOUND; }
+};
+
+// Sine behind a producer with an output bound (Pipe<X, Sine> with OutBound<X>::has; HoistOf below puts it there): the
+// packed path's domain guard is decided ONCE PER BLOCK from the bound, and the frames run wide_sin2 without the tmax operand.
+//   Let B >= |in| for every frame, D = fl(B * |sample_duration|) >= |fl(in * sample_duration)| (monotonic rounding).  The
+//   unwrapped phase obeys |phase'| = |fl(phase + d)| <= (|phase| + D)(1 + 2^-24), so over the n <= 64 frames of a block
+//   every phase the sine is evaluated at satisfies |phase_k| <= (|phase_0| + n D)(1 + 2^-24)^64 < (|phase_0| + n D)(1 + 2^-17.9).
+//   The quadrant argument is t = fl(fl(phase * F32_TAU) * TWO_OVER_PI) with F32_TAU * TWO_OVER_PI = 4 (1 +- 2^-22), so
+//   |t| <= 4 |phase_k| (1 + 2^-21).  wide_sin2 needs |t| < 8192, i.e. |phase_k| < 2048 (1 - 2^-21); with the bound above that
+//   is |phase_0| + n D < 2048 (1 - 2^-17.5) = 2047.989.  The check below computes |phase_0| + n D in f32 (two roundings,
+//   relative 2^-23) and compares with 2047: a margin of one whole turn (2^-11) where 2^-17 is needed.
+// A block whose bound fails the check -- or whose bound is NaN / infinite -- gets tmax = inf and is rendered by the scalar
+// path exactly as a tripped per-frame guard would have it.  The bound taken at the block start covers every wave that walks
+// the block, also one that skips part of it (skip2 performs the same recurrence).  The -0.0 rule is Sine's.
+// Layout-identical to Sine.  begin_block(int) without a bound (a caller that does not know the producer) trips always.
+struct SineB : Sine {
+    static constexpr float TURNS_MAX = 2047.0f;
+    FD_HD void begin_block(int) { tmax = __builtin_inff(); }
+    FD_HD void begin_block(int size, float in_bound) {
+        const float pmax = __builtin_fabsf(phase) + (float)size * (in_bound * __builtin_fabsf(sample_duration));
+        tmax = (pmax < TURNS_MAX && f2u(phase) != 0x80000000u) ? 0.0f : __builtin_inff();  // (NaN compares false)
+    }
+    template <int PH> FD_HD void step2(const v2f* in, v2f* out) {
+        if (PH == PH_SIMD) {
+            v2f d = in[0] * sample_duration;
+            float t0 = phase;
+            phase += d.x;
+            float t1 = phase;
+            phase += d.y;
+            out[0] = wide_sin2(v2f{t0, t1} * F32_TAU);
+        } else {
+            Sine::template step2<PH>(in, out);
+        }
+    }
+};
+template <> struct OutBound<SineB> {
+    static constexpr bool has = true;
+    static FD_HD float get(const SineB&) { return SINE_OUT_BOUND; }
+};
+
 // Sine in tolerance mode (FDSP_MATH_FAST): the phase recurrence of Sine::process is kept operation for operation, the
 // f32x8 sine polynomial is replaced by fast_sin (fd_math.hpp; within 1.2e-7 of it).  tick / remainder samples unchanged.
 struct SineFast : Sine {
@@ -459,18 +529,19 @@ struct SvfCore {
     // unfused form round the same real number once -- identical bits -- EXCEPT when 2*v overflows (|v| >= 2^127): the
     // reference's product becomes inf there while the fused form stays finite.  `vmax` accumulates max(|v1|, |v2|)
     // (one v_max3_f32); the caller checks it per tile and re-renders the tile with tick() if it reached 2^127.
-    FD_HD float tick_fused(float v0, float& vmax) {
+    // (TRACK = false: the caller has established |v1|, |v2| < 2^127 for the frame some other way -- FixedSvfB below)
+    template <bool TRACK = true> FD_HD float tick_fused(float v0, float& vmax) {
         float v3 = v0 - ic2eq;
         float v1 = a1 * ic1eq + a2 * v3;
         float v2 = ic2eq + a2 * ic1eq + a3 * v3;
-        FD_SVF_TRACK(vmax, v1, v2);
+        if (TRACK) FD_SVF_TRACK(vmax, v1, v2);
         ic1eq = __builtin_fmaf(2.0f, v1, -ic1eq);
         ic2eq = __builtin_fmaf(2.0f, v2, -ic2eq);
         return m0 * v0 + m1 * v1 + m2 * v2;
     }
     // ... and when m0 = m1 = +0.0 and m2 = 1.0 (LowpassMode): `m0*v0 + m1*v1 + m2*v2` = (+-0 + +-0) + v2 is v2 itself,
     // bit for bit, whenever v0, v1 are finite and v2 is not -0.0 -- FixedSvfLp guards both (see there).
-    FD_HD float tick_lp(float v0, float& vmax) {
+    template <bool TRACK = true> FD_HD float tick_lp(float v0, float& vmax) {
         // The two state equations as ONE <2 x float> computation (same operations, same order, per component): a lone
         // wave issues one VALU instruction per ~4-5 cycles whatever its width (profiles/r03_ubench_issue.txt), and this
         // recurrence is what the filter wave's issue slots go to -- 8 slots per frame instead of 11.
@@ -480,7 +551,7 @@ struct SvfCore {
         const float s = ic2eq + a2 * ic1eq;
         const v2f q = v2f{v3, v3} * v2f{a2, a3};
         const v2f v = v2f{u, s} + q;
-        FD_SVF_TRACK(vmax, v.x, v.y);
+        if (TRACK) FD_SVF_TRACK(vmax, v.x, v.y);
         const v2f ic = __builtin_elementwise_fma(splat2(2.0f), v, -v2f{ic1eq, ic2eq});
         ic1eq = ic.x;
         ic2eq = ic.y;
@@ -561,6 +632,77 @@ struct FixedSvfLp : FixedSvf {
 };
 FD_HD bool svf_is_plain_lowpass(const FixedSvf& f) {
     return f2u(f.c.m0) == 0u && f2u(f.c.m1) == 0u && f2u(f.c.m2) == 0x3f800000u && f2u(f.c.ic2eq) != 0x80000000u;
+}
+
+// FixedSvf / FixedSvfLp behind a producer with an output bound, in a packed loop that announces its 8-frame items
+// (item_begin below; HoistOf puts the types there): the |v| < 2^127 guard of the fused state update is decided ONCE PER ITEM
+// from the state at the item's start, and the frames run without the per-frame v_max3_f32.
+//   Let u = 2^-24, A = max(1, |a1|, |a2|, |a3|), B >= |v0| for every frame, and M = max(|ic1eq|, |ic2eq|, B) before a frame.
+//   The frame computes (each operation rounded once, nothing contracted but the two explicit FMAs):
+//     v3 = v0 - ic2                       |v3|   <= 2M (1+u)
+//     v1 = a1*ic1 + a2*v3                 |v1|   <= (AM(1+u) + 2AM(1+u)^2)(1+u)              <= 3AM (1+u)^3
+//     v2 = (ic2 + a2*ic1) + a3*v3         |v2|   <= ((M + AM(1+u))(1+u) + 2AM(1+u)^2)(1+u)   <= 4AM (1+u)^3     (M <= AM)
+//     ic1' = fma(2, v1, -ic1)             |ic1'| <= (6AM(1+u)^3 + M)(1+u)                    <= 7AM (1+u)^4
+//     ic2' = fma(2, v2, -ic2)             |ic2'| <= (8AM(1+u)^3 + M)(1+u)                    <= 9AM (1+u)^4
+//   so M' = max(|ic1'|, |ic2'|, B) < 10 A M, and in frame k = 0 .. 7 of an item that starts with M_0
+//     |v1|, |v2| <= 4A (1+u)^3 (10A)^k M_0 <= 4.0001e7 A^8 M_0 < 2^25.3 A^8 M_0.
+//   (An underflowing operation adds at most 2^-149 instead of a relative u: nowhere near 2^127.)  Hence A^8 M_0 < 2^96 at
+//   the item's start keeps |v| < 2^121.3 < 2^127 through the item: 2*v never overflows and fma(2, v, -ic) == 2*v - ic bit
+//   for bit.  The f32 evaluation of A^8 (three squarings, each within u) and of the product eats 2^-21 of 2^5.7 of slack.
+// item(): vmax = max(vmax, |ic1eq|, |ic2eq|) -- ONE v_max3_f32 per item; begin_block seeds vmax with B.  tripped() asks
+// vmax * A^8 < 2^96 per tile: it fails for an infinite state or bound (vmax = inf), for an overflowing A^8 (inf, or 0 * inf
+// = NaN) and for a NaN bound (seeded as inf) -- always on the slow, exact side.  NaN states and inputs need no guard: the
+// fused and the unfused update both give NaN (and the per-frame guard, a v_max3, ignored NaNs as well).
+// Layout-identical to FixedSvf.  begin_block(int) without a bound trips always.
+FD_HD bool svf_item_guard_ok(const SvfCore& c, float vmax) {
+    const float A = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(1.0f, __builtin_fabsf(c.a1)), __builtin_fabsf(c.a2)), __builtin_fabsf(c.a3));
+    const float A2 = A * A, A4 = A2 * A2, A8 = A4 * A4;
+    return vmax * A8 < 0x1p96f;
+}
+#define FD_SVF_BOUNDED_GUARD                                                                                              \
+    FD_HD void begin_block(int) { vmax = __builtin_inff(); }                                                              \
+    FD_HD void begin_block(int, float in_bound) { vmax = in_bound < __builtin_inff() ? __builtin_fabsf(in_bound) : __builtin_inff(); } \
+    FD_HD void item() { vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(c.ic1eq)), __builtin_fabsf(c.ic2eq)); }
+struct FixedSvfB : FixedSvf {
+    FD_SVF_BOUNDED_GUARD
+    FD_HD bool tripped() const { return !svf_item_guard_ok(c, vmax); }
+    template <int PH> FD_HD void step2(const v2f* in, v2f* out) {
+        if (PH == PH_SIMD) {
+            const float a = c.template tick_fused<false>(in[0].x, vmax);
+            const float b = c.template tick_fused<false>(in[0].y, vmax);
+            out[0] = v2f{a, b};
+        } else {
+            FixedSvf::template step2<PH>(in, out);
+        }
+    }
+};
+struct FixedSvfLpB : FixedSvfLp {
+    FD_SVF_BOUNDED_GUARD
+    FD_HD bool tripped() const {  // ... and FixedSvfLp's end-state test (a tile that met an infinite v0 / v1, or a NaN)
+        return !(svf_item_guard_ok(c, vmax) && __builtin_fabsf(c.ic1eq) < __builtin_inff() && __builtin_fabsf(c.ic2eq) < __builtin_inff());
+    }
+    template <int PH> FD_HD void step2(const v2f* in, v2f* out) {
+        if (PH == PH_SIMD) {
+            const float a = c.template tick_lp<false>(in[0].x, vmax);
+            const float b = c.template tick_lp<false>(in[0].y, vmax);
+            out[0] = v2f{a, b};
+        } else {
+            FixedSvf::template step2<PH>(in, out);
+        }
+    }
+};
+// TakesBound<Y>: Y's begin_block wants the bound of what feeds it (Pipe::begin_block, Seg<Pipe>::begin hand it over)
+template <class T> struct TakesBound { static constexpr bool v = false; };
+template <> struct TakesBound<SineB> { static constexpr bool v = true; };
+template <> struct TakesBound<FixedSvfB> { static constexpr bool v = true; };
+template <> struct TakesBound<FixedSvfLpB> { static constexpr bool v = true; };
+// WantsBound<Y>: Y takes a bound, or is what HoistOf (below) replaces by a node that does
+template <class T> struct WantsBound { static constexpr bool v = TakesBound<T>::v; };
+template <> struct WantsBound<Sine> { static constexpr bool v = true; };
+template <> struct WantsBound<FixedSvf> { static constexpr bool v = true; };
+template <> struct WantsBound<FixedSvfLp> { static constexpr bool v = true; };
+template <class X, class Y> FD_HD void begin_block_behind(const X& x, Y& y, int n) {  // y's begin_block as the consumer of x
+    if constexpr (TakesBound<Y>::v) y.begin_block(n, OutBound<X>::get(x)); else y.begin_block(n);
 }
 
 // Svf<f32, M> with parameter inputs  svf.rs:748-855 (ID 36).  NIN = 3 (audio, cutoff, q) or 4 (+ gain).
@@ -3490,7 +3632,7 @@ struct Pipe {
     FD_HD void reset() { x.reset(); y.reset(); }
     FD_HD uint64_t ping(bool probe, uint64_t h) { return y.ping(probe, x.ping(probe, atto(h, ID))); }  // :1459
     FD_HD void end_simd() { x.end_simd(); y.end_simd(); }
-    FD_HD void begin_block(int n) { x.begin_block(n); y.begin_block(n); }
+    FD_HD void begin_block(int n) { x.begin_block(n); begin_block_behind(x, y, n); }
     FD_HD void bind(Ctx& a) { x.bind(a); y.bind(a); }
     FD_HD bool tripped() const { return x.tripped() || y.tripped(); }
     template <int PH> FD_HD void step(const float* in, float* out) {
@@ -3622,6 +3764,20 @@ struct Unop {
     template <int PH> FD_HD void skip2(const v2f* in) { x.template skip2<PH>(in); }
 };
 
+// output bounds of the combinators (OutBound, above): a Pipe states its last node's, x * s and x + s follow from x's
+template <class X, class Y> struct OutBound<Pipe<X, Y>> {
+    static constexpr bool has = OutBound<Y>::has;
+    static FD_HD float get(const Pipe<X, Y>& g) { return OutBound<Y>::get(g.y); }
+};
+template <class X> struct OutBound<Unop<X, UMulScalar>> {
+    static constexpr bool has = OutBound<X>::has && X::OUT == 1;
+    static FD_HD float get(const Unop<X, UMulScalar>& g) { return OutBound<X>::get(g.x) * __builtin_fabsf(g.scalar) * BOUND_MARGIN; }
+};
+template <class X> struct OutBound<Unop<X, UAddScalar>> {
+    static constexpr bool has = OutBound<X>::has && X::OUT == 1;
+    static FD_HD float get(const Unop<X, UAddScalar>& g) { return (OutBound<X>::get(g.x) + __builtin_fabsf(g.scalar)) * BOUND_MARGIN; }
+};
+
 // ---- type-level variants of a graph -------------------------------------------------------------------------------
 // A variant replaces leaf types by layout-identical derived types (same fields, same visit order, same ID) that differ
 // only in the arithmetic of the packed path; the combinators Pipe / Stack / Binop / Unop carry the replacement through.
@@ -3642,6 +3798,23 @@ template <int N> struct FastOf<Moog<N>> { using type = MoogFast<N>; };
 FD_VARIANT_THROUGH(LpOf)
 FD_VARIANT_THROUGH(FastOf)
 FD_VARIANT_THROUGH(PlainOf)
+// HoistOf<G>: behind a producer that states an output bound, Sine -> SineB and FixedSvf / FixedSvfLp -> FixedSvfB / FixedSvfLpB
+// (guards checked per block / per item).  Chosen at COMPILE time by the packed loops that announce their items (item_begin):
+// the voice-minor stage pipeline (render_pipe_body; see below for the time-split kernels).  Every other loop, and every Sine / FixedSvf without such a producer
+// (a leaf fed from an input stream, a producer without a bound), keeps the per-frame guards.  Exact.
+template <bool C, class A, class B> struct Pick { using type = A; };
+template <class A, class B> struct Pick<false, A, B> { using type = B; };
+template <class G> struct HoistOf { using type = G; };
+FD_VARIANT_THROUGH(HoistOf)
+template <class X> struct HoistOf<Pipe<X, Sine>> { using type = Pipe<typename HoistOf<X>::type, typename Pick<OutBound<X>::has, SineB, Sine>::type>; };
+template <class X> struct HoistOf<Pipe<X, FixedSvf>> { using type = Pipe<typename HoistOf<X>::type, typename Pick<OutBound<X>::has, FixedSvfB, FixedSvf>::type>; };
+template <class X> struct HoistOf<Pipe<X, FixedSvfLp>> { using type = Pipe<typename HoistOf<X>::type, typename Pick<OutBound<X>::has, FixedSvfLpB, FixedSvfLp>::type>; };
+// The time-split kernels do NOT take HoistOf: their code is the per-frame guards', instruction for instruction.  On the 16 384- /
+// 8 192-voice shards (not power-bound) the hoisted forms measured SLOWER in same-session A/Bs (profiles/guard_hoist_bench.json, DESIGN.md
+// 6.19): both guards hoisted +4 %, the sines' alone +7 %.  In the filter wave -- one dependent chain -- the per-frame v_max3_f32 sits
+// in the wait state between the v_pk_fma_f32 that produces the state and the first multiply that reads it; without it the compiler
+// puts an s_nop there (7 VALU + 2 s_nop per frame instead of 8 + 1).  Those kernels also respond to code placement alone (+2.8 %
+// from a longer prologue in front of unchanged loops), so the two figures are not clean either way.
 template <class A, class B> struct SameType { static constexpr bool v = false; };
 template <class A> struct SameType<A, A> { static constexpr bool v = true; };
 template <class T> struct Pointee;
@@ -3666,6 +3839,8 @@ template <class X, class U> FD_HD bool lp_ok(const Unop<X, U>& g) { return lp_ok
 // pairs are issued back to back instead of one L2 round trip per pair.  Reaches through the plain combinators only.
 template <class G> FD_HD void item_begin(G&) {}
 template <int SET, int NOUT> FD_HD void item_begin(WaveSynth<SET, NOUT>& w) { w.item_pos = 0; }
+FD_HD void item_begin(FixedSvfB& f) { f.item(); }    // the item's guard: one v_max3_f32 over the state at its start
+FD_HD void item_begin(FixedSvfLpB& f) { f.item(); }
 template <class X, class Y> FD_HD void item_begin(Pipe<X, Y>& g);
 template <class X, class Y> FD_HD void item_begin(Stack<X, Y>& g);
 template <class O, class X, class Y> FD_HD void item_begin(Binop<O, X, Y>& g);
