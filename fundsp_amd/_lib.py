@@ -76,6 +76,11 @@ SYMBOLS = {
     "fdsp_reverb_stereo_create": (_i, [_sz, _d, _d, _d, C.POINTER(_P)]),
     "fdsp_reverb4_stereo_create": (_i, [_sz, _d, _d, C.POINTER(_P)]),
     "fdsp_reverb4_stereo_create_on": (_i, [_i, _sz, _d, _d, C.POINTER(_P)]),
+    "fdsp_reverb4_stereo_delays_create": (_i, [_sz, _fp, _i, _d, C.POINTER(_P)]),
+    "fdsp_reverb4_stereo_delays_create_on": (_i, [_i, _sz, _fp, _i, _d, C.POINTER(_P)]),
+    "fdsp_reverb4_set_delays": (_i, [_P, _fp, _sz, _sz]),
+    "fdsp_bank_fitness_reserve": (_i, [_P]),
+    "fdsp_bank_reverb_fitness": (_i, [_P, _P, _P, _P]),
     "fdsp_reverb3_stereo_create": (_i, [_sz, _d, _d, _f, C.POINTER(_P)]),
     "fdsp_reverb3_stereo_create_on": (_i, [_i, _sz, _d, _d, _f, C.POINTER(_P)]),
     "fdsp_reverb3_stereo_svf_create": (_i, [_sz, _d, _d, _i, _f, _f, _f, C.POINTER(_P)]),

@@ -221,6 +221,50 @@ class Bank:
         return cls("reverb4_stereo", instances, _handle=h)
 
     @classmethod
+    def reverb4_stereo_delays(cls, instances, delays, time, device=-1):
+        """Bank of `instances` x reverb4_stereo_delays(delays, time) (prelude.rs:1917-1941) through the lane-per-frame kernel
+        (fdsp_reverb4_stereo_delays_create).  `delays`: [32] f32 seconds for the whole bank, or [instances, 32] for a table per instance --
+        the candidates of examples/optimize.rs.  Every delay must be at least 128 samples at DEFAULT_SR; the rings hold the longest delay
+        given here or 0.105 s, whichever is larger (set_delays replaces rows up to that)."""
+        V = int(instances)
+        d = np.ascontiguousarray(delays, dtype=np.float32)
+        if d.shape not in ((32,), (V, 32)):
+            raise ValueError(f"reverb4_stereo_delays: delays take [32] or [instances, 32], got {d.shape}")
+        h = C.c_void_p()
+        check(lib().fdsp_reverb4_stereo_delays_create_on(int(device), V, _fptr(d), 1 if d.ndim == 2 else 0, float(time), C.byref(h)))
+        b = cls("reverb4_stereo", V, _handle=h)
+        b.per_instance = d.ndim == 2
+        return b
+
+    def set_delays(self, delays, first=0):
+        """Replace delay rows from `first` of a reverb4_stereo_delays bank (fdsp_reverb4_set_delays): [32] for one row, [rows, 32] for several
+        (rows are instances with per-instance tables, else the single row 0).  The instances whose row changes are reset."""
+        d = np.ascontiguousarray(delays, dtype=np.float32)
+        if d.ndim == 1:
+            d = d[None]
+        if d.ndim != 2 or d.shape[1] != 32:
+            raise ValueError(f"set_delays: delays take [32] or [rows, 32], got {d.shape}")
+        check(lib().fdsp_reverb4_set_delays(self._h, _fptr(d), int(first), d.shape[0]))
+
+    def fitness_reserve(self):
+        """Allocate the scratch reverb_fitness renders into (fdsp_bank_fitness_reserve): the call itself then allocates nothing."""
+        check(lib().fdsp_bank_fitness_reserve(self._h))
+
+    def reverb_fitness(self, terms=False, stream=None):
+        """reverb_fitness (reverb.rs:31-139) of every instance of a stereo effect bank, on the device (fdsp_bank_reverb_fitness): a device
+        tensor [instances]; with `terms` also [instances, 4] = echo_0, pen_0, echo_1, pen_1.  The bank is reset before and after."""
+        import torch
+
+        dev = torch.device("cuda", self.device())   # the bank's device, whichever is current
+        fit = torch.empty(self.voices, dtype=torch.float32, device=dev)
+        tt = torch.empty((self.voices, 4), dtype=torch.float32, device=dev) if terms else None
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().fdsp_bank_reverb_fitness(self._h, C.c_void_p(fit.data_ptr()), C.c_void_p(tt.data_ptr()) if terms else None,
+                                             C.c_void_p(stream) if stream else None))
+        return (fit, tt) if terms else fit
+
+    @classmethod
     def reverb3_stereo(cls, instances, time, diffusion, cutoff, device=-1, svf=None, q=1.0, gain=1.0):
         """Bank of `instances` x reverb3_stereo(time, diffusion, filter) (prelude.rs:1858-1871, reverb.rs:152-279: the allpass-loop reverb) through its
         lane-per-frame kernel.  The loop filter: lowpole_hz(cutoff) (the documented one; fdsp_reverb3_stereo_create), or with `svf` = "lowpass" ..

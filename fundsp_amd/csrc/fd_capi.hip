@@ -16,6 +16,7 @@
 
 #include "../../include/fundsp_hip.h"
 #include "fd_engine.hpp"
+#include "fd_fitness.hpp"
 #include "fd_fxbank.hpp"
 #include "fd_opts.hpp"
 
@@ -450,6 +451,13 @@ struct fdsp_bank {
     float* score_stage = nullptr;
     float* score_scratch = nullptr;
     size_t score_scratch_n = 0;
+    // fdsp_bank_reverb_fitness (fd_fitness.hpp): the impulse [V][2][N] and behind it the response [V][2][N] the call renders -- the render
+    // kernels take one stride for input and output -- and the twiddle / window tables.  Allocated by fdsp_bank_fitness_reserve or the first
+    // call, kept until the bank goes, not cloned.  The four terms per instance land in the head of the impulse half once it has been read.
+    float* fit_scratch = nullptr;
+    float* fit_tables = nullptr;
+    int fit_allocs = 0;                                // device allocations made for it so far ("fitness_allocs": 2 once reserved, for good)
+    hipEvent_t fit_e0 = nullptr, fit_e1 = nullptr;     // around the scoring kernels of the last call ("fitness_score_us")
 };
 
 namespace {
@@ -880,6 +888,17 @@ int fdsp_bank_get_option(const fdsp_bank* b, const char* name) {
         const size_t per = (size_t)fdsp_bank_outputs(b) * b->V;
         return per ? (int)(b->score_scratch_n / per) : 0;
     }
+    if (name && std::strcmp(name, "fitness_scratch_kib") == 0)  // KiB of fdsp_bank_reverb_fitness scratch the bank holds now (read-only; 0: none yet)
+        return b->fit_scratch && b->fit_tables ? (int)((2 * b->V * 2 * (size_t)fd::FIT_N * sizeof(float)) >> 10) : 0;
+    if (name && std::strcmp(name, "fitness_allocs") == 0) return b->fit_allocs;  // device allocations made for the fitness calls so far (read-only)
+    if (name && std::strcmp(name, "fitness_score_us") == 0) {  // device time of the scoring kernels of the last fdsp_bank_reverb_fitness, microseconds (waits for them)
+        float ms = 0.0f;
+        if (!b->fit_e1 || hipEventSynchronize(b->fit_e1) != hipSuccess || hipEventElapsedTime(&ms, b->fit_e0, b->fit_e1) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FDSP_EINVAL, "fitness_score_us: no fdsp_bank_reverb_fitness call to report");
+        }
+        return (int)(ms * 1000.0f + 0.5f);
+    }
     return fail(FDSP_EINVAL, "unknown bank option");
 }
 
@@ -1114,6 +1133,31 @@ int fdsp_reverb4_stereo_create_on(int device, size_t instances, double room_size
     return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_reverb_stereo(instances, 2, room_size, time, 0.0, s, fx); }, room_size, time);
 }
 
+int fdsp_reverb4_stereo_delays_create(size_t instances, const float* delays, int per_instance, double time, fdsp_bank** out) {
+    return fdsp_reverb4_stereo_delays_create_on(-1, instances, delays, per_instance, time, out);
+}
+int fdsp_reverb4_stereo_delays_create_on(int device, size_t instances, const float* delays, int per_instance, double time, fdsp_bank** out) {
+    if (out) *out = nullptr;
+    if (!delays) return fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: delays NULL");
+    if (per_instance != 0 && per_instance != 1) return fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: per_instance takes 0 or 1");
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: no instances");
+    const size_t n = (per_instance ? instances : 1) * 32;
+    for (size_t i = 0; i < n; i++) {
+        if (!(delays[i] >= 0.0f) || !(delays[i] < 1e6f)) return fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+        if (std::round((double)delays[i] * FDSP_DEFAULT_SR) < 128.0)
+            return fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+    }
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_reverb4_delays(instances, delays, per_instance, time, s, fx); }, 1.0, time);
+}
+int fdsp_reverb4_set_delays(fdsp_bank* b, const float* delays, size_t first, size_t count) {
+    if (!b || !delays) return fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: bank or delays NULL");
+    DeviceGuard guard(b->device);
+    HIPCHK(await_last_render(b));
+    if (int rc = fd::fx_reverb4_set_delays(b->fx.get(), delays, first, count, b->stream)) return rc;
+    HIPCHK(sync_bank_stream(b));
+    return FDSP_OK;
+}
+
 int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (lines != 2 && lines != 4 && lines != 8 && lines != 16 && lines != 32) return fail(FDSP_EINVAL, "fdsp_fdn_create: lines takes 2, 4, 8, 16 or 32 (FrameHadamard needs a power of two; the kernel holds at most 32 lines in registers)");
@@ -1304,6 +1348,10 @@ void fdsp_bank_destroy(fdsp_bank* b) {
     if (b->score_stage) hipFree(b->score_stage);
     if (b->score_scratch) hipFree(b->score_scratch);
     if (b->panw) hipFree(b->panw);
+    if (b->fit_scratch) hipFree(b->fit_scratch);
+    if (b->fit_tables) hipFree(b->fit_tables);
+    if (b->fit_e0) hipEventDestroy(b->fit_e0);
+    if (b->fit_e1) hipEventDestroy(b->fit_e1);
     if (b->st_in) hipFree(b->st_in);
     if (b->st_out) hipFree(b->st_out);
     if (b->pin_in) hipHostFree(b->pin_in);
@@ -1641,6 +1689,74 @@ int fdsp_bank_process(fdsp_bank* b, size_t frames, const float* d_in, float* d_o
         b->timed = timing;
         b->ext_pending = s != b->stream;
     }
+    return FDSP_OK;
+}
+
+// ---- reverb_fitness per instance (fd_fitness.hpp) -----------------------------------------------------------------------------------------
+namespace {
+int fitness_bank(const fdsp_bank* b, const char* who) {
+    if (!b) return fail(FDSP_EINVAL, std::string(who) + ": bank is NULL");
+    if (!b->fx) return fail(FDSP_ENOTSUP, std::string(who) + ": effect banks only (reverb_fitness scores a stereo reverb unit, not a voice bank)");
+    if (b->fx->inputs() != 2 || b->fx->outputs() != 2) return fail(FDSP_ENOTSUP, std::string(who) + ": the bank must have 2 inputs and 2 outputs (An<impl AudioNode<Inputs = U2, Outputs = U2>>)");
+    return FDSP_OK;
+}
+int fitness_reserve(fdsp_bank* b) {
+    if (b->fit_scratch && b->fit_tables && b->fit_e1) return FDSP_OK;
+    if (!b->fit_tables) {
+        std::vector<float> tab(fd::FIT_TABLE_FLOATS);
+        fd::fit_make_tables(tab.data());
+        float* p = nullptr;
+        hipError_t e = hipMalloc((void**)&p, tab.size() * sizeof(float));
+        if (e != hipSuccess) return fail(FDSP_ENOMEM, std::string("hipMalloc(fitness tables): ") + hipGetErrorString(e));
+        e = hipMemcpy(p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(p); return fail(FDSP_EDEVICE, hipGetErrorString(e)); }
+        b->fit_tables = p;
+        b->fit_allocs++;
+    }
+    if (!b->fit_scratch) {
+        const hipError_t e = hipMalloc((void**)&b->fit_scratch, 2 * b->V * 2 * (size_t)fd::FIT_N * sizeof(float));
+        if (e != hipSuccess) { b->fit_scratch = nullptr; return fail(FDSP_ENOMEM, std::string("hipMalloc(fitness scratch): ") + hipGetErrorString(e)); }
+        b->fit_allocs++;
+    }
+    if (!b->fit_e0) HIPCHK(hipEventCreate(&b->fit_e0));
+    if (!b->fit_e1) HIPCHK(hipEventCreate(&b->fit_e1));
+    return FDSP_OK;
+}
+}  // namespace
+
+int fdsp_bank_fitness_reserve(fdsp_bank* b) {
+    if (int rc = fitness_bank(b, "fdsp_bank_fitness_reserve")) return rc;
+    DeviceGuard guard(b->device);
+    return fitness_reserve(b);
+}
+
+int fdsp_bank_reverb_fitness(fdsp_bank* b, float* d_fitness, float* d_terms, void* stream) {
+    if (int rc = fitness_bank(b, "fdsp_bank_reverb_fitness")) return rc;
+    if (!d_fitness) return fail(FDSP_EINVAL, "fdsp_bank_reverb_fitness: d_fitness is NULL");
+    DeviceGuard guard(b->device);
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s != b->stream) hipStreamIsCapturing(s, &cap);
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(FDSP_EINVAL, "fdsp_bank_reverb_fitness during a stream capture: the call resets the bank and may allocate its scratch (capture of a fitness call is out of scope)");
+    if (int rc = order_after_bank_stream(b, s)) return rc;
+    if (int rc = fitness_reserve(b)) return rc;
+    if (b->ext_pending) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
+    resolve_opts(b);
+    const size_t half = b->V * 2 * (size_t)fd::FIT_N;
+    float *imp = b->fit_scratch, *resp = b->fit_scratch + half;
+    HIPCHK(b->fx->reset(s));
+    fd::fit_launch_impulse(imp, b->V * 2, s);
+    b->fx->render(imp, resp, (size_t)fd::FIT_N, (size_t)fd::FIT_N, FDSP_LAYOUT_PLANAR, 0, false, s);   // PROCESS mode, planar
+    b->last_kernel = fd::tl_opts.last_kernel;
+    HIPCHK(hipEventRecord(b->fit_e0, s));
+    fd::fit_launch_score(resp, b->fit_tables, b->V, d_terms ? d_terms : imp, d_fitness, s);   // (the impulse has been read: its head takes the terms)
+    HIPCHK(hipEventRecord(b->fit_e1, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(b->fx->reset(s));   // the bank is left as constructed
+    if (s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
+    b->timed = false;
+    b->ext_pending = s != b->stream;
     return FDSP_OK;
 }
 

@@ -103,6 +103,25 @@ void fdn_make_const_reverb4(double room_size, double time, double sample_rate, F
     c->out_scale = (float)(1.0 / 4.0);
 }
 
+int fdn_make_table_reverb4(const float* delays, size_t rows, double time, double sample_rate, double hold_seconds, int* lens, FdnConst* c) {
+    fdn_make_const_reverb4(10.0, time, sample_rate, c);  // reverb4_stereo_delays :1921-1922: room_size = 10.0 in `a`; weights, pans, scales
+    if (!(hold_seconds * sample_rate < (double)(1 << 19))) return -1;
+    int maxlen = (int)std::round(hold_seconds * sample_rate) + 1, shortest = 1 << 30;
+    for (size_t i = 0; i < rows * 32; i++) {
+        const double samples = std::round((double)delays[i] * sample_rate);  // Delay::new(d as f64), set_sample_rate delay.rs:108
+        if (!(samples < (double)(1 << 19))) return -1;
+        lens[i] = (int)samples + 1;
+        maxlen = lens[i] > maxlen ? lens[i] : maxlen;
+        shortest = lens[i] - 1 < shortest ? lens[i] - 1 : shortest;
+    }
+    for (int k = 0; k < 32; k++) c->len[k] = lens[k];  // (the first row's: the kernel reads the table)
+    int cap = 256;
+    while (cap < maxlen) cap <<= 1;
+    c->cap = cap;
+    c->ring_stride = (size_t)32 * ((size_t)cap + 64);
+    return cap > (1 << 18) ? -1 : shortest;
+}
+
 void fdn_make_const_generic(const FdnDesc& d, double sample_rate, FdnConst* c) {
     *c = FdnConst{};
     int maxlen = 0;
@@ -442,6 +461,87 @@ __global__ __launch_bounds__(256) void k_fdn_render_frames(FdnConst c, FdnState 
     if (lane < 32) fdn_state_store<3>(s, inst, lane, hist, fbr);
 }
 
+// ---- reverb4_stereo_delays with a delay table per instance, lane = FRAME --------------------------------------------------------------------
+// k_fdn_render_frames<., 2> with the ring lengths of the wave's instance read from a row of a device table: `lens + inst * lens_stride` is
+// wave-uniform, so the 32 lengths of a block's ring fetch are scalar loads (the table is only ever read here), and the ring capacity is a
+// run-time value as in k_fdn_frames_generic.  Everything else is the two-section kernel's sequence of steps, in the same order: the same
+// samples for the same lengths.
+struct FdnTableLines {
+    const int* __restrict__ lens;
+    const FdnConst& c;
+    __device__ __forceinline__ int len(int k) const { return lens[k]; }
+    __device__ __forceinline__ float w(int j, int) const { return c.w[j]; }
+};
+
+__global__ __launch_bounds__(256) void k_fdn_render_frames_table(FdnConst c, FdnState s, const int* __restrict__ lens, size_t lens_stride, size_t V,
+                                                                 const float* __restrict__ in, float* __restrict__ out, size_t T, size_t fstride,
+                                                                 int layout, int tick_mode, FdnBus bus) {
+    constexpr int NL = 16;  // lines per network
+    __shared__ float hist_all[4][32 * HS];  // per line: delay outputs d[n-2], d[n-1] | d[0..63]
+    __shared__ float fbr_all[4][32 * HS];   // per line: fb[-1] | fb[0..63]
+    __shared__ float sc_wl[32], sc_wr[32];  // pan weights: an LDS broadcast read per use
+    if (threadIdx.x < 32) {
+        sc_wl[threadIdx.x] = c.wl[threadIdx.x];
+        sc_wr[threadIdx.x] = c.wr[threadIdx.x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* hist = hist_all[wib];
+    float* fbr = fbr_all[wib];
+    const size_t inst = (size_t)blockIdx.x * 4 + wib;
+    if (inst >= V) return;
+    const FdnTableLines p{lens + inst * lens_stride, c};
+    const FdnOut io{out, V, T, fstride, inst, layout, lane};
+    const int CMASK = c.cap - 1;
+    const __amdgpu_buffer_rsrc_t rings = fdn_rings(s, inst, c.ring_stride);
+    const int lane4 = lane * 4;
+    int wp = __builtin_amdgcn_readfirstlane(s.wpos[inst]);  // write position of the block's first frame: wave-uniform
+    if (lane < 32) fdn_state_load<3>(s, inst, lane, hist, fbr);
+    float dn[32], xin[2];  // prefetched ring reads / inputs of the NEXT block (lane = frame)
+    auto fetch = [&](size_t t0n, int wpn) {
+        fdn_ring_fetch(dn, rings, lane4, c.cap, wpn, p);
+        const int sizen = fdn_block_size(T, t0n);
+#pragma unroll
+        for (int ch = 0; ch < 2; ch++)
+            xin[ch] = lane < sizen ? (layout == 0 ? in[((size_t)ch * T + t0n + lane) * V + inst] : in[(inst * 2 + ch) * fstride + t0n + lane]) : 0.0f;
+    };
+    fetch(0, wp);
+    for (size_t t0 = 0; t0 < T; t0 += 64) {
+        const int size = fdn_block_size(T, t0);
+        float d[32], xi0 = xin[0], xi1 = xin[1];
+#pragma unroll
+        for (int k = 0; k < 32; k++) d[k] = dn[k];
+        if (t0 + 64 < T) fetch(t0 + 64, (wp + 64) & CMASK);  // loads of the next block fly during this block's arithmetic
+        float o[32], h[32];
+        fdn_fir_lines<32, 3>(o, d, hist, lane, p);
+#pragma unroll
+        for (int k = 0; k < 32; k++) h[k] = o[k];
+        fdn_hadamard<NL>(h);  // within each network
+        fdn_feedback_put(h, c.had_scale, fbr, lane);
+        float xw[32];
+        fdn_ring_input<0, NL>(xw, fbr, lane, xi0, xi1);
+        // MultiJoin<U2, U8> of the first network's 16 outputs -> 2 channels -> MultiSplit<U2, U8> into the second network
+        float j0, j1;
+        fdn_join<16>(o, 2, tick_mode, j0, j1);
+        fdn_ring_input<NL, 32>(xw, fbr, lane, j0, j1);
+        fdn_ring_store(xw, rings, lane, lane4, c.cap, wp, size);
+        float l = 0.0f, rr = 0.0f;  // Reduce::tick left fold (audionode.rs:2427-2439) of the Panner outputs of the second network's lines
+#pragma unroll
+        for (int k = 32 - NL; k < 32; k++) {
+            const float pl = sc_wl[k] * o[k], pr = sc_wr[k] * o[k];
+            l = k == 32 - NL ? pl : l + pl;
+            rr = k == 32 - NL ? pr : rr + pr;
+        }
+        l *= c.out_scale;  // * dc((1/4, 1/4))
+        rr *= c.out_scale;
+        fdn_output_store(io, 2, t0, size, bus, l, rr, xi0, xi1);
+        fdn_block_carry<32, 3>(hist, fbr, lane, size);
+        wp = (wp + size) & CMASK;
+    }
+    if (lane == 0) s.wpos[inst] = wp;
+    if (lane < 32) fdn_state_store<3>(s, inst, lane, hist, fbr);
+}
+
 // ---- the generic network, lane = FRAME -----------------------------------------------------------------------------------------------
 // `split::<N>() / multisplit::<M, N/M>() >> fdn::<N, _>(stacki(|i| delay(t_i) >> fir(w))) >> join::<N>() / multijoin::<M, N/M>()`: the Hadamard
 // feedback delay network as the prelude documents it (prelude.rs:1323-1345, the "Mono Reverb" example :1334), N = NL lines of any delays
@@ -562,6 +662,14 @@ void fdn_launch_transpose(const float* src, float* dst, size_t V, size_t T, int 
 
 void fdn_launch_reset_state(const FdnState& s, float* s1, float* s2, size_t ring_stride, size_t instances, hipStream_t stream) {
     hipLaunchKernelGGL(k_fdn_reset, dim3(2048), dim3(256), 0, stream, s, s1, s2, ring_stride, instances);
+}
+
+void fdn_launch_render_reverb4_table(const FdnConst& c, const FdnState& s, const int* lens, size_t lens_stride, size_t instances, const float* in,
+                                     float* out, size_t T, size_t fstride, int layout, int tick_mode, hipStream_t stream, const FdnBus& bus) {
+    if (instances == 0 || T == 0) return;
+    tl_opts.last_kernel = LK_FDN_FRAMES;
+    hipLaunchKernelGGL(k_fdn_render_frames_table, dim3((unsigned)((instances + 3) / 4)), dim3(256), 0, stream, c, s, lens, lens_stride, instances, in, out,
+                       T, fstride, layout, tick_mode, bus);
 }
 
 void fdn_launch_render(const FdnConst& c, const FdnState& s, size_t instances, const float* in, float* out, size_t T,

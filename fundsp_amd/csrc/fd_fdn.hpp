@@ -101,6 +101,21 @@ void fdn_make_const_generic(const FdnDesc& d, double sample_rate, FdnConst* c);
 void fdn_launch_render(const FdnConst& c, const FdnState& s, size_t instances, const float* in, float* out, size_t T,
                        size_t fstride, int layout, int tick_mode, hipStream_t stream, const FdnBus& bus = FdnBus());
 
+// reverb4_stereo_delays(times, time) with a delay table PER INSTANCE (prelude.rs:1917-1941; the candidates of examples/optimize.rs,
+// reverb.rs:17-28): the two-section lane = frame kernel with the 32 ring lengths read from a row of a device table (wave-uniform loads, as
+// fd_fdnx.hpp's table; read-only in the kernel) instead of FdnConst::len.  FIR weights, pan weights and scales stay uniform (FdnConst).
+// host: `delays` = [rows][32] f32 seconds as the reference takes them (Delay::new(d as f64)), `lens` = [rows][32] ring lengths at
+// `sample_rate`; the constants are fdn_make_const_reverb4's at room_size 10 (reverb4_stereo_delays fixes it, :1921) with the ring capacity
+// sized from the longest delay of any row or from `hold_seconds`, whichever is larger.  The bank passes the longest delay it was CREATED
+// with or FDN_R4_SEARCH_MAX, whichever is larger -- so a bank made from one round of a search over 0.030-0.070 s holds every later round
+// at any room scale up to 1.5, and the capacity does not depend on what fdsp_reverb4_set_delays uploaded since.  Returns the shortest
+// delay in samples over all rows (the caller applies the two-block rule), -1 when a ring would exceed 2^18 slots.
+constexpr double FDN_R4_SEARCH_MAX = 0.070 * 1.5;
+int fdn_make_table_reverb4(const float* delays, size_t rows, double time, double sample_rate, double hold_seconds, int* lens, FdnConst* c);
+// lens_stride: 32 (a row per instance) or 0 (one row for the bank)
+void fdn_launch_render_reverb4_table(const FdnConst& c, const FdnState& s, const int* lens, size_t lens_stride, size_t instances, const float* in,
+                                     float* out, size_t T, size_t fstride, int layout, int tick_mode, hipStream_t stream, const FdnBus& bus = FdnBus());
+
 // [channels][T][V] (voice-minor) <-> [V][channels][T] (planar, frame stride T): the staging copies of voice-minor launches (fd_fdn.hip)
 void fdn_launch_transpose(const float* src, float* dst, size_t V, size_t T, int channels, bool to_planar, hipStream_t stream);
 

@@ -1,5 +1,7 @@
 // fd_fxbank.hip -- the effect banks of fd_fxbank.hpp: buffers, configuration, clone and launch of each family (host code; the kernels are in
 // fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_resynth.hip and fd_convolve.hip; those of the networks' fused mix-down in fd_fxmix.hip).
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "fd_fxbank.hpp"
@@ -217,6 +219,93 @@ class HadamardFx final : public NetFx {
     FdnDesc desc_;
     FdnConst c_{};
     FdnState st_{};
+};
+
+// reverb4_stereo_delays(times, time) with one delay table for the bank or one per instance (fd_fdn.hpp "PER INSTANCE"): the host keeps the
+// delays in seconds, the device a table of ring lengths at the current rate.  A change of rate re-derives every row, checks the two-block
+// rule over all of them and carries the FIR history and the feedback value like the uniform reverbs.
+class Reverb4TableFx final : public NetFx {
+  public:
+    Reverb4TableFx(std::vector<float> delays, int per_instance, double time, double hold_seconds, size_t V)
+        : NetFx(V, "reverb4_stereo_delays"), d_(std::move(delays)), per_(per_instance), time_(time), hold_(hold_seconds) { tables_ = 1; }
+    ~Reverb4TableFx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { fdn_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+    // every row is valid at the CURRENT rate (the creation's, the last change's or fdsp_reverb4_set_delays' check): the clone is built there
+    int clone(hipStream_t s, std::unique_ptr<FxBank>* out) override {
+        auto d = std::make_unique<Reverb4TableFx>(d_, per_, time_, hold_, V_);
+        if (int rc = d->create(sr_, s)) return rc;
+        if (hipError_t e = copy_bufs(d->bufs(), bufs(), s, tables_)) return hip_fail(e, "fdsp_bank_clone: reverb4_stereo_delays state");
+        d->bus_ = bus_;
+        *out = std::move(d);
+        return FDSP_OK;
+    }
+    // rows first .. first+count-1 (instances, or the single row 0 of a bank with one table), checked before anything changes; then the
+    // table rows are uploaded and those instances reset (the whole bank where it shares one row), in stream order
+    int set_delays(const float* rows, size_t first, size_t count, hipStream_t s) {
+        const size_t nrows = per_ ? V_ : 1;
+        if (first > nrows || count > nrows - first)
+            return api_fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: rows out of range (one row per instance with per_instance, else the single row 0)");
+        std::vector<int> lens(count * 32);
+        for (size_t i = 0; i < count * 32; i++) {
+            if (!(rows[i] >= 0.0f) || !(rows[i] < 1e6f)) return api_fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: a delay is negative or not a number (Delay::new asserts time >= 0)");
+            const double samples = std::round((double)rows[i] * sr_);
+            if (samples < 128.0)
+                return api_fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+            if (samples + 1.0 > (double)c_.cap)
+                return api_fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: a delay of " + std::to_string((long long)samples) + " samples needs a larger ring than the bank's " +
+                                                 std::to_string(c_.cap) + " slots (sized at creation from the longest delay given, at least 0.105 s)");
+            lens[i] = (int)samples + 1;
+        }
+        if (count == 0) return FDSP_OK;
+        std::copy(rows, rows + count * 32, d_.begin() + first * 32);
+        hipError_t e = hipMemcpyAsync(tab_ + first * 32, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            const size_t i0 = per_ ? first : 0, n = per_ ? count : V_;
+            FdnState part = st_;
+            part.rings += i0 * c_.ring_stride; part.wpos += i0; part.v1 += i0 * 32; part.v2 += i0 * 32; part.fb += i0 * 32;
+            fdn_launch_reset(c_, part, n, s);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);   // (lens is a local, rows is borrowed)
+        return e == hipSuccess ? FDSP_OK : hip_fail(e, "fdsp_reverb4_set_delays");
+    }
+
+  private:
+    int configure(double sr, hipStream_t s) override {
+        const size_t rows = per_ ? V_ : 1;
+        std::vector<int> lens(rows * 32);
+        FdnConst c;
+        const int shortest = fdn_make_table_reverb4(d_.data(), rows, time_, sr, hold_, lens.data(), &c);
+        if (shortest < 0) return api_fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
+        if (shortest < 128)
+            return api_fail(FDSP_EINVAL, "fdsp_reverb4_stereo_delays_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+        FdnState st{};
+        int* tab = nullptr;
+        hipError_t e = alloc_bufs(bufs(c, st, tab));
+        if (e == hipSuccess && (e = hipMemcpyAsync(tab, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st, tab));
+        if (e != hipSuccess) return hip_fail(e, "fdsp_reverb4_stereo_delays_create buffers");
+        fdn_launch_reset(c, st, V_, s);   // new lines start empty; the FIRs' history and the feedback value stay (HadamardFx::configure)
+        carry_and_free(bufs(c, st, tab), bufs(c_, st_, tab_), 3, s);   // v1, v2, fb (and the stream drains before `lens` goes)
+        c_ = c; st_ = st; tab_ = tab; sr_ = sr;
+        return launch_error();
+    }
+    Bufs bufs(const FdnConst& c, FdnState& st, int*& tab) const {
+        const size_t n = V_;
+        return {{(void**)&tab, (per_ ? n : 1) * 32 * sizeof(int)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)}, {(void**)&st.wpos, n * sizeof(int)},
+                {(void**)&st.v1, n * 32 * sizeof(float)}, {(void**)&st.v2, n * 32 * sizeof(float)}, {(void**)&st.fb, n * 32 * sizeof(float)}};
+    }
+    Bufs bufs() override { return bufs(c_, st_, tab_); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<Reverb4TableFx>(d_, per_, time_, hold_, V_); }
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) override {
+        fdn_launch_render_reverb4_table(c_, st_, tab_, per_ ? 32 : 0, V_, in, out, T, fstride, layout, tick, s, bus_);
+    }
+
+    std::vector<float> d_;   // [rows][32] seconds, as given (f32: Delay::new(d as f64))
+    int per_;
+    double time_, hold_;     // hold_: the delay the rings hold at least, fixed at creation
+    FdnConst c_{};
+    FdnState st_{};
+    int* tab_ = nullptr;     // [rows][32] ring lengths at sr_
 };
 
 // reverb3_stereo (fd_reverb3.hpp): what the reference's Reverb::set_sample_rate leaves alone survives a new rate (the `pre` diffusers
@@ -496,6 +585,17 @@ class ConvolveFx final : public FxBank {
 int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t s, std::unique_ptr<FxBank>* out) {
     const HadamardFx::Kind kind = sections == 2 ? HadamardFx::REVERB4 : HadamardFx::REVERB;
     return make_net(std::make_unique<HadamardFx>(kind, room_size, time, damping, FdnDesc(), instances), FDSP_DEFAULT_SR, s, out);
+}
+int fx_reverb4_delays(size_t instances, const float* delays, int per_instance, double time, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    std::vector<float> d(delays, delays + (per_instance ? instances : 1) * 32);
+    double hold = FDN_R4_SEARCH_MAX;   // the rings hold the longest delay given or 0.070 s x 1.5, whichever is larger
+    for (float x : d) hold = (double)x > hold ? (double)x : hold;
+    return make_net(std::make_unique<Reverb4TableFx>(std::move(d), per_instance, time, hold, instances), FDSP_DEFAULT_SR, s, out);
+}
+int fx_reverb4_set_delays(FxBank* fx, const float* rows, size_t first, size_t count, hipStream_t s) {
+    auto* r = dynamic_cast<Reverb4TableFx*>(fx);
+    if (!r) return api_fail(FDSP_EINVAL, "fdsp_reverb4_set_delays: not a bank of fdsp_reverb4_stereo_delays_create");
+    return r->set_delays(rows, first, count, s);
 }
 int fx_fdn(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, hipStream_t s,
            std::unique_ptr<FxBank>* out) {

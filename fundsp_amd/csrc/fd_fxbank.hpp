@@ -51,6 +51,12 @@ void fx_launch_copy_rows(const float* src, size_t sstride, float* dst, size_t ds
 // kernels' delay rule at the creation rate (44.1 kHz but for fx_fdn_network) and the allocation.
 // sections 1: reverb_stereo(room_size, time, damping), 2: reverb4_stereo(room_size, time)
 int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// reverb4_stereo_delays(delays, time): `delays` = [32] f32 seconds, or [instances][32] with per_instance (fd_fdn.hpp "PER INSTANCE")
+int fx_reverb4_delays(size_t instances, const float* delays, int per_instance, double time, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// fdsp_reverb4_set_delays: refuses what is not such a bank (`fx` may be NULL), rows out of range, and a delay that is negative, not a number,
+// under 128 samples or beyond the bank's ring capacity before anything changes; then uploads the rows and resets their instances on
+// `stream` and waits for it (the host array is borrowed)
+int fx_reverb4_set_delays(FxBank* fx, const float* rows, size_t first, size_t count, hipStream_t stream);
 int fx_fdn(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, hipStream_t stream,
            std::unique_ptr<FxBank>* out);
 // svf_mode < 0: lowpole_hz(cutoff) in the loop, else FixedSvf(svf_mode, cutoff, q, gain)

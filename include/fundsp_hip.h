@@ -230,6 +230,36 @@ int fdsp_reverb_stereo_create(size_t instances, double room_size, double time, d
  * are known at the head of a block; 272 B per instance-frame as well).  FDSP_MODE_PROCESS / FDSP_MODE_TICK differ in MultiJoin's
  * arithmetic exactly like the reference (src/audionode.rs:697-720).  Same handle semantics as reverb_stereo banks; "fdn_kernel" is ignored. */
 int fdsp_reverb4_stereo_create(size_t instances, double room_size, double time, fdsp_bank** out);
+/* reverb4_stereo_delays(delays, time) (src/prelude.rs:1917-1941): the same two networks with the caller's 32 delay times -- one table for
+ * the bank (per_instance = 0, delays = [32]) or one per instance (per_instance = 1, delays = [instances][32]): the candidates of
+ * examples/optimize.rs (src/reverb.rs:17-28), thousands of them in lock-step.  Delays are f32 seconds as the reference takes them
+ * (Delay::new(delays[i] as f64)); `time` enters through a = pow(db_amp(-60), 0.03 / time) as f32 (room_size is 10 here, :1921).  The
+ * lane-per-frame kernel reads the instance's 32 ring lengths from a device table; everything else -- both layouts, PROCESS / TICK,
+ * set_sample_rate (every row is re-derived, the 128-sample rule checked over all of them, nothing changes on failure), reset, clone,
+ * fdsp_bank_set_bus, the fused mix-down, flushed denormals -- is fdsp_reverb4_stereo_create's.  FDSP_EINVAL before anything is allocated
+ * for a NULL table, a delay that is negative or not a number, or one under 128 samples at 44.1 kHz.
+ * RING CAPACITY: one power of two for the bank, fixed by the longest delay given HERE or 0.070 s x 1.5 = 0.105 s, whichever is larger
+ * (at the current rate; 8 192 slots at 44.1 and 48 kHz for the search range 0.030-0.070 s). */
+int fdsp_reverb4_stereo_delays_create(size_t instances, const float* delays, int per_instance, double time, fdsp_bank** out);
+/* Replace the delay rows of instances first .. first+count-1 ([count][32] f32 seconds, borrowed for the call; a bank with one table has
+ * the single row 0) between launches, in stream order, and reset those instances (all of them where the bank shares one row): one search
+ * round is one upload, not a new bank.  FDSP_EINVAL, with nothing changed, for a bank of another kind, rows out of range, a delay that
+ * is negative, not a number or under 128 samples at the bank's rate, or one that needs a larger ring than the bank has. */
+int fdsp_reverb4_set_delays(fdsp_bank* bank, const float* delays, size_t first, size_t count);
+/* reverb_fitness (src/reverb.rs:31-139) of every instance of an effect bank with 2 inputs and 2 outputs -- the reverbs, stereo networks,
+ * a two-channel convolver -- on the device: the bank is reset, renders Impulse::<U2> (1.0 on both channels at frame 0) for 32 768 frames
+ * in FDSP_MODE_PROCESS at its current sample rate (the reference's number is at 44 100 Hz, the default) into scratch it owns, every
+ * (instance, channel) response is scored (echo density; Hann window, real FFT, outliers above the mean of the 50 bins before), and the
+ * bank is reset again: it is left as constructed.  d_fitness = [instances] device floats; d_terms, if not NULL, [instances][4] =
+ * echo_0, pen_0, echo_1, pen_1 with fitness = echo_0 - pen_0 + echo_1 - pen_1.  Every sum has a fixed order (fd_fitness.hpp): the
+ * same bits run to run and for any bank size.  The scratch -- 2 x instances x 2 x 32 768 floats, the render kernels take one stride for
+ * input and output -- is allocated by fdsp_bank_fitness_reserve or by the first call, kept until the bank goes and not cloned
+ * (fdsp_bank_get_option(bank, "fitness_scratch_kib") reads its size, 0 while there is none; "fitness_allocs" counts the device
+ * allocations made for these calls so far -- 2 once reserved, for good; "fitness_score_us" is the device time of the last call's
+ * scoring kernels in microseconds).
+ * FDSP_ENOTSUP for voice banks and other arities; FDSP_EINVAL on a stream that is being captured. */
+int fdsp_bank_fitness_reserve(fdsp_bank* bank);
+int fdsp_bank_reverb_fitness(fdsp_bank* bank, float* d_fitness, float* d_terms, void* stream);
 /* The generic Hadamard feedback delay network as the prelude documents it (src/prelude.rs:1323-1345, "Mono Reverb" :1334):
  *     split::<N>() >> fdn::<N, _>(stacki::<N, _, _>(|i| delay(delays[i]) >> fir(weights))) >> join::<N>()
  * `instances` independent networks of `lines` = N delay lines (2, 4, 8, 16 or 32), Delay::new(delays[i]) seconds each
@@ -426,6 +456,7 @@ int fdsp_device_count(void);
 int fdsp_bank_create_on(int device, const char* kind, size_t voices, size_t ring_frames, fdsp_bank** out);
 int fdsp_reverb_stereo_create_on(int device, size_t instances, double room_size, double time, double damping, fdsp_bank** out);
 int fdsp_reverb4_stereo_create_on(int device, size_t instances, double room_size, double time, fdsp_bank** out);
+int fdsp_reverb4_stereo_delays_create_on(int device, size_t instances, const float* delays, int per_instance, double time, fdsp_bank** out);
 int fdsp_reverb3_stereo_create_on(int device, size_t instances, double time, double diffusion, float lowpole_cutoff_hz, fdsp_bank** out);
 int fdsp_reverb3_stereo_svf_create_on(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff_hz, float q, float gain, fdsp_bank** out);
 int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out);

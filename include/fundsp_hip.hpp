@@ -548,6 +548,20 @@ class Bank {
         b.kind_ = "reverb4_stereo";
         return b;
     }
+    // reverb4_stereo_delays(delays, time) (prelude.rs:1917-1941) with 32 delay times for the whole bank or instances x 32 for a table per
+    // instance (the candidates of examples/optimize.rs); set_delays replaces rows between launches and resets their instances
+    static Bank reverb4_stereo_delays(size_t instances, const std::vector<float>& delays, double time) {
+        if (delays.size() != 32 && delays.size() != instances * 32) detail::arity("reverb4_stereo_delays takes 32 or instances x 32 delay times");
+        Bank b;
+        check(fdsp_reverb4_stereo_delays_create(instances, delays.data(), delays.size() != 32 ? 1 : 0, time, &b.h_));
+        b.kind_ = "reverb4_stereo";
+        return b;
+    }
+    void set_delays(const float* delays, size_t first = 0, size_t count = 1) { check(fdsp_reverb4_set_delays(h_, delays, first, count)); }
+    // reverb_fitness (reverb.rs:31-139) of every instance of a stereo effect bank, on the device: d_fitness [instances], d_terms NULL or
+    // [instances][4] (echo_0, pen_0, echo_1, pen_1); the bank is reset before and after.  fitness_reserve: the call then allocates nothing
+    void fitness_reserve() { check(fdsp_bank_fitness_reserve(h_)); }
+    void reverb_fitness(float* d_fitness, float* d_terms = nullptr, void* stream = nullptr) { check(fdsp_bank_reverb_fitness(h_, d_fitness, d_terms, stream)); }
     // reverb3_stereo(time, diffusion, lowpole_hz(cutoff)) (prelude.rs:1858-1871, reverb.rs:152-279): the allpass-loop reverb through its lane-per-frame kernel
     static Bank reverb3_stereo(size_t instances, double time, double diffusion, float lowpole_cutoff_hz) {
         Bank b;

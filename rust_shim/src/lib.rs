@@ -115,6 +115,10 @@ pub mod ffi {
         pub fn fdsp_bank_create_on(device: c_int, kind: *const c_char, voices: usize, ring_frames: usize, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_reverb_stereo_create_on(device: c_int, instances: usize, room_size: f64, time: f64, damping: f64, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_reverb4_stereo_create_on(device: c_int, instances: usize, room_size: f64, time: f64, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_reverb4_stereo_delays_create_on(device: c_int, instances: usize, delays: *const f32, per_instance: c_int, time: f64, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_reverb4_set_delays(bank: *mut FdspBank, delays: *const f32, first: usize, count: usize) -> c_int;
+        pub fn fdsp_bank_fitness_reserve(bank: *mut FdspBank) -> c_int;
+        pub fn fdsp_bank_reverb_fitness(bank: *mut FdspBank, d_fitness: *mut f32, d_terms: *mut f32, stream: *mut c_void) -> c_int;
         pub fn fdsp_reverb3_stereo_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, lowpole_cutoff_hz: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_reverb3_stereo_svf_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, svf_mode: c_int, cutoff_hz: f32, q: f32, gain: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_create_on(device: c_int, instances: usize, lines: c_int, delays: *const f64, taps: c_int, weights: *const f32, inputs: c_int, outputs: c_int, out: *mut *mut FdspBank) -> c_int;
@@ -261,6 +265,35 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_reverb4_stereo_create_on(device as c_int, instances, room_size, time, &mut bank) })?;
         Self::adopt(bank, "reverb4_stereo", instances)
+    }
+
+    /// `instances` x `reverb4_stereo_delays(delays, time)` (src/prelude.rs:1917-1941): `delays` holds 32 times for the whole bank or
+    /// `instances` x 32 for a table per instance -- the candidates of examples/optimize.rs (src/reverb.rs:17-28) in one bank.
+    pub fn reverb4_stereo_delays(instances: usize, delays: &[f32], time: f64, device: i32) -> Result<Self, String> {
+        if delays.len() != 32 && delays.len() != instances * 32 {
+            return Err("HipBank::reverb4_stereo_delays: delays needs 32 or instances x 32 times".into());
+        }
+        let per_instance = (delays.len() != 32) as c_int;
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_reverb4_stereo_delays_create_on(device as c_int, instances, delays.as_ptr(), per_instance, time, &mut bank) })?;
+        Self::adopt(bank, "reverb4_stereo", instances)
+    }
+
+    /// Replace the delay rows `first` .. of a `reverb4_stereo_delays` bank (`delays` holds count x 32 times) and reset their instances.
+    pub fn set_delays(&mut self, delays: &[f32], first: usize) -> Result<(), String> {
+        if delays.is_empty() || delays.len() % 32 != 0 {
+            return Err("HipBank::set_delays: delays needs count x 32 times".into());
+        }
+        check(unsafe { fdsp_reverb4_set_delays(self.bank, delays.as_ptr(), first, delays.len() / 32) })
+    }
+
+    /// `AudioNode::allocate` for `reverb_fitness`: the call then allocates nothing.
+    pub fn fitness_reserve(&mut self) -> Result<(), String> { check(unsafe { fdsp_bank_fitness_reserve(self.bank) }) }
+
+    /// `reverb_fitness` (src/reverb.rs:31-139) of every instance of a stereo effect bank, on the device: `d_fitness` = [instances] device
+    /// floats, `d_terms` NULL or [instances][4] (echo_0, pen_0, echo_1, pen_1).  The bank is reset before and after.
+    pub fn reverb_fitness(&mut self, d_fitness: *mut f32, d_terms: *mut f32, stream: *mut c_void) -> Result<(), String> {
+        check(unsafe { fdsp_bank_reverb_fitness(self.bank, d_fitness, d_terms, stream) })
     }
 
     /// `instances` x `reverb3_stereo(time, diffusion, lowpole_hz(cutoff))` (src/prelude.rs:1858-1871; `Reverb<F>`, src/reverb.rs:152-279) through its
