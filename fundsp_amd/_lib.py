@@ -14,6 +14,7 @@ LAYOUT_VOICE_MINOR, LAYOUT_PLANAR = 0, 1
 MODE_PROCESS, MODE_TICK = 0, 1
 MATH_EXACT, MATH_FAST = 0, 1
 SCORE_VOICES, SCORE_NOTES = 0, 1  # the "score_exec" option: a lane is a voice / a lane is a note
+SVF_SERIAL, SVF_PARALLEL = 0, 1  # the "svf_exec" option: the time-split kernels' serial filter wave / tolerance mode's time-parallel filter stage
 BUS_NONE, BUS_WET, BUS_DRY_WET = 0, 1, 2  # fdsp_bank_set_bus: the node alone | wet * node | dry * multipass() & wet * node
 MIX_SUM, MIX_PAN = 1, 2  # fdsp_bank_process_mix: sum the output channels over the voices | pan a mono graph per voice, then sum
 FADE_POWER, FADE_SMOOTH = 0, 1  # sequencer.rs Fade::Power / Fade::Smooth

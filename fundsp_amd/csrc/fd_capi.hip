@@ -33,7 +33,7 @@ const char* jit_compiler_origin();
 namespace fd {
 // process-wide DEFAULTS (fdsp_set_option); a bank's own value (fdsp_bank_set_option) overrides them for that bank.  Atomics:
 // hosts drive banks from several threads.  The launch code never reads these: it reads the thread-local block below.
-std::atomic<int> g_pipe_split{1}, g_fdn_kernel{0}, g_time_split{1};
+std::atomic<int> g_pipe_split{1}, g_fdn_kernel{0}, g_time_split{1}, g_svf_exec{FDSP_SVF_SERIAL};
 std::atomic<int> g_math{FDSP_MATH_EXACT};  // default arithmetic of banks created from now on (fdsp_set_option("math", ..))
 std::atomic<int> g_score_chunk{0};        // mixed score launches, one lane per note: frames per scratch chunk, 0 = from the byte budget (events_render)
 std::atomic<int> g_fx_mix_chunk{0};       // effect banks' fused mix-down: frames per scratch chunk, 0 = from the byte budget (fd_fxbank.hip)
@@ -411,7 +411,7 @@ struct fdsp_bank {
     mutable bool async_param_pending = false;
     int math = FDSP_MATH_EXACT;  // FDSP_MATH_FAST: renders take the kind's tolerance-mode variant when it has one
     // per-bank launch options (fdsp_bank_set_option); -1 = follow the process-wide default at every launch
-    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1, opt_fx_mix_chunk = -1, opt_score_chunk = -1;
+    int opt_pipe_split = -1, opt_time_split = -1, opt_fdn_kernel = -1, opt_timing = -1, opt_fx_mix_chunk = -1, opt_score_chunk = -1, opt_svf_exec = -1;
     size_t ring_frames = 0;      // as given at creation (fdsp_bank_clone)
     int last_kernel = 0;         // fd::LastKernel of the most recent render launch (fdsp_bank_get_option "last_kernel")
     bool ring_check_pending = false;  // a lifecycle launch may have changed a delay length: verify capacity before rendering
@@ -765,6 +765,8 @@ const OptSpec LAUNCH_OPTS[] = {
      &fd::g_fx_mix_chunk, &fdsp_bank::opt_fx_mix_chunk, 64},
     {"score_chunk_frames", 0, 1 << 21, "score_chunk_frames takes 0 (automatic: from the scratch budget) or a multiple of 64 up to 2 097 152 (frames per chunk of a mixed score launch with one lane per note)",
      &fd::g_score_chunk, &fdsp_bank::opt_score_chunk, 64},
+    {"svf_exec", FDSP_SVF_SERIAL, FDSP_SVF_PARALLEL, "svf_exec takes FDSP_SVF_SERIAL (0: the time-split kernels' serial filter wave) or FDSP_SVF_PARALLEL (1: tolerance-mode banks of at most one voice group per CU split the filter stage over time)",
+     &fd::g_svf_exec, &fdsp_bank::opt_svf_exec},
 };
 const OptSpec* launch_opt(const char* name) {
     if (!name) return nullptr;
@@ -779,6 +781,7 @@ void resolve_opts(const fdsp_bank* b) {
     fd::tl_opts.time_split = b->opt_time_split >= 0 ? b->opt_time_split : fd::g_time_split.load(std::memory_order_relaxed);
     fd::tl_opts.fdn_kernel = b->opt_fdn_kernel >= 0 ? b->opt_fdn_kernel : fd::g_fdn_kernel.load(std::memory_order_relaxed);
     fd::tl_opts.fx_mix_chunk_frames = b->opt_fx_mix_chunk >= 0 ? b->opt_fx_mix_chunk : fd::g_fx_mix_chunk.load(std::memory_order_relaxed);
+    fd::tl_opts.svf_exec = b->opt_svf_exec >= 0 ? b->opt_svf_exec : fd::g_svf_exec.load(std::memory_order_relaxed);
     fd::tl_opts.last_kernel = fd::LK_NONE;
 }
 bool timing_on(const fdsp_bank* b) { return (b->opt_timing >= 0 ? b->opt_timing : fd::g_timing.load(std::memory_order_relaxed)) != 0; }
@@ -884,6 +887,7 @@ int fdsp_bank_get_option(const fdsp_bank* b, const char* name) {
     if (name && std::strcmp(name, "last_kernel") == 0) return b->last_kernel;
     if (name && std::strcmp(name, "score_exec") == 0) return b->score_exec;
     if (name && std::strcmp(name, "has_score_notes") == 0) return score_notes_kind(b) ? 1 : 0;
+    if (name && std::strcmp(name, "has_svf_parallel") == 0) return (!b->fx && b->ops && b->ops->svf_parallel) ? 1 : 0;  // the kind has k_render_ts3p ("svf_exec")
     if (name && std::strcmp(name, "score_scratch_frames") == 0) {  // frames the mixed note path's scratch holds now (read-only)
         const size_t per = (size_t)fdsp_bank_outputs(b) * b->V;
         return per ? (int)(b->score_scratch_n / per) : 0;
@@ -1431,6 +1435,7 @@ int fdsp_bank_clone(const fdsp_bank* src, fdsp_bank** out) {
     b->opt_timing = src->opt_timing;
     b->opt_fx_mix_chunk = src->opt_fx_mix_chunk;
     b->opt_score_chunk = src->opt_score_chunk;
+    b->opt_svf_exec = src->opt_svf_exec;
     b->score_exec = src->score_exec;  // (no staging image, no scratch: the clone's first uncaptured scored launch, or its fdsp_bank_mix_reserve, makes them)
     e = sync_bank_stream(b);
     if (e != hipSuccess) return bail(e, "copy");

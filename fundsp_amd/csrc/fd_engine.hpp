@@ -62,6 +62,8 @@ struct KindOps {
     std::function<void(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, size_t fstride,
                        int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s)>
         render_fast;
+    // ... and render_fast has the time-split kernel with the time-parallel filter stage ("svf_exec" 1; fdsp_bank_get_option "has_svf_parallel")
+    bool svf_parallel = false;
     // Render + mix-down in one launch (fd_device.hpp "fused mix-down"): part = device [voice groups][mix channels][T] partial
     // mixes, mix = MIX_SUM / MIX_PAN, panw = device [2][stride] pan weights (MIX_PAN).  Voice-minor inputs.  false = this graph /
     // launch has no fused kernel.  Empty for kinds built without one (attach_mix<G>).
@@ -169,6 +171,10 @@ void launch_ts(const RenderPlan& p, const RenderArgs& a) {
     if (p.gpw == 1) ts3(IntC<1>{});
     else ts3(IntC<2>{});
 }
+// the time-split kernel with the time-parallel filter stage ("svf_exec" 1; fd_tsp.hpp): a kind that has it says so by specialising
+// TspKernel for its tolerance-mode graph type, and the unit that compiles the kernel defines launch_tsp for that type (fd_kinds_fm_tsp.hip)
+template <class G> struct TspKernel { static constexpr bool ok = false; };
+template <class G> void launch_tsp(const RenderPlan& p, const RenderArgs& a);
 template <class G, int MODE, int LAYOUT>
 void launch_single(const RenderPlan& p, const RenderArgs& a) {
     constexpr int WPB = RenderGeom<G, LAYOUT>::WPB;  // = p.gpw
@@ -201,12 +207,15 @@ template <class G>
 void launch_render(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, size_t fstride,
                    int layout, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s) {
     if (V == 0 || T == 0) return;
-    constexpr GraphTraits traits = graph_traits<G>(false);
+    GraphTraits traits = graph_traits<G>(false);
+    traits.tsp_ok = TspKernel<G>::ok;
     const RenderPlan p = plan_render(traits, tl_opts, (size_t)simd_count() / 4, V, T, layout, mode, fstride, (((uintptr_t)in | (uintptr_t)out) & 15) == 0);
     tl_opts.last_kernel = p.family;
     const RenderArgs a{slots, stride, V, in, out, T, fstride, aux, ring, ring_cap, nullptr, s};
     if (p.family == LK_TIME_SPLIT) {
         if constexpr (TsPlan<G>::ok) launch_ts<G, MIX_NONE>(p, a);
+    } else if (p.family == LK_TIME_SPLIT_SVF) {
+        if constexpr (TspKernel<G>::ok) launch_tsp<G>(p, a);
     } else if (mode == MODE_PROCESS) {
         launch_render_mode<G, MODE_PROCESS>(p, a, layout);
     } else {
@@ -345,6 +354,7 @@ KindOps make_kind(const char* name) {
     k.render = &launch_render<G>;
     using GF = typename FastOf<G>::type;
     if constexpr (!SameType<GF, G>::v) k.render_fast = &launch_render<GF>;
+    k.svf_parallel = TspKernel<GF>::ok;
     k.render_events = &launch_render_events<G>;
     k.render_score = &launch_render_score<G>;
     if constexpr (G::RINGS == 0) {  // notes of one voice would share the voice's ring

@@ -8,9 +8,10 @@
 // emitting it pair by pair with an `s_nop` after every dependent packed op (38-44 per item, 6-14 % slower; profiles/
 // r03_ab1_knockout_prio.txt, r03_isa_fm_svf.txt).  The ILP strategy produces the interleaved form every time.  It cannot
 // be a whole-library flag: ROCm 7.2's clang crashes with it in the register allocator on other kinds (Oversampler).
-#include "fd_kinds_fm.hpp"
+#include "fd_kinds_fm_tsp.hpp"
 
 namespace fd {
+// ... and those with the time-parallel filter stage of the tolerance-mode twins in fd_kinds_fm_tsp.hip (launch_tsp<G>, fd_engine.hpp)
 // the three-way time-split kernels of these types are compiled in fd_kinds_fm_ts.hip (-amdgpu-sched-strategy=max-ilp, see the Makefile)
 #define FD_X(G, GPW) extern template __global__ void k_render_ts3<G, GPW>(float* __restrict__, size_t, size_t, float* __restrict__, size_t, const void*);
 FD_FM_TS3_KERNELS(FD_X)

@@ -52,10 +52,12 @@ struct GraphTraits {
     bool has_fast;            // the graph has a tolerance-mode twin (FastOf<G> is another type)
     bool note_fresh;          // scores may render the notes of a voice independently (no rings, no node marked note_stale); set where the graph is
                               // described (make_kind / describe_body), not by graph_traits: the answer comes from a visit()
+    bool tsp_ok;              // the time-split kernel with the time-parallel filter stage exists (fd_tsp.hpp): tolerance-mode twins of some ahead-of-time
+                              // kinds; set by their launcher (fd_engine.hpp launch_render), never for run-time kinds
 };
 
 struct RenderPlan {
-    int family;    // LK_SINGLE_WAVE, LK_PIPELINE, LK_PIPELINE_PLANAR, LK_TIME_SPLIT or LK_WIDE_CHAIN; LK_NONE = no fused kernel (plan_render_mix)
+    int family;    // LK_SINGLE_WAVE, LK_PIPELINE, LK_PIPELINE_PLANAR, LK_TIME_SPLIT, LK_TIME_SPLIT_SVF or LK_WIDE_CHAIN; LK_NONE = no fused kernel (plan_render_mix)
     int gpw;       // voice groups per workgroup: 1, 2 or 4 (single wave: waves per workgroup)
     unsigned grid; // workgroups
     int vpw;       // voices per wave (below 64 only in the voice-minor single-wave kernel)
@@ -92,6 +94,9 @@ inline RenderPlan plan_render(const GraphTraits& g, const LaunchOpts& o, size_t 
     const bool voice_minor = layout == LAYOUT_VOICE_MINOR;
     if (g.ts_ok && voice_minor && plan_time_split(o, cus, groups, T, mode)) {
         if (o.time_split == 1) {  // both oscillator stages split three ways, the filter wave (nearly) alone on a SIMD
+            // "svf_exec" 1, a request: the filter stage split over time too.  tsp_ok is only ever set for a tolerance-mode graph type, so the
+            // bank's "math" is FDSP_MATH_FAST here; one voice group per workgroup only (the kernel's LDS tiles)
+            if (o.svf_exec == 1 && g.tsp_ok && groups <= cus) return {LK_TIME_SPLIT_SVF, 1, (unsigned)groups, 64, 0, 0};
             const int gpw = groups <= cus ? 1 : 2;
             return {LK_TIME_SPLIT, gpw, plan_grid(groups, gpw), 64, 0, 0};
         }

@@ -128,7 +128,8 @@ int fdsp_bank_get_option(const fdsp_bank* bank, const char* name);
  * fdsp_bank_get_option(bank, "last_kernel") (read-only): the kernel family the most recent render launch took --
  * 1 single-wave, 2 pipeline, 3 planar pipeline, 4 time-split, 5 voice scheduler, 6 / 7 reverb lane-per-frame / -line,
  * 8 the chain of waves that renders a wide sum of generators (sumi / busi of >= 8 oscillators) on a small bank,
- * 9 the voice scheduler playing a score (fdsp_bank_set_score), 10 a score rendered with one lane per note ("score_exec"). */
+ * 9 the voice scheduler playing a score (fdsp_bank_set_score), 10 a score rendered with one lane per note ("score_exec"),
+ * 11 time-split with the time-parallel filter stage ("svf_exec"). */
 /* fdsp_bank_get_option(bank, "has_fused_mix") (read-only): 1 if fdsp_bank_process_mix has kernels for the bank's kind (voice banks), or
  * the bank is a reverb / network bank (their mix-down renders into a scratch: "the stereo mix-down" below); 0 for resynthesizer and convolver banks. */
 /* "fx_mix_chunk_frames" (default 0 = automatic, from a 256 MiB budget): frames per chunk of the mix scratch of a reverb / network bank, a
@@ -153,6 +154,22 @@ int fdsp_bank_get_option(const fdsp_bank* bank, const char* name);
  * small is refused.  "score_scratch_frames" (read-only): the frames the scratch holds now. */
 #define FDSP_SCORE_VOICES 0
 #define FDSP_SCORE_NOTES 1
+/* "svf_exec" (launch option like "time_split": process-wide, per bank, -1 = follow the default; default FDSP_SVF_SERIAL): how the
+ * time-split kernels of small banks run the fixed SVF that ends an oscillator chain.
+ *   FDSP_SVF_SERIAL    one wave carries the filter's recurrence frame by frame (the reference's arithmetic; that wave is the round time).
+ *   FDSP_SVF_PARALLEL  tolerance mode only: the filter is linear in its state, so every 64-frame block is rendered from state zero in
+ *                      chunks of 32 frames by two waves, and a third adds what the carried state contributes (tables of the voice's
+ *                      coefficients, built in f64 at the start of the launch) and carries the state on.  Not the reference's bits.
+ * A request: it applies where "math" is FDSP_MATH_FAST, "time_split" is 1, the launch would take the time-split kernel (process mode,
+ * voice-minor, whole blocks), the bank has at most one voice group per CU and its kind has the kernel ("has_svf_parallel", read-only:
+ * 1 / 0; today fm_svf and sine_hz_lowpass_hz) -- "last_kernel" then reads 11; everywhere else the launch is exactly the one of
+ * FDSP_SVF_SERIAL.  Stated tolerance, per voice, against the filter ticked in f64 on the same input:
+ *   |error| <= 4.6 x (the serial f32 tick's worst error on that voice) + 2^-23 x (the voice's peak output),
+ * and over a bank no worse than the serial tick's worst voice (tests/test_svf_par_host.py measures 2.3 x and the bank-wide figures;
+ * tests/test_gpu_svf_par.py holds the kernel to the same bound).  Launch splits do not change a bit, the state in ic1eq / ic2eq is the
+ * filter's state after the launch and either executor continues from the other's.  Non-finite samples propagate as they do serially. */
+#define FDSP_SVF_SERIAL 0
+#define FDSP_SVF_PARALLEL 1
 /* "host_zero_copy_max" (default 262144): fdsp_bank_process_host calls moving at most this many floats per direction
  * let the kernel read/write pinned host memory directly instead of staging through HBM (lower per-block latency). */
 /* "fdn_kernel" (default 0): reverb banks render with one lane per FRAME (0) or one lane per DELAY LINE (1); identical

@@ -646,7 +646,9 @@ class Bank {
     // FDSP_BUS_DRY_WET = `dry * multipass() & wet * node` -- README.md:436 `multipass() & 0.2 * reverb_stereo(20.0, 2.0, 1.0)` is
     // set_bus(FDSP_BUS_DRY_WET, 0.2f) --, FDSP_BUS_NONE = the node alone.  Unop<X, FrameMulScalar> + Bus + MultiPass: audionode.rs:1190-1228, 1842-1877, 373-403
     void set_bus(int mode, float wet = 1.0f, float dry = 1.0f) { check(fdsp_bank_set_bus(h_, mode, wet, dry)); }
-    // launch options of this bank ("pipe_split", "time_split", "fdn_kernel", "timing", "math"; -1 = process-wide default)
+    // launch options of this bank ("pipe_split", "time_split", "fdn_kernel", "timing", "math", "svf_exec"; -1 = process-wide default)
+    // "svf_exec" = FDSP_SVF_PARALLEL: tolerance-mode banks of at most one voice group per CU run the SVF behind an oscillator chain
+    // split over time ("has_svf_parallel" tells whether the kind has the kernel, "last_kernel" 11 that it ran; fundsp_hip.h)
     void set_option(const std::string& name, int value) { check(fdsp_bank_set_option(h_, name.c_str(), value)); }
     int get_option(const std::string& name) const {
         const int v = fdsp_bank_get_option(h_, name.c_str());

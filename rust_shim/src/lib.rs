@@ -103,6 +103,8 @@ pub mod ffi {
     pub const FDSP_MODE_TICK: c_int = 1;
     pub const FDSP_MATH_EXACT: c_int = 0;
     pub const FDSP_MATH_FAST: c_int = 1;
+    pub const FDSP_SVF_SERIAL: c_int = 0;
+    pub const FDSP_SVF_PARALLEL: c_int = 1;
     pub const FDSP_MIX_SUM: c_int = 1;
     pub const FDSP_MIX_PAN: c_int = 2;
 
