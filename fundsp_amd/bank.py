@@ -90,10 +90,28 @@ class Bank:
                 eff.set_sample_rate(sample_rate)
             src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, fdn_kernel=fdn_kernel, flush_denormals=ftz)
             return Chain(src, eff, construction_hash=probe_hash(graph))
+        rt = G.convolve_route_plan(graph)
+        if rt is not None:   # a tree of stacks and branches over convolvers, `a ^ b`, `(a ^ b) | (c ^ d)`: one routed bank (fdsp_convolve_routed_create)
+            b = cls.convolve(voices, rt[0], flush_denormals=flush_denormals, source=rt[1])
+            if sample_rate is not None:
+                b.set_sample_rate(sample_rate)
+            return b
+        rt = G.convolve_route_plan(parts[1]) if parts is not None else None
+        if rt is not None and not G.has_convolve(parts[0]) and not G.has_resynth(parts[0]):
+            # `front >> (convolve(..) ^ convolve(..))`: the chain above with a routed bank as its effect half; Branch::ID = 8 and the
+            # convolvers' IDs enter the whole graph's construction hash through Branch::ping (the probe walks the type)
+            ftz = flush_denormals or "Feedback" in parts[0].type
+            eff = cls.convolve(voices, rt[0], flush_denormals=ftz, source=rt[1])
+            if sample_rate is not None:
+                eff.set_sample_rate(sample_rate)
+            src = cls.from_graph(parts[0], voices, ring_frames=ring_frames, sample_rate=sample_rate, fdn_kernel=fdn_kernel, flush_denormals=ftz)
+            return Chain(src, eff, construction_hash=probe_hash(graph))
         if G.has_convolve(graph):
-            raise ValueError("convolve(..) renders as a whole graph, as a stack of convolvers `convolve(..) | convolve(..)`, or as the last node "
-                             "of a pipe, `front >> convolve(..)` / `front >> (convolve(..) | convolve(..))` (a Chain); inside any other stack, a "
-                             "sum, bus or feedback, or followed by more nodes, it is not supported")
+            raise ValueError("convolve(..) renders as a whole graph, as a stack of convolvers `convolve(..) | convolve(..)`, as a branch of them "
+                             "`convolve(..) ^ convolve(..)` (one input through several responses; stacks and branches nest), or as the last node "
+                             "of a pipe, `front >> convolve(..)` / `front >> (convolve(..) | convolve(..))` / `front >> (convolve(..) ^ "
+                             "convolve(..))` (a Chain); inside any other stack, a sum, bus or feedback, or followed by more nodes, it is not "
+                             "supported")
         if parts is not None and (getattr(parts[1], "resynth_plan", None) or getattr(parts[1], "resynth_fn_plan", None)) is not None and not G.has_resynth(parts[0]):
             # `front >> resynth(..)` -- the reference's criterion bench noise() >> resynth::<U1, U1, _>(1024, ..): the front keeps its fused kernel,
             # the resynthesizer its FFT kernels; the front is seeded from the whole graph's construction hash (Resynth::ID = 80 enters it through the
@@ -418,14 +436,22 @@ class Bank:
         check(lib().fdsp_resynth_set_params(self._h, _fptr(t), int(first), t.shape[0]))
 
     @classmethod
-    def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None):
+    def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None, source=None):
         """Bank of `instances` x `channels` convolvers, convolve(&wave, channel) (convolve.rs) per channel, through the partitioned FFT
         convolution kernels (fdsp_convolve_create): y[n] = sum h[k] x[n - k], no latency, every split into launches the same bits.
         `response`: [len] or [channels, len], with per_instance=True [instances, channels, len].  `channels` defaults to the response's
         (a [len] response is given to every channel when `channels` says more than one); `max_len` is the capacity set_response can
-        fill later (default: len)."""
+        fill later (default: len).
+        `source`: None -- channel c reads input c -- or one input index per output: the routed bank (fdsp_convolve_routed_create) of
+        max(source) + 1 inputs whose output c convolves input source[c] with response row c, `convolve(&w, 0) ^ convolve(&w, 1)` being
+        source=[0, 0].  Outputs of one input share its input ring, block transforms and spectrum ring; the bits are those of the plain bank
+        fed copies of the input rows."""
         V = int(instances)
         h = convolve_response_rows(response, channels, V if per_instance else None)
+        if source is not None:
+            source = tuple(int(i) for i in source)
+            if len(source) != h.shape[-2]:
+                raise ValueError(f"convolve: source needs one input index per output ({h.shape[-2]}), got {len(source)}")
         spec = _lib.ConvolveSpec()
         spec.channels, spec.len = h.shape[-2], h.shape[-1]
         spec.max_len = int(max_len) if max_len is not None else h.shape[-1]
@@ -433,8 +459,14 @@ class Bank:
         spec.flush_denormals = 1 if flush_denormals else 0
         spec.response = _fptr(h)
         hd = C.c_void_p()
-        check(lib().fdsp_convolve_create_on(-1 if device is None else int(device), V, C.byref(spec), C.byref(hd)))
+        dev = -1 if device is None else int(device)
+        if source is None:
+            check(lib().fdsp_convolve_create_on(dev, V, C.byref(spec), C.byref(hd)))
+        else:
+            src = (C.c_int * len(source))(*source)
+            check(lib().fdsp_convolve_routed_create_on(dev, V, C.byref(spec), max(source) + 1, src, C.byref(hd)))
         b = cls("convolve", V, _handle=hd)
+        b.source = source
         b.max_len, b.block_length = int(spec.max_len), lib().fdsp_convolve_block_length(int(spec.max_len))
         b.per_instance = bool(per_instance)
         return b
@@ -471,7 +503,7 @@ class Bank:
         check(lib().fdsp_bank_clone(self._h, C.byref(h)))
         b = Bank(self.kind, self.voices, _handle=h)
         b.sample_rate = self.sample_rate
-        for k in ("window", "params", "max_len", "block_length", "per_instance"):
+        for k in ("window", "params", "max_len", "block_length", "per_instance", "source"):
             if hasattr(self, k):
                 setattr(b, k, getattr(self, k))
         return b

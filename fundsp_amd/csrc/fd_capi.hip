@@ -1301,9 +1301,30 @@ int fdsp_convolve_create_on(int device, size_t instances, const fdsp_convolve_sp
     if (!out) return fail(FDSP_EINVAL, "out is NULL");
     *out = nullptr;
     if (int rc = cv_check_spec(instances, sp)) return rc;
-    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_convolve(instances, *sp, s, fx); });
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_convolve(instances, *sp, 0, nullptr, s, fx); });
 }
 int fdsp_convolve_create(size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out) { return fdsp_convolve_create_on(-1, instances, spec, out); }
+// a routed bank: the spec's checks, then the routing's, all before a device is touched
+int fdsp_convolve_routed_create_on(int device, size_t instances, const fdsp_convolve_spec* sp, int inputs, const int* source, fdsp_bank** out) {
+    if (!out) return fail(FDSP_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = cv_check_spec(instances, sp)) return rc;
+    if (inputs < 1 || inputs > sp->channels)
+        return fail(FDSP_EINVAL, "fdsp_convolve_routed_create: inputs = " + std::to_string(inputs) + " takes 1 .. channels = " + std::to_string(sp->channels));
+    if (!source) return fail(FDSP_EINVAL, "fdsp_convolve_routed_create: source NULL");
+    unsigned fed = 0;
+    for (int o = 0; o < sp->channels; o++) {
+        if (source[o] < 0 || source[o] >= inputs)
+            return fail(FDSP_EINVAL, "fdsp_convolve_routed_create: source[" + std::to_string(o) + "] = " + std::to_string(source[o]) + " takes 0 .. inputs - 1 = " + std::to_string(inputs - 1));
+        fed |= 1u << source[o];
+    }
+    for (int i = 0; i < inputs; i++)
+        if (!(fed >> i & 1u)) return fail(FDSP_EINVAL, "fdsp_convolve_routed_create: source names no output for input " + std::to_string(i) + " (every input feeds at least one output)");
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_convolve(instances, *sp, inputs, source, s, fx); });
+}
+int fdsp_convolve_routed_create(size_t instances, const fdsp_convolve_spec* spec, int inputs, const int* source, fdsp_bank** out) {
+    return fdsp_convolve_routed_create_on(-1, instances, spec, inputs, source, out);
+}
 int fdsp_convolve_set_response(fdsp_bank* b, const float* h_response, size_t len, size_t first, size_t count) {
     if (!b || !h_response) return fail(FDSP_EINVAL, "fdsp_convolve_set_response: bank or response NULL");
     if (int rc = fd::fx_convolve_check(b->fx.get(), len, first, count)) return rc;

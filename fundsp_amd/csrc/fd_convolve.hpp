@@ -27,6 +27,11 @@
 //   * Head and output, n = jB + r:  a = h[0] * x[n];  for i = 1 .. min(r, M - 1):  a = a + h[i] * x[n - i];  y[n] = pend_j[r] + a.
 //   * reset(): n = 0 (nothing before it is read again).  set_response: new h, M, P and G, then reset.  Channel c of a bank is its own 1 -> 1
 //     convolver with response row c; instances run in lock-step (one sample counter).
+//   * Routing: a bank has I inputs and C outputs, 1 <= I <= C <= 8, and a source map source[c] in [0, I) under which every input feeds at
+//     least one output.  Output c is the 1 -> 1 convolver above with response row c, reading input source[c]: block spectra X_j and the
+//     input samples are per (instance, input); G, h, Z, pend and y are per (instance, output).  No operation and no order changes, so a
+//     routed bank gives the bits of the C-channel bank fed copies of the input rows (tests/convolve_ref.py: render(x[:, source, :], h)),
+//     and the identity map (I = C, fdsp_convolve_create) is the bank of the bullets above.
 //
 // Device layout.  Nothing is allocated after creation.  A launch is cut into chunks of at most Lmax = KB * B samples, and a chunk runs, on
 // the bank's stream (S = the count at its start, read from device memory, so a captured launch replays with the state moving on):
@@ -41,9 +46,23 @@
 //   k_cv_output   one workgroup per (instance, channel, tile of min(B, 256) samples aligned to the absolute count): the block's inputs up to
 //                 the tile's end and the taps they meet are staged in LDS, one lane per sample adds pend + head,
 //   k_cv_advance  one lane: n += L.
+// A routed bank (fdsp_convolve_routed_create; NG > 0) keeps xin and spec per (instance, INPUT) -- [V][I][Rx], [V][I][R][B + 1]; k_cv_input and
+// k_cv_forward run over V x I rows -- and zbuf, pend, h and G per (instance, output) as above.  The outputs of one input, in increasing
+// output order, are cut into FAN GROUPS of at most CV_FAN = 2; the groups (full ones first) are part of CvConst, passed by value with every
+// launch, never read from device memory.  Tail and head run per group instead of per output:
+//   k_cv_tail_fan<F>    a lane owns bin k of one (instance, group) for CV_J boundaries: each X of the group's input is loaded ONCE and enters
+//                       the F x CV_J sums of the group's outputs, every sum with its own window of response bins and p increasing from zero,
+//   k_cv_output_fan<F>  one workgroup per (instance, group, tile): the block's input samples are staged in LDS once, the taps of the F outputs
+//                       behind them ((1 + F) * B floats: 48 KiB at B = 4096, F = 2, under the 64 KiB a workgroup may take here); a lane
+//                       computes the F heads of its sample, each in the order above, from ONE read of every xs[r - i].
+// A group of one output runs the same two kernels at F = 1 (a permutation or the identity map is all such groups).  k_cv_inverse is the
+// plain bank's.  A plain bank (NG = 0) launches k_cv_tail / k_cv_output exactly as before.
 // M and P live on the device too (dims), so a replayed capture follows set_response.  KB = clamp(256 MiB / (V * C * (B + 1) * 8 B), 8, 64).
 // Memory: V*C * (Rx*4 + (R + KB)*(B + 1)*8 + (KB + 1)*B*4) + rows*C * ((Pcap + 1)*B*4 + Pcap*(B + 1)*8) bytes, rows = V with per-instance
-// responses, else 1.
+// responses, else 1.  Routed: V * (I * (Rx*4 + R*(B + 1)*8) + C * (KB*(B + 1)*8 + (KB + 1)*B*4)) plus the same response tables; KB keeps its
+// formula with C = outputs (zbuf is per output), so the chunks are the C-channel plain bank's.  A 1 -> 2 bank of 2 048 instances x 96 000
+// taps (B = 1024, Pcap = 94, KB = 8, R = 102, Rx = 16 384) saves one input's rings against the 2 -> 2 bank fed the input twice:
+// 2 048 * (16 384*4 + 102*1 025*8) = 1 847 164 928 bytes, 1.72 GiB of the 2 -> 2 bank's 3.83 GiB of state.
 //
 // Accuracy of the statement against a float64 convolution, max |y - y64| / (sum |h| * max |x|) (tests/test_convolve_ref.py, four times the
 // largest figure measured over 8 seeds): 4.1e-7 at B = 64, 9.5e-7 at B = 128 .. 4096.  The error follows sqrt(P) * log2(2B) * 2^-24 with a
@@ -60,6 +79,7 @@ namespace fd {
 constexpr int CV_MAX_CH = 8;
 constexpr int CV_MIN_LOGB = 6, CV_MAX_LOGB = 12;   // B = 64 .. 4096
 constexpr int CV_J = 8;                            // block boundaries per lane of the tail kernel
+constexpr int CV_FAN = 2;                          // outputs of one input that a fan group renders together (routed banks)
 
 struct CvConst {
     int B, logB, C;
@@ -73,11 +93,17 @@ struct CvConst {
     const float2* tw;         // [B] (cos, -sin)(2 pi j / 2B)
     const float* h;           // [rows][C][Hcap]
     const float2* G;          // [rows][C][Pcap][B + 1]
+    // routing (the contract's last bullet); a plain bank has I = C, the identity map and NG = 0
+    int I;                    // inputs, 1 .. C
+    int source[CV_MAX_CH];    // output c reads input source[c]
+    int NG, NG2;              // fan groups; the first NG2 hold CV_FAN outputs, the others one.  NG = 0: the plain kernel sequence
+    int gsrc[CV_MAX_CH];      // a group's input
+    int gout[CV_MAX_CH][CV_FAN];   // its outputs, increasing (a group of one repeats its output)
 };
 
 struct CvState {
-    float* xin;               // [V][C][Rx]
-    float2* spec;             // [V][C][R][B + 1]
+    float* xin;               // [V][I][Rx]
+    float2* spec;             // [V][I][R][B + 1]
     float2* zbuf;             // [V][C][KB][B + 1]
     float* pend;              // [V][C][KB + 1][B]
     unsigned long long* samples;   // [1] samples since reset
@@ -86,6 +112,9 @@ struct CvState {
 
 // host: B for a response capacity; the largest capacity a bank takes
 int cv_block_length(size_t max_len);
+// host: I, source and the fan groups of `c` (C set) from a source map of C entries that the caller has checked; fan = false: the plain bank
+// (source may be NULL: the identity map, no groups)
+void cv_set_routing(CvConst& c, int inputs, const int* source, bool fan);
 constexpr size_t CV_MAX_LEN = (size_t)1 << 24;
 
 namespace cv_ieee {

@@ -505,7 +505,7 @@ class ConvolveFx final : public FxBank {
     // (the pointers of `c` are another instance's)
     ConvolveFx(const CvConst& c, int ftz, size_t V, size_t max_len) : c_(c), ftz_(ftz), V_(V), max_len_(max_len) { for (const Buf& b : bufs()) *b.p = nullptr; }
     ~ConvolveFx() override { free_bufs(bufs()); }
-    int inputs() const override { return c_.C; }
+    int inputs() const override { return c_.I; }   // (a plain bank has I = C; a routed one shares an input among several outputs)
     int outputs() const override { return c_.C; }
     // Convolver has no set_sample_rate override: the response's own rate is ignored and nothing depends on the bank's
     int set_sample_rate(double, hipStream_t) override { return FDSP_OK; }
@@ -567,9 +567,10 @@ class ConvolveFx final : public FxBank {
         return FDSP_OK;
     }
     Bufs bufs() {   // the tables first
-        const size_t B = (size_t)c_.B, B1 = B + 1, rc = (size_t)c_.rows * c_.C, vc = V_ * c_.C;
+        // the input ring and the spectrum ring per (instance, input), the rest per (instance, output)
+        const size_t B = (size_t)c_.B, B1 = B + 1, rc = (size_t)c_.rows * c_.C, vc = V_ * c_.C, vi = V_ * c_.I;
         return {{(void**)&c_.tw, B * sizeof(float2)}, {(void**)&c_.h, rc * c_.Hcap * sizeof(float)}, {(void**)&c_.G, rc * c_.Pcap * B1 * sizeof(float2)},
-                {(void**)&st_.xin, vc * (size_t)c_.Rx * sizeof(float)}, {(void**)&st_.spec, vc * (size_t)c_.R * B1 * sizeof(float2)},
+                {(void**)&st_.xin, vi * (size_t)c_.Rx * sizeof(float)}, {(void**)&st_.spec, vi * (size_t)c_.R * B1 * sizeof(float2)},
                 {(void**)&st_.zbuf, vc * (size_t)c_.KB * B1 * sizeof(float2)}, {(void**)&st_.pend, vc * (size_t)(c_.KB + 1) * B * sizeof(float)},
                 {(void**)&st_.samples, sizeof(unsigned long long)}, {(void**)&st_.dims, 2 * sizeof(int)}};
     }
@@ -722,12 +723,13 @@ int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** 
     return FDSP_OK;
 }
 
-int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
+int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, int inputs, const int* source, hipStream_t s, std::unique_ptr<FxBank>* out) {
     const size_t V = instances;
     CvConst c{};
     c.B = cv_block_length(sp.max_len);
     while ((1 << c.logB) < c.B) c.logB++;
     c.C = sp.channels;
+    cv_set_routing(c, source ? inputs : sp.channels, source, source != nullptr);   // source NULL: fdsp_convolve_create, the plain kernel sequence
     c.rows = sp.per_instance ? (int)V : 1;
     c.Pcap = (int)((sp.max_len + c.B - 1) / c.B);
     c.Hcap = (size_t)(c.Pcap + 1) * c.B;

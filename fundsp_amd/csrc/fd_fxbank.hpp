@@ -71,7 +71,9 @@ int fx_resynth_fn_compile(const fdsp_resynth_fn_spec& spec, std::shared_ptr<cons
 int fx_resynth_params(FxBank* fx, size_t first, size_t count, float** row0, size_t* row_floats);
 // fdsp_resynth_set_band / _gain: checks the bank (`fx` may be NULL) and the rows; the device address of row `first` and the floats per row
 int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** row0, size_t* row_floats);
-int fx_convolve(size_t instances, const fdsp_convolve_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// source NULL: the plain bank of fdsp_convolve_create; else the routed bank of fdsp_convolve_routed_create (`inputs` and the `channels`
+// entries of `source` checked by the caller; read during the call only)
+int fx_convolve(size_t instances, const fdsp_convolve_spec& spec, int inputs, const int* source, hipStream_t stream, std::unique_ptr<FxBank>* out);
 // fdsp_convolve_set_response: _check refuses what is not a convolver bank (`fx` may be NULL), a length beyond the capacity and rows out of
 // range before anything is touched; _response uploads [count][channels][len] for rows first .. first+count-1, transforms the partitions on
 // `stream` and clears the history (the caller waits for the stream: the host array is borrowed)

@@ -58,7 +58,9 @@ class Graph:
     def __xor__(self, other):  # Branch, combinator.rs `^`
         if self.nin != other.nin:
             raise TypeError("Branch arity mismatch")
-        return self._pair(other, "Branch", self.nin, self.nout + other.nout)
+        g = self._pair(other, "Branch", self.nin, self.nout + other.nout)
+        g.branch_parts = (self, other)   # convolve_route_plan: a branch of convolvers is one bank that routes an input to several responses
+        return g
 
     def __invert__(self):      # Thru, combinator.rs `!`
         return Graph(f"Thru<{self.type}>", self.nin, self.nin, [((0,) + p, f, v, u) for p, f, v, u in self.params],
@@ -979,8 +981,8 @@ struct ConvolvePing {
 
 def convolve(response, channel=0):
     """convolve(&wave, channel) (prelude.rs:3154-3160): a 1 -> 1 convolver with channel `channel` of the Wave `response` ([len] or
-    [channels, len]; the Wave's sample rate plays no part).  Bank.from_graph renders the node alone, a stack of them, or either as the last
-    node of a pipe."""
+    [channels, len]; the Wave's sample rate plays no part).  Bank.from_graph renders the node alone, a stack of them, a branch of them (`a ^ b`: one
+    input through several responses, convolve_route_plan), or any of these as the last node of a pipe."""
     w = np.asarray(response, dtype=np.float32)
     if w.ndim == 1:
         w = w[None]
@@ -1018,3 +1020,32 @@ def convolve_plan(graph):
     for c, r in enumerate(rs):
         h[c, :len(r)] = r
     return h
+
+
+def convolve_route_plan(graph):
+    """(h [outputs, len], source, inputs) when `graph` is a tree of stacks `|` and branches `^` over convolve(..) leaves -- output c convolves
+    input source[c] with h[c] (Bank.convolve(.., source=source)) --, else None.  A leaf is one input into one output; `a | b` puts b's
+    inputs behind a's; `a ^ b` gives both the same inputs.  Shorter responses are zero-padded to the longest."""
+    def walk(g):
+        if getattr(g, "convolve_response", None) is not None:
+            return [g.convolve_response], [0], 1
+        st, br = getattr(g, "stack_parts", None), getattr(g, "branch_parts", None)
+        if st is None and br is None:
+            return None
+        a, b = (walk(p) for p in (st or br))
+        if a is None or b is None:
+            return None
+        if st is not None:
+            return a[0] + b[0], a[1] + [i + a[2] for i in b[1]], a[2] + b[2]
+        return (a[0] + b[0], a[1] + b[1], a[2]) if a[2] == b[2] else None   # (Graph.__xor__ has checked the arities)
+
+    plan = walk(graph)
+    if plan is None:
+        return None
+    rs, source, inputs = plan
+    if len(rs) > 8:
+        raise ValueError(f"convolve: {len(rs)} convolvers in one tree of stacks and branches (a bank takes 1 .. 8 outputs)")
+    h = np.zeros((len(rs), max(len(r) for r in rs)), dtype=np.float32)
+    for c, r in enumerate(rs):
+        h[c, :len(r)] = r
+    return h, source, inputs

@@ -418,6 +418,24 @@ typedef struct fdsp_convolve_spec {
 } fdsp_convolve_spec;
 int fdsp_convolve_create(size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out);
 int fdsp_convolve_create_on(int device, size_t instances, const fdsp_convolve_spec* spec, fdsp_bank** out);
+/* Routed convolver banks: ONE input through SEVERAL responses, the reference's Branch of convolvers -- a mono voice into a stereo room is
+ * convolve(&w, 0) ^ convolve(&w, 1), a stereo source into a four-channel response (ll ^ lr) | (rl ^ rr).  The bank has `inputs` inputs and
+ * spec->channels outputs, 1 <= inputs <= channels <= 8; output c is the 1 -> 1 convolver of the contract above with response row c,
+ * reading input source[c] (source holds `channels` entries in [0, inputs), borrowed for the call; every input feeds at least one output).
+ * No operation and no order changes: the bits are those of fdsp_convolve_create fed copies of the input rows, and the identity map gives
+ * the plain constructor's bits.  What is shared is the input side -- the input ring, the forward transform of every block and the
+ * spectrum ring (the frequency-domain delay line) exist once per (instance, INPUT); the response tables, the partition sums, the inverse
+ * transform, the pending ring and the direct head stay per (instance, OUTPUT), and outputs of one input are rendered two at a time from
+ * one load of each block spectrum and of each input sample (fd_convolve.hpp "fan groups").  KB keeps its formula with channels = outputs,
+ * so the chunks are the plain bank's, and a bank takes
+ *   instances x (inputs x (Rx x 4 + (Pcap + KB) x (B + 1) x 8) + channels x (KB x (B + 1) x 8 + (KB + 1) x B x 4))
+ *     + rows x channels x ((Pcap + 1) x B x 4 + Pcap x (B + 1) x 8)
+ * bytes.  response, fdsp_convolve_set_response (rows [channels][len], channels = outputs), reset, clone, set_sample_rate, capture and
+ * the FDSP_ENOTSUP answers are those of fdsp_convolve_create.  FDSP_EINVAL with a message that names the field, before anything is
+ * allocated or a device is touched: what fdsp_convolve_create refuses, inputs < 1 or inputs > channels, source NULL, an entry outside
+ * [0, inputs), an input that feeds no output. */
+int fdsp_convolve_routed_create(size_t instances, const fdsp_convolve_spec* spec, int inputs, const int* source, fdsp_bank** out);
+int fdsp_convolve_routed_create_on(int device, size_t instances, const fdsp_convolve_spec* spec, int inputs, const int* source, fdsp_bank** out);
 /* Re-initialise the convolvers between launches, as Convolver::set_response does: rows first .. first+count-1 take h_response
  * [count][channels][len] (borrowed for the call), their partitions are transformed on the device, and the history of the WHOLE bank is
  * cleared (the instances share one sample counter).  len takes 1 .. max_len; a bank has one response length, so replacing only some of

@@ -616,6 +616,14 @@ class Bank {
         b.kind_ = "convolve";
         return b;
     }
+    // one input through several responses, `convolve(&w, 0) ^ convolve(&w, 1)` (fdsp_convolve_routed_create): spec.channels outputs, output c
+    // convolves input source[c] (spec.channels entries in [0, inputs)) with response row c
+    static Bank convolve_routed(size_t instances, const fdsp_convolve_spec& spec, int inputs, const int* source) {
+        Bank b;
+        check(fdsp_convolve_routed_create(instances, &spec, inputs, source, &b.h_));
+        b.kind_ = "convolve";
+        return b;
+    }
     // Convolver::set_response for rows first .. first+count-1: h_response [count][channels][len]; the bank's history is cleared
     void set_response(const float* h_response, size_t len, size_t first = 0, size_t count = 1) {
         check(fdsp_convolve_set_response(h_, h_response, len, first, count));

@@ -131,6 +131,7 @@ pub mod ffi {
         pub fn fdsp_resynth_set_band(bank: *mut FdspBank, lo_hi: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_resynth_set_gain(bank: *mut FdspBank, gain: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_convolve_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_convolve_routed_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, inputs: c_int, source: *const c_int, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_convolve_set_response(bank: *mut FdspBank, response: *const f32, len: usize, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_destroy(bank: *mut FdspBank);
         pub fn fdsp_bank_clone(bank: *const FdspBank, out: *mut *mut FdspBank) -> c_int; // Clone: slots, rings, sample rate, options, events
@@ -453,6 +454,31 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         };
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_convolve_create_on(device as c_int, instances, &spec, &mut bank) })?;
+        Self::adopt(bank, "convolve", instances)
+    }
+
+    /// One input through several responses, `convolve(&w, 0) ^ convolve(&w, 1)` (fdsp_convolve_routed_create): a bank of `inputs` inputs
+    /// and `source.len()` outputs whose output c convolves input `source[c]` with response row c; `response` as for [`Self::convolve`]
+    /// with channels = outputs.  Outputs of one input share its input ring and spectrum ring; the bits are those of [`Self::convolve`] fed
+    /// copies of the input rows.  Source only: no Rust toolchain has built it.
+    pub fn convolve_routed(instances: usize, inputs: usize, source: &[i32], response: &[f32], len: usize, max_len: usize, per_instance: bool,
+                           flush_denormals: bool, device: i32) -> Result<Self, String> {
+        let rows = if per_instance { instances } else { 1 };
+        let channels = source.len();
+        if channels < 1 || channels > 8 || len < 1 || response.len() != rows * channels * len {
+            return Err("HipBank::convolve_routed: response needs rows x outputs x len taps (rows = instances with per_instance), 1 .. 8 outputs".into());
+        }
+        let spec = FdspConvolveSpec {
+            channels: channels as c_int,
+            max_len,
+            len,
+            per_instance: per_instance as c_int,
+            flush_denormals: flush_denormals as c_int,
+            response: response.as_ptr(),
+        };
+        let src: Vec<c_int> = source.iter().map(|&i| i as c_int).collect();
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_convolve_routed_create_on(device as c_int, instances, &spec, inputs as c_int, src.as_ptr(), &mut bank) })?;
         Self::adopt(bank, "convolve", instances)
     }
 
