@@ -15,15 +15,21 @@ def tabs(N):
     return R.tables(N, O.lib().o_math_cosf)
 
 
+SIZES = [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192]   # every window length the library instantiates (LOGN = 2 .. 13)
+
+
 def test_pass_through_is_the_input_delayed_by_the_window():
-    """tests/test_basic.rs:662-686: resynth::<U1, U1, _>(32, pass) returns x[t - 32] from t = 64 on within 1e-6; every N: a stated bound"""
+    """tests/test_basic.rs:662-686: resynth::<U1, U1, _>(32, pass) returns x[t - 32] from t = 64 on within 1e-6; every N: a stated bound
+    (1e-6 up to 256, 2e-6 at 512 and 1024, 4e-6 above)"""
     rng = np.random.default_rng(0)
-    for N, tol in ((32, 1e-6), (4, 1e-6), (64, 1e-6), (256, 1e-6), (1024, 2e-6), (4096, 4e-6), (8192, 4e-6)):
+    for N, tol in ((32, 1e-6), (4, 1e-6), (64, 1e-6), (256, 1e-6), (1024, 2e-6), (4096, 4e-6), (8192, 4e-6),
+                   (8, 1e-6), (16, 1e-6), (128, 1e-6), (512, 2e-6), (2048, 4e-6)):
         T = 3 * N + 100
         x = rng.uniform(-1.0, 1.0, (1, 1, T)).astype(np.float32)
         y = R.render(x, N, tabs=tabs(N))
         assert not y[0, 0, :N].any(), "silent for t < N"
         err = np.abs(y[0, 0, 2 * N:] - x[0, 0, N:T - N]).max()
+        print(f"pass-through N={N}: max error {err:.3e} (bound {tol:.0e})")
         assert err <= tol, (N, err)
 
 
@@ -42,7 +48,7 @@ def stft64(x, N, proc_bins):
     return y
 
 
-@pytest.mark.parametrize("N", [32, 256, 1024])
+@pytest.mark.parametrize("N", SIZES)
 def test_restated_fft_and_processors_against_float64(N):
     rng = np.random.default_rng(N)
     T = 4 * N + 37
@@ -52,7 +58,9 @@ def test_restated_fft_and_processors_against_float64(N):
     seg = (x[0, 0, :N] * hann).astype(np.float32)
     Xr, Xi = R.rfft(seg, tw, R._Ops(False))
     ref = np.fft.rfft(seg.astype(np.float64))
-    assert np.abs((Xr + 1j * Xi) - ref).max() <= 1e-6 * np.log2(N) * np.abs(ref).max()
+    err = np.abs((Xr + 1j * Xi) - ref).max()
+    print(f"N={N} rfft: max error {err:.3e}, {100.0 * err / (1e-6 * np.log2(N) * np.abs(ref).max()):.2f} % of the bound")
+    assert err <= 1e-6 * np.log2(N) * np.abs(ref).max()
     sr = 44100.0
     lo, hi = 2000.0, 9000.0
     fr = np.float32(np.float32(sr) / np.float32(N)) * np.arange(N // 2 + 1, dtype=np.float32)
@@ -61,10 +69,12 @@ def test_restated_fft_and_processors_against_float64(N):
     for proc, kw, f in (("band", dict(band=(lo, hi)), lambda Y: Y * band), ("gain", dict(gain=g), lambda Y: Y * g.astype(np.float64))):
         y = R.render(x, N, processor=proc, tabs=(hann, tw), **kw)[0, 0]
         want = stft64(x[0, 0], N, f)
-        assert np.abs(y - want).max() <= 1e-6 * np.log2(N) * max(1.0, np.abs(want).max()), proc
+        err, bound = np.abs(y - want).max(), 1e-6 * np.log2(N) * max(1.0, np.abs(want).max())
+        print(f"N={N} {proc}: max error {err:.3e}, {100.0 * err / bound:.2f} % of the bound {bound:.3e}")
+        assert err <= bound, proc
 
 
-@pytest.mark.parametrize("N", [4, 8, 64, 1024, 8192])
+@pytest.mark.parametrize("N", SIZES)
 def test_library_tables_equal_the_restatement(N):
     import fundsp_amd as F
 
