@@ -320,7 +320,9 @@ class Reverb3Fx final : public NetFx {
     int configure(double sr, hipStream_t s) override {
         Rv3Const c;
         if (!rv3_make_const(time_, diffusion_, flt_, sr, &c))
-            return api_fail(FDSP_EINVAL, "reverb3_stereo: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule; >= 14.2 kHz)");
+            // rv3_make_const: the shortest line, round(400 / 44100 * sr) + 1, reaches 129 at 14056.875 Hz; the longest, round(1123 / 44100 * sr) + 1, passes 2^20 at 41.177 MHz
+            return api_fail(FDSP_EINVAL, "reverb3_stereo: every delay must exceed 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule; >= 14057 Hz) "
+                                         "and none may exceed 2^20 samples (< 41.17 MHz)");
         const bool first = st_.pre == nullptr;
         Rv3State st = st_;   // (pre, wpre and fval are allocated once)
         if (hipError_t e = alloc_bufs(bufs(c, st, first))) return hip_fail(e, "reverb3_stereo buffers");
