@@ -13,8 +13,14 @@ fitness_f64: numpy float64 throughout, np.fft.rfft, the means from a cumulative 
 fitness_f32_serial: the reference's own order in f32 -- one serial `fitness +=` / `-=` chain over both channels, weights 1 / (i as f32), the
 f32 window, the running `sum -= norm0; sum += norm1`, hypot norms -- with the spectrum taken from the f64 FFT of the f32 windowed samples and
 rounded to f32 (microfft's own rounding is not restated).  Its terms are the same serial sums started from 0 each.
-`window` is the reference's outlier_samples; the small hand-computed cases of the tests pass a shorter one."""
+`window` is the reference's outlier_samples; the small hand-computed cases of the tests pass a shorter one.
+
+fitness_device_order: the DEVICE's order (fundsp_amd/csrc/fd_fitness.hpp, "ORDER OF THE SUMS"), operation for operation in f32 -- the lanes'
+partial sums, the fold tree, the windowed and packed row through resynth_ref.rfft (the project's radix-2 FFT), the norms through f64, every
+mean summed afresh, the 0.1 once after the fold.  Every step is one f32 rounding, no FMA: the device's bits, not a tolerance."""
 import numpy as np
+
+import resynth_ref
 
 THRESHOLD = np.float32(1.0e-9)
 OUTLIER_WEIGHT = 0.1
@@ -104,3 +110,84 @@ def fitness_f32_serial(response, window=OUTLIER_SAMPLES):
         chain += [w, -p]
         terms += [_serial_sum(w), _serial_sum(p)]
     return _serial_sum(np.concatenate(chain)), np.array(terms, dtype=np.float32)
+
+
+def _lane_sums(terms, lanes):
+    """lane t's sum of terms[t], terms[t + lanes], .. added in that order from 0.0; terms [count] or [count, parts] (the parts of one index
+    are added in order before the next index).  A term that does not count is +0.0: x + 0.0 == x for the sums here, which never go below +0.0"""
+    terms = np.asarray(terms, dtype=np.float32)
+    if terms.ndim == 1:
+        terms = terms[:, None]
+    rounds = -(-terms.shape[0] // lanes)
+    pad = np.zeros((rounds * lanes, terms.shape[1]), dtype=np.float32)
+    pad[:terms.shape[0]] = terms
+    pad = pad.reshape(rounds, lanes, terms.shape[1])
+    acc = np.zeros(lanes, dtype=np.float32)
+    for r in range(rounds):
+        for p in range(terms.shape[1]):
+            acc = acc + pad[r, :, p]
+    return acc
+
+
+def _fold(red):
+    """red[t] += red[t + s], s = lanes/2 .. 1: red[0]"""
+    red = np.array(red, dtype=np.float32)
+    assert len(red) & (len(red) - 1) == 0, "the lanes are a power of two"
+    s = len(red) // 2
+    while s >= 1:
+        red[:s] = red[:s] + red[s:2 * s]
+        s //= 2
+    return red[0]
+
+
+def _device_order(response, hann, tw, lanes=1024, window=OUTLIER_SAMPLES, echo_first=1, strict_threshold=False, hann_shift=0, pen_first=None,
+                  pen_stop=None, mean_bins=None, mean_shift=0, weight_per_term=False):
+    """fitness_device_order and, through the options after `window`, single-fault variants of it for the tests that check that the crafted
+    responses tell them apart (tests/test_reverb_fitness_order_host.py).  The defaults are the header's order."""
+    f = np.float32
+    r = np.asarray(response, dtype=np.float32)
+    assert r.ndim == 2 and r.shape[0] == 2
+    n = r.shape[1]
+    nh = n // 2
+    hann, tw = np.asarray(hann, dtype=np.float32), np.asarray(tw, dtype=np.float32).reshape(-1, 2)
+    assert hann.shape == (n,) and tw.shape == (nh, 2) and nh > window + 1
+    op = resynth_ref._Ops(False)
+    i = np.arange(n)
+    pen_first = window + 1 if pen_first is None else pen_first
+    pen_stop = nh if pen_stop is None else pen_stop
+    mean_bins = window if mean_bins is None else mean_bins
+    terms = []
+    for c in range(2):
+        # echo_c: lane t over i = 2m, 2m + 1, m = t, t + lanes, ..
+        counts = (np.abs(r[c]) > THRESHOLD) if strict_threshold else (np.abs(r[c]) >= THRESHOLD)
+        counts &= i >= echo_first
+        with np.errstate(divide="ignore"):
+            w = np.where(counts, f(1.0) / i.astype(np.float32), f(0.0)).astype(np.float32)
+        terms.append(_fold(_lane_sums(w.reshape(nh, 2), lanes)))
+        # the windowed row, packed and transformed; the norms through f64
+        xw = (r[c] * np.roll(hann, -hann_shift)).astype(np.float32)
+        xr, xi = resynth_ref.rfft(xw, tw, op)
+        re, im = xr[:nh].astype(np.float64), xi[:nh].astype(np.float64)
+        im[0] = float(xr[nh])                                # bin 0 packs (DC, Nyquist)
+        norm = np.sqrt(re * re + im * im).astype(np.float32)
+        # mean_k afresh per bin, ascending j from 0.0
+        k = np.arange(pen_first, pen_stop)
+        s = np.zeros(len(k), dtype=np.float32)
+        for j in range(mean_bins):
+            s = s + norm[k - mean_bins + mean_shift + j]
+        mean = s / f(mean_bins)
+        n1 = norm[k]
+        d = n1 - mean
+        sq = np.where(n1 > mean, d * d, f(0.0)).astype(np.float32)
+        if weight_per_term:
+            terms.append(_fold(_lane_sums(sq * f(OUTLIER_WEIGHT), lanes)))
+        else:
+            terms.append(_fold(_lane_sums(sq, lanes)) * f(OUTLIER_WEIGHT))
+    t = np.array(terms, dtype=np.float32)
+    return ((t[0] - t[1]) + t[2]) - t[3], t
+
+
+def fitness_device_order(response, hann, tw, lanes=1024, window=OUTLIER_SAMPLES):
+    """(fitness, [echo_0, pen_0, echo_1, pen_1]) as f32, in the order fd_fitness.hpp states.  hann [N], tw [N/2, 2] = (cos, -sin): the tables
+    of resynth_ref.tables(N, the oracle's cosf).  `lanes` (a power of two) and `window` are parameters for the small cases checked by hand."""
+    return _device_order(response, hann, tw, lanes, window)

@@ -10,7 +10,12 @@ the reference's own f32 order -- from fitness_f64, per term and for the total, o
 deviate from fitness_f64 by 4 * delta: another (fixed) summation order and the project's f32 FFT are f32 effects of the same size.
 
 Measured on one MI355X (relative, per echo_0 pen_0 echo_1 pen_1 | total; test_terms_and_total_within_the_yardstick prints
-them): delta 2.6e-6 1.2e-5 1.8e-6 1.1e-5 | 4.8e-5; the device's largest deviation 3.0e-8 1.4e-7 6.5e-8 1.7e-7 | 1.9e-7."""
+them): delta 2.6e-6 1.2e-5 1.8e-6 1.1e-5 | 4.8e-5; the device's largest deviation 3.0e-8 1.4e-7 6.5e-8 1.7e-7 | 1.9e-7.
+
+What is pinned how: the tolerance here says that the device's order computes reverb_fitness -- it is held to float64, a reference that shares
+nothing with the kernel -- and leaves 1e-5 and more per term.  The arithmetic itself, all four terms and the total of these same banks and of
+responses crafted for the loop bounds and the threshold, is pinned bit for bit by tests/test_gpu_reverb_fitness_bits.py against
+reverb_fitness_ref.fitness_device_order, the restatement of fd_fitness.hpp's order; banks(), responses() and scores() are shared with it."""
 import numpy as np
 import pytest
 
