@@ -17,7 +17,9 @@
 //                                   svfp_carry:  s_{c+1}.x = fma(P00, s_c.x, P01 * s_c.y) + z_c.x         (.y: P10, P11, z_c.y)
 //                                   s_0 = the state carried in from the previous block, s_K goes to the next one (and to ic1eq / ic2eq).
 // Every operation is f32 but the table build.  The two FMAs of svfp_fix / svfp_carry are explicit and everything else is kept
-// uncontracted (pragma below, and the library is built with -ffp-contract=off): host and device compute the same bits.
+// uncontracted (pragma below, and the library is built with -ffp-contract=off): host and device compute the same bits.  Checked:
+// tests/svf_par_ref.py restates this order in numpy, tests/test_svf_par_ref.py holds a host build of this header to it and
+// tests/test_gpu_svf_par_bits.py the kernel, frames and end state, as uint32.
 //
 // Accuracy (tests/test_svf_par_host.py): a chunk pass starts from zero, so its rounding errors grow over LC frames
 // instead of the whole launch, and the carried state goes through ONE rounded 2 x 2 product per chunk instead of LC ticks -- against an

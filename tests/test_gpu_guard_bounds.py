@@ -13,6 +13,7 @@ import oracle as O
 from fundsp_amd import LAYOUT_VOICE_MINOR, MIX_PAN, MODE_PROCESS
 from fundsp_amd import workloads as W
 from guard_bound_rows import edge_rows
+from svf_par_ref import tick
 from test_gpu_parity import assert_bit_equal, run_bank
 
 pytestmark = pytest.mark.gpu
@@ -50,13 +51,7 @@ def reference_rows(lengths):
     two = F(2.0)
     with np.errstate(all="ignore"):
         for t in range(total):  # SvfCore::tick, the reference's operations in the reference's order, all rows at once
-            v0 = x[:, t]
-            v3 = v0 - ic2
-            v1 = a1 * ic1 + a2 * v3
-            v2 = ic2 + a2 * ic1 + a3 * v3
-            ic1 = two * v1 - ic1
-            ic2 = two * v2 - ic2
-            y[:, t] = m0 * v0 + m1 * v1 + m2 * v2
+            y[:, t], ic1, ic2 = tick((a1, a2, a3, m0, m1, m2), ic1, ic2, x[:, t], two)
     rest = np.array([not r[8] for r in ROWS])
     assert_bit_equal(y[rest], full[rest], "the numpy SVF tick equals the oracle's filter where it starts from rest")
     _REF[key] = y

@@ -109,27 +109,35 @@ def test_geometry(gpu, V, T):
         assert_bit_equal(par.get_slot(slot), ser.get_slot(slot), slot)
 
 
-def test_config1_kind(gpu):
-    """sine_hz(f) >> lowpass_hz(fc, q): the other kind that has the kernel"""
-    V, T = 100, 192
+def config1_params(V):
     rng = np.random.default_rng(5)
     f = (55.0 * 2.0 ** (5.0 * rng.random(V))).astype(np.float32)
     fc = (100.0 * 2.0 ** (7.0 * rng.random(V))).astype(np.float32)
     q = (0.5 + 3.5 * rng.random(V)).astype(np.float32)
+    return dict(f=f, fc=fc, q=q)
 
-    def bank(svf_exec, mode, gain):
-        b = gpu.Bank("sine_hz_lowpass_hz", V)
-        b.set_param("0.0:value[0]", f)
-        b.set_param("1:cutoff", fc)
-        b.set_param("1:q", q)
-        b.set_param("1:mode", mode.astype(np.float32))
-        b.set_param("1:gain", gain)
-        b.set_sample_rate(SR)
-        b.set_seed(np.arange(V, dtype=np.uint64))
-        b.set_option("math", MATH_FAST)
-        b.set_option("svf_exec", svf_exec)
-        return b
 
+def config1_bank(gpu, p, svf_exec, mode, gain):
+    """sine_hz(f) >> lowpass_hz(fc, q) with per-voice filter modes, tolerance mode"""
+    V = len(p["f"])
+    b = gpu.Bank("sine_hz_lowpass_hz", V)
+    b.set_param("0.0:value[0]", p["f"])
+    b.set_param("1:cutoff", p["fc"])
+    b.set_param("1:q", p["q"])
+    b.set_param("1:mode", mode.astype(np.float32))
+    b.set_param("1:gain", gain)
+    b.set_sample_rate(SR)
+    b.set_seed(np.arange(V, dtype=np.uint64))
+    b.set_option("math", MATH_FAST)
+    b.set_option("svf_exec", svf_exec)
+    return b
+
+
+def test_config1_kind(gpu):
+    """sine_hz(f) >> lowpass_hz(fc, q): the other kind that has the kernel"""
+    V, T = 100, 192
+    p = config1_params(V)
+    bank = lambda svf_exec, mode, gain: config1_bank(gpu, p, svf_exec, mode, gain)
     modes = np.arange(V) % 9
     par, ser, x = bank(SVF_PARALLEL, modes, 2.0), bank(SVF_SERIAL, modes, 2.0), bank(SVF_SERIAL, np.full(V, BELL), 1.0)
     assert par.get_option("has_svf_parallel") == 1
