@@ -103,6 +103,8 @@ SYMBOLS = {
     "fdsp_convolve_create_on": (_i, [_i, _sz, C.POINTER(ConvolveSpec), C.POINTER(_P)]),
     "fdsp_convolve_routed_create": (_i, [_sz, C.POINTER(ConvolveSpec), _i, C.POINTER(_i), C.POINTER(_P)]),
     "fdsp_convolve_routed_create_on": (_i, [_i, _sz, C.POINTER(ConvolveSpec), _i, C.POINTER(_i), C.POINTER(_P)]),
+    "fdsp_convolve_matrix_create": (_i, [_sz, C.POINTER(ConvolveSpec), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_P)]),
+    "fdsp_convolve_matrix_create_on": (_i, [_i, _sz, C.POINTER(ConvolveSpec), _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_P)]),
     "fdsp_convolve_set_response": (_i, [_P, _fp, _sz, _sz, _sz]),
     "fdsp_convolve_block_length": (_i, [_sz]),
     "fdsp_bank_set_bus": (_i, [_P, _i, _f, _f]),

@@ -436,7 +436,8 @@ class Bank:
         check(lib().fdsp_resynth_set_params(self._h, _fptr(t), int(first), t.shape[0]))
 
     @classmethod
-    def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None, source=None):
+    def convolve(cls, instances, response, channels=None, max_len=None, per_instance=False, flush_denormals=False, device=None, source=None,
+                 target=None):
         """Bank of `instances` x `channels` convolvers, convolve(&wave, channel) (convolve.rs) per channel, through the partitioned FFT
         convolution kernels (fdsp_convolve_create): y[n] = sum h[k] x[n - k], no latency, every split into launches the same bits.
         `response`: [len] or [channels, len], with per_instance=True [instances, channels, len].  `channels` defaults to the response's
@@ -445,13 +446,24 @@ class Bank:
         `source`: None -- channel c reads input c -- or one input index per output: the routed bank (fdsp_convolve_routed_create) of
         max(source) + 1 inputs whose output c convolves input source[c] with response row c, `convolve(&w, 0) ^ convolve(&w, 1)` being
         source=[0, 0].  Outputs of one input share its input ring, block transforms and spectrum ring; the bits are those of the plain bank
-        fed copies of the input rows."""
+        fed copies of the input rows.
+        `target`: None, or with `source` one output index per TERM, non-decreasing: the summing bank (fdsp_convolve_matrix_create) of
+        max(source) + 1 inputs, max(target) + 1 outputs and up to 16 terms (the response's channels); term t convolves input source[t] with
+        response row t and is added into output target[t] -- `convolve(&w, 0) + convolve(&w, 1)` being source=[0, 1], target=[0, 0], a
+        true-stereo response `(ll + rl) ^ (lr + rr)` source=[0, 1, 0, 1], target=[0, 0, 1, 1].  The terms of an output are summed before
+        its one inverse transform (tests/convolve_matrix_ref.py); an output of one term has the routed bank's bits."""
         V = int(instances)
-        h = convolve_response_rows(response, channels, V if per_instance else None)
+        if target is not None and source is None:
+            raise ValueError("convolve: target (one output index per term) needs source (one input index per term)")
+        h = convolve_response_rows(response, channels, V if per_instance else None, most=8 if target is None else 16)
         if source is not None:
             source = tuple(int(i) for i in source)
             if len(source) != h.shape[-2]:
-                raise ValueError(f"convolve: source needs one input index per output ({h.shape[-2]}), got {len(source)}")
+                raise ValueError(f"convolve: source needs one input index per {'output' if target is None else 'term'} ({h.shape[-2]}), got {len(source)}")
+        if target is not None:
+            target = tuple(int(o) for o in target)
+            if len(target) != h.shape[-2]:
+                raise ValueError(f"convolve: target needs one output index per term ({h.shape[-2]}), got {len(target)}")
         spec = _lib.ConvolveSpec()
         spec.channels, spec.len = h.shape[-2], h.shape[-1]
         spec.max_len = int(max_len) if max_len is not None else h.shape[-1]
@@ -462,22 +474,40 @@ class Bank:
         dev = -1 if device is None else int(device)
         if source is None:
             check(lib().fdsp_convolve_create_on(dev, V, C.byref(spec), C.byref(hd)))
-        else:
+        elif target is None:
             src = (C.c_int * len(source))(*source)
             check(lib().fdsp_convolve_routed_create_on(dev, V, C.byref(spec), max(source) + 1, src, C.byref(hd)))
+        else:
+            src, tgt = (C.c_int * len(source))(*source), (C.c_int * len(target))(*target)
+            check(lib().fdsp_convolve_matrix_create_on(dev, V, C.byref(spec), max(source) + 1, max(target) + 1, src, tgt, C.byref(hd)))
         b = cls("convolve", V, _handle=hd)
-        b.source = source
+        b.source, b.target = source, target
         b.max_len, b.block_length = int(spec.max_len), lib().fdsp_convolve_block_length(int(spec.max_len))
         b.per_instance = bool(per_instance)
         return b
 
+    @classmethod
+    def convolve_tree(cls, graph, instances, max_len=None, flush_denormals=False, device=None):
+        """The summing bank of a tree of `|`, `^` and `+` over convolve(..) leaves (graph.convolve_matrix_plan), e.g. the true-stereo
+        response `(ll + rl) ^ (lr + rr)`: Bank.convolve(.., source=term_input, target=term_output).  Bank.from_graph keeps refusing `+`
+        over convolvers; this is the constructor of its own."""
+        from . import graph as G
+
+        plan = G.convolve_matrix_plan(graph)
+        if plan is None:
+            raise ValueError("convolve_tree: the graph takes a tree of stacks `|`, branches `^` and sums `+` over convolve(..) leaves")
+        h, tin, tout, _, _ = plan
+        return cls.convolve(instances, h, max_len=max_len, flush_denormals=flush_denormals, device=device, source=tin, target=tout)
+
     def set_response(self, response, first=0):
         """Convolver::set_response for rows from `first` (fdsp_convolve_set_response): [len] or [channels, len] for one row, [rows, channels,
-        len] for several (rows are instances with per-instance responses, else the single row 0).  The history of the whole bank is cleared."""
+        len] for several (rows are instances with per-instance responses, else the single row 0; channels are the outputs, in a summing bank
+        the terms).  The history of the whole bank is cleared."""
         if self.kind != "convolve":
             raise ValueError("set_response: not a convolver bank")
         t = np.asarray(response, dtype=np.float32)
-        h = convolve_response_rows(t, self.outputs(), t.shape[0] if t.ndim == 3 else None)
+        tg = getattr(self, "target", None)
+        h = convolve_response_rows(t, self.outputs() if tg is None else len(tg), t.shape[0] if t.ndim == 3 else None, most=8 if tg is None else 16)
         if h.ndim == 2:
             h = h[None]
         check(lib().fdsp_convolve_set_response(self._h, _fptr(h), h.shape[-1], int(first), h.shape[0]))
@@ -503,7 +533,7 @@ class Bank:
         check(lib().fdsp_bank_clone(self._h, C.byref(h)))
         b = Bank(self.kind, self.voices, _handle=h)
         b.sample_rate = self.sample_rate
-        for k in ("window", "params", "max_len", "block_length", "per_instance", "source"):
+        for k in ("window", "params", "max_len", "block_length", "per_instance", "source", "target"):
             if hasattr(self, k):
                 setattr(b, k, getattr(self, k))
         return b
@@ -810,17 +840,17 @@ class Bank:
         return ms.value
 
 
-def convolve_response_rows(response, channels, rows):
+def convolve_response_rows(response, channels, rows, most=8):
     """A convolver's response as the C ABI reads it: contiguous f32 [channels, len], or [rows, channels, len] when `rows` is given.  A [len]
-    response goes to every channel; a [1, len] one too."""
+    response goes to every channel; a [1, len] one too.  `most`: the channels a bank takes (16 terms in a summing bank)."""
     t = np.asarray(response, dtype=np.float32)
     if t.ndim < 1 or t.ndim > (2 if rows is None else 3) or t.shape[-1] < 1:
         raise ValueError(f"convolve: response takes [len], [channels, len]{'' if rows is None else ' or [instances, channels, len]'} with len >= 1; got shape {t.shape}")
     if rows is not None and t.ndim == 3 and t.shape[0] != rows:
         raise ValueError(f"convolve: a per-instance response needs {rows} rows, got {t.shape[0]}")
     Cn = int(channels) if channels is not None else (t.shape[-2] if t.ndim >= 2 else 1)
-    if not 1 <= Cn <= 8:
-        raise ValueError(f"convolve: channels takes 1 .. 8, got {Cn}")
+    if not 1 <= Cn <= most:
+        raise ValueError(f"convolve: channels takes 1 .. {most}, got {Cn}")
     if t.ndim == 1:
         t = t[None]
     if t.shape[-2] not in (1, Cn):

@@ -1285,16 +1285,18 @@ int fdsp_resynth_set_params(fdsp_bank* b, const float* h, size_t first, size_t c
     return FDSP_OK;
 }
 // ---- convolver banks (fd_fxbank.hpp fx_convolve) -------------------------------------------------------------------------------------------
-static int cv_check_spec(size_t instances, const fdsp_convolve_spec* sp) {
-    if (!sp) return fail(FDSP_EINVAL, "fdsp_convolve_create: spec NULL");
-    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_convolve_create: no instances");
-    if (sp->channels < 1 || sp->channels > 8) return fail(FDSP_EINVAL, "fdsp_convolve_create: channels takes 1 .. 8");
-    if (sp->max_len < 1 || sp->max_len > ((size_t)1 << 24)) return fail(FDSP_EINVAL, "fdsp_convolve_create: max_len (the response capacity) takes 1 .. 2^24 taps");
+// (`who`: the constructor named in the messages; a summing bank's channels are its terms, up to 16)
+static int cv_check_spec(size_t instances, const fdsp_convolve_spec* sp, const std::string& who = "fdsp_convolve_create: ", int max_channels = 8) {
+    if (!sp) return fail(FDSP_EINVAL, who + "spec NULL");
+    if (instances == 0) return fail(FDSP_EINVAL, who + "no instances");
+    if (sp->channels < 1 || sp->channels > max_channels)
+        return fail(FDSP_EINVAL, who + (max_channels == 8 ? "channels takes 1 .. 8" : "channels (the terms) takes 1 .. 16"));
+    if (sp->max_len < 1 || sp->max_len > ((size_t)1 << 24)) return fail(FDSP_EINVAL, who + "max_len (the response capacity) takes 1 .. 2^24 taps");
     if (sp->len < 1 || sp->len > sp->max_len)
-        return fail(FDSP_EINVAL, "fdsp_convolve_create: len = " + std::to_string(sp->len) + " takes 1 .. max_len = " + std::to_string(sp->max_len));
-    if (sp->per_instance != 0 && sp->per_instance != 1) return fail(FDSP_EINVAL, "fdsp_convolve_create: per_instance takes 0 or 1");
-    if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, "fdsp_convolve_create: flush_denormals takes 0 or 1");
-    if (!sp->response) return fail(FDSP_EINVAL, "fdsp_convolve_create: response NULL");
+        return fail(FDSP_EINVAL, who + "len = " + std::to_string(sp->len) + " takes 1 .. max_len = " + std::to_string(sp->max_len));
+    if (sp->per_instance != 0 && sp->per_instance != 1) return fail(FDSP_EINVAL, who + "per_instance takes 0 or 1");
+    if (sp->flush_denormals != 0 && sp->flush_denormals != 1) return fail(FDSP_EINVAL, who + "flush_denormals takes 0 or 1");
+    if (!sp->response) return fail(FDSP_EINVAL, who + "response NULL");
     return FDSP_OK;
 }
 int fdsp_convolve_create_on(int device, size_t instances, const fdsp_convolve_spec* sp, fdsp_bank** out) {
@@ -1324,6 +1326,40 @@ int fdsp_convolve_routed_create_on(int device, size_t instances, const fdsp_conv
 }
 int fdsp_convolve_routed_create(size_t instances, const fdsp_convolve_spec* spec, int inputs, const int* source, fdsp_bank** out) {
     return fdsp_convolve_routed_create_on(-1, instances, spec, inputs, source, out);
+}
+// a summing bank: the spec's checks, then the tables', all before a device is touched
+int fdsp_convolve_matrix_create_on(int device, size_t instances, const fdsp_convolve_spec* sp, int inputs, int outputs, const int* term_input,
+                                   const int* term_output, fdsp_bank** out) {
+    const std::string me = "fdsp_convolve_matrix_create: ";
+    if (!out) return fail(FDSP_EINVAL, me + "out is NULL");
+    *out = nullptr;
+    if (int rc = cv_check_spec(instances, sp, me, 16)) return rc;
+    if (inputs < 1 || inputs > 8) return fail(FDSP_EINVAL, me + "inputs = " + std::to_string(inputs) + " takes 1 .. 8");
+    if (outputs < 1 || outputs > 8) return fail(FDSP_EINVAL, me + "outputs = " + std::to_string(outputs) + " takes 1 .. 8");
+    if (!term_input) return fail(FDSP_EINVAL, me + "term_input NULL");
+    if (!term_output) return fail(FDSP_EINVAL, me + "term_output NULL");
+    unsigned fed = 0, made = 0;
+    for (int t = 0; t < sp->channels; t++) {
+        const std::string at = "[" + std::to_string(t) + "] = ";
+        if (term_input[t] < 0 || term_input[t] >= inputs)
+            return fail(FDSP_EINVAL, me + "term_input" + at + std::to_string(term_input[t]) + " takes 0 .. inputs - 1 = " + std::to_string(inputs - 1));
+        if (term_output[t] < 0 || term_output[t] >= outputs)
+            return fail(FDSP_EINVAL, me + "term_output" + at + std::to_string(term_output[t]) + " takes 0 .. outputs - 1 = " + std::to_string(outputs - 1));
+        if (t > 0 && term_output[t] < term_output[t - 1])
+            return fail(FDSP_EINVAL, me + "term_output" + at + std::to_string(term_output[t]) + " after " + std::to_string(term_output[t - 1]) + " (term_output is non-decreasing)");
+        fed |= 1u << term_input[t];
+        made |= 1u << term_output[t];
+    }
+    for (int o = 0; o < outputs; o++)
+        if (!(made >> o & 1u)) return fail(FDSP_EINVAL, me + "term_output names no term for output " + std::to_string(o) + " (every output has at least one term)");
+    for (int i = 0; i < inputs; i++)
+        if (!(fed >> i & 1u)) return fail(FDSP_EINVAL, me + "term_input names no term for input " + std::to_string(i) + " (every input feeds at least one term)");
+    return fx_bank_create(device, instances, FDSP_DEFAULT_SR, out,
+                          [&](hipStream_t s, FxPtr* fx) { return fd::fx_convolve_matrix(instances, *sp, inputs, outputs, term_input, term_output, s, fx); });
+}
+int fdsp_convolve_matrix_create(size_t instances, const fdsp_convolve_spec* spec, int inputs, int outputs, const int* term_input, const int* term_output,
+                                fdsp_bank** out) {
+    return fdsp_convolve_matrix_create_on(-1, instances, spec, inputs, outputs, term_input, term_output, out);
 }
 int fdsp_convolve_set_response(fdsp_bank* b, const float* h_response, size_t len, size_t first, size_t count) {
     if (!b || !h_response) return fail(FDSP_EINVAL, "fdsp_convolve_set_response: bank or response NULL");

@@ -80,7 +80,7 @@ __global__ void k_cv_input(CvConst c, CvState st, size_t V, const float* __restr
 
 // rfft_N of N = 2B real values, B-point working set in LDS; P lanes per unit, G units per 256-lane workgroup.
 // RESP = false: unit (f, instance, input) -- the block that completes f-th in the chunk, followed by B zeros -> spectrum ring.
-// RESP = true:  unit (p, row * C + channel) of rows [row0, ..) -- g_p of the stored taps -> response spectra.
+// RESP = true:  unit (p, row * NT + response row) of rows [row0, ..) -- g_p of the stored taps -> response spectra.
 template <int LOGB, bool RESP>
 __global__ __launch_bounds__(256) void k_cv_forward(CvConst c, CvState st, size_t units, size_t inner, int L, size_t row0) {
     constexpr int B = 1 << LOGB, N = 2 * B, P = B < 256 ? B : 256, G = 256 / P, NB = (B + P) / P;
@@ -88,19 +88,19 @@ __global__ __launch_bounds__(256) void k_cv_forward(CvConst c, CvState st, size_
     const int lane = threadIdx.x % P, g = threadIdx.x / P;
     const size_t unit = (size_t)blockIdx.x * G + g;
     const bool in_range = unit < units;
-    const size_t vc = in_range ? unit % inner : 0;   // instance * I + input, or (row - row0) * C + channel
+    const size_t vc = in_range ? unit % inner : 0;   // instance * I + input, or (row - row0) * NT + response row
     const size_t f = in_range ? unit / inner : 0;
     Cf* buf = lds + g * B;
     bool live = in_range;
     float2* dst;
     if (RESP) {
-        const float* __restrict__ hr = c.h + (row0 * c.C + vc) * c.Hcap + f * B;   // h[pB ..]: g_p[i] = hr[B + i] (i < B), hr[i - B] (i > B)
+        const float* __restrict__ hr = c.h + (row0 * c.NT + vc) * c.Hcap + f * B;   // h[pB ..]: g_p[i] = hr[B + i] (i < B), hr[i - B] (i > B)
         for (int m = lane; m < B; m += P) {
             const int i = 2 * m;
             const int o = i < B ? B + i : i - B;
             buf[bitrev(m, LOGB)] = Cf{i == B ? 0.0f : hr[o], hr[o + 1]};   // g_p[B] = 0: no output of the first B reads it
         }
-        dst = (float2*)c.G + ((row0 * c.C + vc) * c.Pcap + f) * (size_t)(B + 1);
+        dst = (float2*)c.G + ((row0 * c.NT + vc) * c.Pcap + f) * (size_t)(B + 1);
     } else {
         const u64 S = *st.samples;
         const u64 jb = S / B + f;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void k_cv_tail(CvConst c, CvState st, size_t V
     const long long jbase = j0 + 1 + bi0;
     const long long btop = jbase + J - 2;
     const size_t row = c.rows == 1 ? 0 : vc / c.C;
-    const float2* __restrict__ Gr = c.G + ((row * c.C + vc % c.C) * c.Pcap) * (size_t)B1 + k;
+    const float2* __restrict__ Gr = c.G + ((row * c.NT + vc % c.C) * c.Pcap) * (size_t)B1 + k;
     const float2* __restrict__ Xr = st.spec + vc * c.R * (size_t)B1 + k;
     Cf acc[J], gw[J];
 #pragma unroll
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_cv_tail_fan(CvConst c, CvState st, size
     Cf acc[F][J], gw[F][J];
 #pragma unroll
     for (int f = 0; f < F; f++) {
-        Gr[f] = c.G + ((row * c.C + c.gout[g][f]) * c.Pcap) * (size_t)B1 + k;
+        Gr[f] = c.G + ((row * c.NT + c.gout[g][f]) * c.Pcap) * (size_t)B1 + k;
 #pragma unroll
         for (int jj = 0; jj < J; jj++) acc[f][jj] = Cf{0.0f, 0.0f}, gw[f][jj] = Cf{0.0f, 0.0f};
     }
@@ -256,6 +256,70 @@ __global__ __launch_bounds__(256) void k_cv_tail_fan(CvConst c, CvState st, size
         for (int jj = 0; jj < J; jj++)
             if (bi0 + jj < nb) Z[(size_t)jj * B1] = make_float2(acc[f][jj].re, acc[f][jj].im);
     }
+}
+
+// The tail of a summing bank: one Z per (instance, output), ONE running sum across the output's terms.  A lane owns bin k of one (instance,
+// output) -- blockIdx.z picks the output, blockIdx.y the CV_J boundaries -- and keeps the CV_J sums in registers over all the terms; each
+// term runs k_cv_tail's whole step loop with its own response spectra, its own input's spectrum ring and its own window of response bins,
+// so sum jj takes term t's partitions p = 0, 1, 2, .. in order after every partition of the terms before it.  The conditions depend on
+// the block indices, the term and the step only: they are uniform over the workgroup, and the term tables of `c` are scalar.
+__global__ __launch_bounds__(256) void k_cv_tail_sum(CvConst c, CvState st, size_t V, int L) {
+    constexpr int J = CV_J;
+    const int B1 = c.B + 1;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= V * (size_t)B1) return;
+    const int k = (int)(idx % B1);
+    const size_t v = idx / B1;
+    const int o = (int)blockIdx.z;
+    const u64 S = *st.samples;
+    const int P = st.dims[1];
+    const long long j0 = (long long)(S / (u64)c.B);
+    const int nb = (int)((long long)((S + (u64)L) / (u64)c.B) - j0);   // boundaries j0 + 1 .. j0 + nb
+    const int bi0 = (int)blockIdx.y * J;
+    if (bi0 >= nb) return;
+    const long long jbase = j0 + 1 + bi0;
+    const long long btop = jbase + J - 2;
+    const size_t row = c.rows == 1 ? 0 : v;
+    Cf acc[J];
+#pragma unroll
+    for (int jj = 0; jj < J; jj++) acc[jj] = Cf{0.0f, 0.0f};
+    for (int t = c.tfirst[o]; t < c.tfirst[o + 1]; t++) {
+        const float2* __restrict__ Gr = c.G + ((row * c.NT + t) * c.Pcap) * (size_t)B1 + k;
+        const float2* __restrict__ Xr = st.spec + (v * c.I + c.tin[t]) * c.R * (size_t)B1 + k;
+        Cf gw[J];
+#pragma unroll
+        for (int jj = 0; jj < J; jj++) gw[jj] = Cf{0.0f, 0.0f};
+        for (int s0 = 0; s0 < P + J - 1; s0 += J) {
+#pragma unroll
+            for (int u = 0; u < J; u++) {
+                const int s = s0 + u;
+                if (s < P) {
+                    const float2 gv = Gr[(size_t)s * B1];
+                    gw[u] = Cf{gv.x, gv.y};
+                }
+                const long long b = btop - s;
+                Cf X{0.0f, 0.0f};
+                if (b >= 0 && b < j0 + nb) {
+                    const float2 xv = Xr[(size_t)((u64)b % (u64)c.R) * B1];
+                    X = Cf{xv.x, xv.y};
+                }
+#pragma unroll
+                for (int jj = 0; jj < J; jj++) {
+                    const int q = J - 1 - jj;
+                    const int p = s - q;
+                    if (bi0 + jj < nb && p >= 0 && p < P && b >= 0) {
+                        const Cf g = gw[(u - q + J) % J];
+                        const float pr = X.re * g.re - X.im * g.im, pi = X.re * g.im + X.im * g.re;
+                        acc[jj] = Cf{acc[jj].re + pr, acc[jj].im + pi};
+                    }
+                }
+            }
+        }
+    }
+    float2* __restrict__ Z = st.zbuf + ((v * c.C + o) * c.KB + bi0) * (size_t)B1 + k;
+#pragma unroll
+    for (int jj = 0; jj < J; jj++)
+        if (bi0 + jj < nb) Z[(size_t)jj * B1] = make_float2(acc[jj].re, acc[jj].im);
 }
 
 // irfft_N of Z, one unit per (boundary of the chunk, instance, channel), N complex values in LDS; the first B real values -> pend ring
@@ -310,7 +374,7 @@ __global__ void k_cv_output(CvConst c, CvState st, size_t V, int L, int ntiles, 
     float* hs = cv_lds + B;
     const size_t ch = vc % c.C, v = vc / c.C;
     const float* __restrict__ xr = st.xin + vc * (size_t)c.Rx;
-    const float* __restrict__ hr = c.h + ((c.rows == 1 ? 0 : v) * c.C + ch) * c.Hcap;
+    const float* __restrict__ hr = c.h + ((c.rows == 1 ? 0 : v) * c.NT + ch) * c.Hcap;
     const u64 xm = (u64)(c.Rx - 1);
     for (int i = threadIdx.x; i < cnt; i += TS) {
         xs[i] = xr[(j * B + i) & xm];
@@ -358,7 +422,7 @@ __global__ void k_cv_output_fan(CvConst c, CvState st, size_t V, int L, int ntil
     for (int i = threadIdx.x; i < cnt; i += TS) xs[i] = xr[(j * B + i) & xm];
 #pragma unroll
     for (int f = 0; f < F; f++) {
-        const float* __restrict__ hr = c.h + ((c.rows == 1 ? 0 : v) * c.C + c.gout[g][f]) * c.Hcap;
+        const float* __restrict__ hr = c.h + ((c.rows == 1 ? 0 : v) * c.NT + c.gout[g][f]) * c.Hcap;
         for (int i = threadIdx.x; i < cnt; i += TS) hs[f * B + i] = hr[i];
     }
     __syncthreads();
@@ -383,6 +447,55 @@ __global__ void k_cv_output_fan(CvConst c, CvState st, size_t V, int L, int ntil
         if (layout == FDSP_LAYOUT_PLANAR) out[vc[f] * fs + t0 + t] = y;
         else out[((size_t)c.gout[g][f] * T + t0 + t) * V + v] = y;
     }
+}
+
+// The head of a summing bank: one workgroup per (instance, output blockIdx.y, tile).  LDS stays at 2 * B floats, so the workgroup walks the
+// output's terms: stage the term's input samples and taps, barrier, every lane whose sample lies in [S, S + L) goes on with its ONE sum a in the
+// contract's order, barrier before the next term overwrites the staging.  No lane leaves before the last barrier: the lanes outside the
+// launch's samples stage and wait with the others and only skip the arithmetic and the store.  Consecutive terms of one input keep xs.
+__global__ void k_cv_output_sum(CvConst c, CvState st, size_t V, int L, int ntiles, float* __restrict__ out, size_t T, size_t t0, size_t fs, int layout) {
+    extern __shared__ float cv_lds[];
+    const int TS = blockDim.x, B = c.B;
+    const size_t v = blockIdx.x / ntiles;
+    const int tile = blockIdx.x % ntiles;
+    const int o = (int)blockIdx.y;
+    const u64 S = *st.samples;
+    const int M = st.dims[0];
+    const u64 n0 = (S / TS + tile) * TS;
+    const u64 j = n0 / B;
+    const int r0 = (int)(n0 % B);
+    const int cnt = r0 + TS;   // <= B
+    float* xs = cv_lds;
+    float* hs = cv_lds + B;
+    const u64 xm = (u64)(c.Rx - 1);
+    const u64 n = n0 + threadIdx.x;
+    const bool live = n >= S && n < S + (u64)L;
+    const int r = r0 + threadIdx.x;
+    const int imax = r < M - 1 ? r : M - 1;
+    const int tA = c.tfirst[o], tB = c.tfirst[o + 1];
+    float a = 0.0f;
+    for (int t = tA; t < tB; t++) {
+        const float* __restrict__ hr = c.h + ((c.rows == 1 ? 0 : v) * c.NT + t) * c.Hcap;
+        if (t == tA || c.tin[t] != c.tin[t - 1]) {
+            const float* __restrict__ xr = st.xin + (v * c.I + c.tin[t]) * (size_t)c.Rx;
+            for (int i = threadIdx.x; i < cnt; i += TS) xs[i] = xr[(j * B + i) & xm];
+        }
+        for (int i = threadIdx.x; i < cnt; i += TS) hs[i] = hr[i];
+        __syncthreads();
+        if (live) {
+            const float p0 = hs[0] * xs[r];
+            a = t == tA ? p0 : a + p0;
+            for (int i = 1; i <= imax; i++) a = a + hs[i] * xs[r - i];
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    const size_t vo = v * c.C + o;
+    const float pend = j == 0 ? 0.0f : st.pend[(vo * (c.KB + 1) + (size_t)(j % (u64)(c.KB + 1))) * (size_t)B + r];
+    const float y = pend + a;
+    const size_t t = (size_t)(n - S);
+    if (layout == FDSP_LAYOUT_PLANAR) out[vo * fs + t0 + t] = y;
+    else out[((size_t)o * T + t0 + t) * V + v] = y;
 }
 
 __global__ void k_cv_advance(CvState st, int L) { *st.samples += (u64)L; }
@@ -418,7 +531,7 @@ void launch_inverse(const CvConst& c, const CvState& st, size_t V, int L, int Fm
 void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float* in, float* out, size_t T, size_t fs, int layout, hipStream_t s) {
     const size_t Lmax = (size_t)c.KB * c.B, VC = V * (size_t)c.C, VI = V * (size_t)c.I;
     const int TS = c.B < 256 ? c.B : 256;
-    const int n2 = c.NG2, n1 = c.NG - c.NG2;   // routed banks: the fan groups of CV_FAN outputs and of one
+    const int n2 = c.NG2, n1 = c.NG - c.NG2;   // routed banks: the fan groups of CV_FAN outputs and of one (a summing bank: c.sum, per output)
     for (size_t t0 = 0; t0 < T; t0 += Lmax) {
         const int L = (int)(T - t0 < Lmax ? T - t0 : Lmax);
         const int Fmax = L / c.B + 1 < c.KB ? L / c.B + 1 : c.KB;   // blocks that can complete in (S, S + L]
@@ -426,7 +539,10 @@ void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float
         hipLaunchKernelGGL(k_cv_input, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, s, c, st, V, in, T, t0, L, fs, layout);
         forward<false>(c, st, (size_t)Fmax, VI, L, 0, s);
         const unsigned jg = (unsigned)((Fmax + CV_J - 1) / CV_J);
-        if (c.NG == 0) {
+        if (c.sum) {
+            const unsigned nx = (unsigned)((V * (size_t)(c.B + 1) + 255) / 256);
+            hipLaunchKernelGGL(k_cv_tail_sum, dim3(nx, jg, (unsigned)c.C), dim3(256), 0, s, c, st, V, L);
+        } else if (c.NG == 0) {
             const size_t nz = VC * (size_t)(c.B + 1);
             hipLaunchKernelGGL(k_cv_tail, dim3((unsigned)((nz + 255) / 256), jg), dim3(256), 0, s, c, st, V, L);
         } else {
@@ -444,7 +560,9 @@ void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float
             default: launch_inverse<12>(c, st, V, L, Fmax, s); break;
         }
         const int ntiles = L / TS + 2;   // tiles of TS samples that (S, S + L] can touch
-        if (c.NG == 0) {
+        if (c.sum) {
+            hipLaunchKernelGGL(k_cv_output_sum, dim3((unsigned)(V * ntiles), (unsigned)c.C), dim3(TS), 2 * c.B * sizeof(float), s, c, st, V, L, ntiles, out, T, t0, fs, layout);
+        } else if (c.NG == 0) {
             hipLaunchKernelGGL(k_cv_output, dim3((unsigned)(VC * ntiles)), dim3(TS), 2 * c.B * sizeof(float), s, c, st, V, L, ntiles, out, T, t0, fs, layout);
         } else {
             const unsigned nx = (unsigned)(V * ntiles);
@@ -458,7 +576,7 @@ void cv_launch_render(const CvConst& c, const CvState& st, size_t V, const float
 }
 
 void cv_launch_response(const CvConst& c, size_t row0, size_t nrows, hipStream_t s) {
-    forward<true>(c, CvState{}, (size_t)c.Pcap, nrows * c.C, 0, row0, s);
+    forward<true>(c, CvState{}, (size_t)c.Pcap, nrows * c.NT, 0, row0, s);
 }
 
 }  // namespace FD_CV_NS

@@ -32,6 +32,20 @@
 //     input samples are per (instance, input); G, h, Z, pend and y are per (instance, output).  No operation and no order changes, so a
 //     routed bank gives the bits of the C-channel bank fed copies of the input rows (tests/convolve_ref.py: render(x[:, source, :], h)),
 //     and the identity map (I = C, fdsp_convolve_create) is the bank of the bullets above.
+//   * Summing: a bank has I inputs, O outputs and NT terms, 1 <= I <= 8, 1 <= O <= 8, 1 <= NT <= 16.  Term t convolves input tin[t] with
+//     response row t and belongs to output tout[t]; tout is non-decreasing, every output has at least one term, every input feeds at
+//     least one term; one response length M for the whole bank (shorter rows zero-padded).  X_j and the input ring are per (instance,
+//     input), G and h per (row, term), Z, pend and y per (instance, output).
+//     Tail of output o at boundary j':  Z = (0, 0);  for each term t of o in increasing t:  for p = 0 .. min(P, j') - 1 in this order:
+//     Z[k] = Z[k] + X^{tin[t]}_{j'-1-p}[k] * G_{t,p}[k];  pend_{j'} = irfft_N(Z)[0 .. B-1].  ONE running sum across the terms, not one sum
+//     per term added afterwards; terms of blocks before the reset are skipped, as above.
+//     Head at n = jB + r:  for the first term t of o:  a = h_t[0] * x_t[n];  a = a + h_t[i] * x_t[n - i] for i = 1 .. min(r, M - 1)  (x_t
+//     the input tin[t]);  for every later term of o, in order:  a = a + h_t[0] * x_t[n], then the same i loop;  y[n] = pend_j[r] + a.
+//     An output with a single term has exactly the routed bank's bits, and a summing bank in which every output has one term IS the
+//     routed bank; every split into launches gives the same bits; FDSP_MODE_TICK == FDSP_MODE_PROCESS.
+//     This is the project's statement of Binop<FrameAdd> over convolvers (src/audionode.rs:903-955, `convolve(&w, 0) + convolve(&w, 1)`):
+//     the reference adds the two nodes' rounded outputs, this bank adds before the inverse transform, and the association of a `+` tree
+//     is flattened to term order.  Both stay inside the float64 bound below; the fft_convolver crate's bits are not pinned either way.
 //
 // Device layout.  Nothing is allocated after creation.  A launch is cut into chunks of at most Lmax = KB * B samples, and a chunk runs, on
 // the bank's stream (S = the count at its start, read from device memory, so a captured launch replays with the state moving on):
@@ -57,6 +71,17 @@
 //                       computes the F heads of its sample, each in the order above, from ONE read of every xs[r - i].
 // A group of one output runs the same two kernels at F = 1 (a permutation or the identity map is all such groups).  k_cv_inverse is the
 // plain bank's.  A plain bank (NG = 0) launches k_cv_tail / k_cv_output exactly as before.
+// A summing bank (fdsp_convolve_matrix_create; sum = 1) keeps xin and spec per (instance, input) as a routed bank does, h and G per (row,
+// TERM) -- [rows][NT][..]; NT is the response-row count of every bank, C for a plain or routed one -- and zbuf and pend per (instance,
+// output).  The term tables tin[16] and tfirst[9] (the first term of each output) travel in CvConst, never through device memory:
+//   k_cv_tail_sum    a lane owns bin k of one (instance, output) for CV_J boundaries; the CV_J sums stay in registers across the output's
+//                    terms, and each term runs k_cv_tail's whole step loop with its own response spectra, spectrum ring and window,
+//   k_cv_output_sum  one workgroup per (instance, output, tile); LDS stays at 2 * B floats (16 terms staged at once would be 512 KiB at
+//                    B = 4096), so the workgroup walks the terms: stage xs / hs, barrier, accumulate, barrier.  Every lane reaches every
+//                    barrier; consecutive terms of one input keep xs.
+// k_cv_input and k_cv_forward run over V x I rows, k_cv_inverse and k_cv_advance over V x O; KB keeps its formula with C = O.  Memory:
+// V * (I * (Rx*4 + R*(B + 1)*8) + O * (KB*(B + 1)*8 + (KB + 1)*B*4)) + rows*NT * ((Pcap + 1)*B*4 + Pcap*(B + 1)*8).  Not built: loading an
+// X once for several outputs that read the same inputs (the fan groups above; true stereo reads each twice), a register-blocked head.
 // M and P live on the device too (dims), so a replayed capture follows set_response.  KB = clamp(256 MiB / (V * C * (B + 1) * 8 B), 8, 64).
 // Memory: V*C * (Rx*4 + (R + KB)*(B + 1)*8 + (KB + 1)*B*4) + rows*C * ((Pcap + 1)*B*4 + Pcap*(B + 1)*8) bytes, rows = V with per-instance
 // responses, else 1.  Routed: V * (I * (Rx*4 + R*(B + 1)*8) + C * (KB*(B + 1)*8 + (KB + 1)*B*4)) plus the same response tables; KB keeps its
@@ -68,6 +93,11 @@
 // largest figure measured over 8 seeds): 4.1e-7 at B = 64, 9.5e-7 at B = 128 .. 4096.  The error follows sqrt(P) * log2(2B) * 2^-24 with a
 // constant of 0.33 at most; the largest figures belong to SHORT responses under a large capacity, where the transforms' noise of the order
 // log2(2B) * 2^-24 stands against a small sum |h|, not to the long heads or the many partitions.
+// Summing banks, max |y - y64| / (sum over the output's terms of sum |h_t| * max |x|) for K = 1, 2, 4, 8 terms per output
+// (tests/test_convolve_matrix_ref.py, the largest figure of 8 seeds): 1.64e-7, 1.31e-7, 1.24e-7, 1.15e-7 at B = 64 and 2.37e-7, 1.97e-7,
+// 1.69e-7, 1.30e-7 at B = 1024; asserted four times the largest, 6.6e-7 and 9.5e-7.  The reference's arithmetic (the plain bank's
+// outputs added in f32, left fold) measures 1.64e-7, 9.49e-8, 5.89e-8, 6.38e-8 and 2.37e-7, 1.49e-7, 9.48e-8, 7.75e-8: inside the same
+// bound, and below the statement's figures for K > 1.  The model sqrt(K P) * log2(2B) * 2^-24 holds with a constant of 0.39 at most.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -80,6 +110,7 @@ constexpr int CV_MAX_CH = 8;
 constexpr int CV_MIN_LOGB = 6, CV_MAX_LOGB = 12;   // B = 64 .. 4096
 constexpr int CV_J = 8;                            // block boundaries per lane of the tail kernel
 constexpr int CV_FAN = 2;                          // outputs of one input that a fan group renders together (routed banks)
+constexpr int CV_MAX_TERMS = 16;                   // terms (response rows) of a summing bank
 
 struct CvConst {
     int B, logB, C;
@@ -91,14 +122,21 @@ struct CvConst {
     int Rx;                   // input ring length (power of two >= Lmax + B)
     float invN;               // 1 / (2B) (exact)
     const float2* tw;         // [B] (cos, -sin)(2 pi j / 2B)
-    const float* h;           // [rows][C][Hcap]
-    const float2* G;          // [rows][C][Pcap][B + 1]
+    const float* h;           // [rows][NT][Hcap]
+    const float2* G;          // [rows][NT][Pcap][B + 1]
     // routing (the contract's last bullet); a plain bank has I = C, the identity map and NG = 0
     int I;                    // inputs, 1 .. C
     int source[CV_MAX_CH];    // output c reads input source[c]
     int NG, NG2;              // fan groups; the first NG2 hold CV_FAN outputs, the others one.  NG = 0: the plain kernel sequence
     int gsrc[CV_MAX_CH];      // a group's input
     int gout[CV_MAX_CH][CV_FAN];   // its outputs, increasing (a group of one repeats its output)
+    // response rows per bank row: h and G are [rows][NT][..] while zbuf and pend are [V][C][..].  A plain or routed bank has NT = C
+    int NT;
+    // summing (the contract's last bullet): sum = 1, C outputs, NT terms; term t convolves input tin[t] with response row t and the terms
+    // of output o are tfirst[o] .. tfirst[o + 1] - 1.  Passed by value like the fan groups, never read from device memory
+    int sum;
+    int tin[CV_MAX_TERMS];
+    int tfirst[CV_MAX_CH + 1];
 };
 
 struct CvState {

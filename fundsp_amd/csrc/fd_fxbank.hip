@@ -526,7 +526,7 @@ class ConvolveFx final : public FxBank {
     void render(const float* in, float* out, size_t T, size_t fstride, int layout, int, bool, hipStream_t s) override {
         (ftz_ ? cv_ftz::cv_launch_render : cv_ieee::cv_launch_render)(c_, st_, V_, in, out, T, fstride, layout, s);
     }
-    // the buffers, the twiddles, the rings defined, then the response [rows][C][len]
+    // the buffers, the twiddles, the rings defined, then the response [rows][NT][len] (NT = C but in a summing bank)
     int init(const float* response, size_t len, hipStream_t s) {
         const Bufs l = bufs();
         std::vector<float> tw(2 * (size_t)c_.B);
@@ -552,11 +552,11 @@ class ConvolveFx final : public FxBank {
     }
     // what re-initialising the node does: new taps (zero beyond len), their partitions' spectra, the lengths, and the history cleared
     int set_response(const float* h, size_t len, size_t first, size_t count, hipStream_t s) {
-        const size_t rowf = (size_t)c_.C * c_.Hcap;
+        const size_t rowf = (size_t)c_.NT * c_.Hcap;
         float* dst = (float*)c_.h + first * rowf;
         const int dims[2] = {(int)len, (int)((len + c_.B - 1) / c_.B)};
         hipError_t e = hipMemsetAsync(dst, 0, count * rowf * sizeof(float), s);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(dst, c_.Hcap * sizeof(float), h, len * sizeof(float), len * sizeof(float), count * c_.C, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(dst, c_.Hcap * sizeof(float), h, len * sizeof(float), len * sizeof(float), count * c_.NT, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(st_.dims, dims, sizeof(dims), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             (ftz_ ? cv_ftz::cv_launch_response : cv_ieee::cv_launch_response)(c_, first, count, s);
@@ -569,8 +569,8 @@ class ConvolveFx final : public FxBank {
         return FDSP_OK;
     }
     Bufs bufs() {   // the tables first
-        // the input ring and the spectrum ring per (instance, input), the rest per (instance, output)
-        const size_t B = (size_t)c_.B, B1 = B + 1, rc = (size_t)c_.rows * c_.C, vc = V_ * c_.C, vi = V_ * c_.I;
+        // the input ring and the spectrum ring per (instance, input), the response tables per (row, response row), the rest per (instance, output)
+        const size_t B = (size_t)c_.B, B1 = B + 1, rc = (size_t)c_.rows * c_.NT, vc = V_ * c_.C, vi = V_ * c_.I;
         return {{(void**)&c_.tw, B * sizeof(float2)}, {(void**)&c_.h, rc * c_.Hcap * sizeof(float)}, {(void**)&c_.G, rc * c_.Pcap * B1 * sizeof(float2)},
                 {(void**)&st_.xin, vi * (size_t)c_.Rx * sizeof(float)}, {(void**)&st_.spec, vi * (size_t)c_.R * B1 * sizeof(float2)},
                 {(void**)&st_.zbuf, vc * (size_t)c_.KB * B1 * sizeof(float2)}, {(void**)&st_.pend, vc * (size_t)(c_.KB + 1) * B * sizeof(float)},
@@ -725,13 +725,10 @@ int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** 
     return FDSP_OK;
 }
 
-int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, int inputs, const int* source, hipStream_t s, std::unique_ptr<FxBank>* out) {
-    const size_t V = instances;
-    CvConst c{};
+// the sizes that follow from the capacity, the outputs c.C and the instances; then the bank (c.C, c.NT, c.I and the routing or the terms set)
+static int cv_finish(CvConst c, size_t V, const fdsp_convolve_spec& sp, hipStream_t s, std::unique_ptr<FxBank>* out) {
     c.B = cv_block_length(sp.max_len);
     while ((1 << c.logB) < c.B) c.logB++;
-    c.C = sp.channels;
-    cv_set_routing(c, source ? inputs : sp.channels, source, source != nullptr);   // source NULL: fdsp_convolve_create, the plain kernel sequence
     c.rows = sp.per_instance ? (int)V : 1;
     c.Pcap = (int)((sp.max_len + c.B - 1) / c.B);
     c.Hcap = (size_t)(c.Pcap + 1) * c.B;
@@ -747,6 +744,26 @@ int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, int inputs, cons
     if (int rc = r->init(sp.response, sp.len, s)) return rc;
     *out = std::move(r);
     return FDSP_OK;
+}
+int fx_convolve(size_t instances, const fdsp_convolve_spec& sp, int inputs, const int* source, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    CvConst c{};
+    c.C = c.NT = sp.channels;
+    cv_set_routing(c, source ? inputs : sp.channels, source, source != nullptr);   // source NULL: fdsp_convolve_create, the plain kernel sequence
+    return cv_finish(c, instances, sp, s, out);
+}
+int fx_convolve_matrix(size_t instances, const fdsp_convolve_spec& sp, int inputs, int outputs, const int* term_input, const int* term_output, hipStream_t s,
+                       std::unique_ptr<FxBank>* out) {
+    CvConst c{};
+    c.C = outputs;
+    c.NT = sp.channels;
+    c.I = inputs;
+    c.sum = 1;
+    for (int t = 0; t < c.NT; t++) {
+        c.tin[t] = term_input[t];
+        c.tfirst[term_output[t] + 1] = t + 1;   // term_output is non-decreasing and names every output: the last term of o ends at t + 1
+    }
+    for (int o = outputs + 1; o <= CV_MAX_CH; o++) c.tfirst[o] = c.NT;
+    return cv_finish(c, instances, sp, s, out);
 }
 int fx_convolve_check(FxBank* fx, size_t len, size_t first, size_t count) {
     auto* r = dynamic_cast<ConvolveFx*>(fx);

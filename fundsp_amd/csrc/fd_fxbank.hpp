@@ -74,6 +74,10 @@ int fx_resynth_table(FxBank* fx, bool gain, size_t first, size_t count, float** 
 // source NULL: the plain bank of fdsp_convolve_create; else the routed bank of fdsp_convolve_routed_create (`inputs` and the `channels`
 // entries of `source` checked by the caller; read during the call only)
 int fx_convolve(size_t instances, const fdsp_convolve_spec& spec, int inputs, const int* source, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// the summing bank of fdsp_convolve_matrix_create: spec.channels terms (response rows), term t reading input term_input[t] into output
+// term_output[t] (both tables and the counts checked by the caller; read during the call only)
+int fx_convolve_matrix(size_t instances, const fdsp_convolve_spec& spec, int inputs, int outputs, const int* term_input, const int* term_output,
+                       hipStream_t stream, std::unique_ptr<FxBank>* out);
 // fdsp_convolve_set_response: _check refuses what is not a convolver bank (`fx` may be NULL), a length beyond the capacity and rows out of
 // range before anything is touched; _response uploads [count][channels][len] for rows first .. first+count-1, transforms the partitions on
 // `stream` and clears the history (the caller waits for the stream: the host array is borrowed)

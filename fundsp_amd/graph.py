@@ -83,7 +83,12 @@ class Graph:
 
     def __mul__(self, o): return self._binop(o, "OpMul") if isinstance(o, Graph) else self._unop("UMulScalar", o)
     def __rmul__(self, o): return self._unop("UMulScalar", o)
-    def __add__(self, o): return self._binop(o, "OpAdd") if isinstance(o, Graph) else self._unop("UAddScalar", o)
+    def __add__(self, o):
+        if not isinstance(o, Graph):
+            return self._unop("UAddScalar", o)
+        g = self._binop(o, "OpAdd")
+        g.add_parts = (self, o)   # convolve_matrix_plan: a sum of convolvers is one bank that adds several inputs into one output
+        return g
     def __radd__(self, o): return self._unop("UAddScalar", o)
     def __sub__(self, o): return self._binop(o, "OpSub") if isinstance(o, Graph) else self._unop("UAddScalar", -np.asarray(o, dtype=np.float32))
     def __rsub__(self, o): return self._unop("UNegAddScalar", o)
@@ -1049,3 +1054,39 @@ def convolve_route_plan(graph):
     for c, r in enumerate(rs):
         h[c, :len(r)] = r
     return h, source, inputs
+
+
+def convolve_matrix_plan(graph):
+    """(h [terms, len], term_input, term_output, inputs, outputs) when `graph` is a tree of stacks `|`, branches `^` and sums `+` over
+    convolve(..) leaves -- term t convolves input term_input[t] with h[t] and is added into output term_output[t]
+    (Bank.convolve(.., source=term_input, target=term_output), Bank.convolve_tree) --, else None.  A leaf is one input into one output;
+    `a | b` puts b's inputs behind a's and b's outputs behind a's; `a ^ b` gives both the same inputs; `a + b` (Binop<FrameAdd>) puts b's
+    inputs behind a's and appends b's terms to a's, output by output.  The terms are then stably ordered by output, so the association of
+    a `+` tree is flattened to term order.  Shorter responses are zero-padded to the longest."""
+    def walk(g):   # ([(response, input, output)], inputs, outputs)
+        if getattr(g, "convolve_response", None) is not None:
+            return [(g.convolve_response, 0, 0)], 1, 1
+        st, br, ad = getattr(g, "stack_parts", None), getattr(g, "branch_parts", None), getattr(g, "add_parts", None)
+        if st is None and br is None and ad is None:
+            return None
+        a, b = (walk(p) for p in (st or br or ad))
+        if a is None or b is None:
+            return None
+        if st is not None:
+            return a[0] + [(r, i + a[1], o + a[2]) for r, i, o in b[0]], a[1] + b[1], a[2] + b[2]
+        if br is not None:   # (Graph.__xor__ has checked the arities)
+            return (a[0] + [(r, i, o + a[2]) for r, i, o in b[0]], a[1], a[2] + b[2]) if a[1] == b[1] else None
+        return (a[0] + [(r, i + a[1], o) for r, i, o in b[0]], a[1] + b[1], a[2]) if a[2] == b[2] else None   # (Graph._binop likewise)
+
+    plan = walk(graph)
+    if plan is None:
+        return None
+    terms, inputs, outputs = plan
+    for n, most, what in ((inputs, 8, "inputs"), (outputs, 8, "outputs"), (len(terms), 16, "terms")):
+        if n > most:
+            raise ValueError(f"convolve: {n} {what} in one tree of stacks, branches and sums (a summing bank takes 1 .. {most} {what})")
+    terms = sorted(terms, key=lambda t: t[2])   # (stable)
+    h = np.zeros((len(terms), max(len(t[0]) for t in terms)), dtype=np.float32)
+    for c, t in enumerate(terms):
+        h[c, :len(t[0])] = t[0]
+    return h, [t[1] for t in terms], [t[2] for t in terms], inputs, outputs

@@ -624,7 +624,17 @@ class Bank {
         b.kind_ = "convolve";
         return b;
     }
-    // Convolver::set_response for rows first .. first+count-1: h_response [count][channels][len]; the bank's history is cleared
+    // several inputs convolved and added into one output, `convolve(&w, 0) + convolve(&w, 1)` (fdsp_convolve_matrix_create): spec.channels
+    // terms, term t convolving input term_input[t] with response row t into output term_output[t] (non-decreasing); the terms of an output
+    // are summed before its one inverse transform.  True stereo `(ll + rl) ^ (lr + rr)`: term_input {0, 1, 0, 1}, term_output {0, 0, 1, 1}
+    static Bank convolve_matrix(size_t instances, const fdsp_convolve_spec& spec, int inputs, int outputs, const int* term_input, const int* term_output) {
+        Bank b;
+        check(fdsp_convolve_matrix_create(instances, &spec, inputs, outputs, term_input, term_output, &b.h_));
+        b.kind_ = "convolve";
+        return b;
+    }
+    // Convolver::set_response for rows first .. first+count-1: h_response [count][channels][len] (channels = the outputs, or the terms of a
+    // summing bank); the bank's history is cleared
     void set_response(const float* h_response, size_t len, size_t first = 0, size_t count = 1) {
         check(fdsp_convolve_set_response(h_, h_response, len, first, count));
     }

@@ -132,6 +132,7 @@ pub mod ffi {
         pub fn fdsp_resynth_set_gain(bank: *mut FdspBank, gain: *const f32, first: usize, count: usize) -> c_int;
         pub fn fdsp_convolve_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_convolve_routed_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, inputs: c_int, source: *const c_int, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_convolve_matrix_create_on(device: c_int, instances: usize, spec: *const FdspConvolveSpec, inputs: c_int, outputs: c_int, term_input: *const c_int, term_output: *const c_int, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_convolve_set_response(bank: *mut FdspBank, response: *const f32, len: usize, first: usize, count: usize) -> c_int;
         pub fn fdsp_bank_destroy(bank: *mut FdspBank);
         pub fn fdsp_bank_clone(bank: *const FdspBank, out: *mut *mut FdspBank) -> c_int; // Clone: slots, rings, sample rate, options, events
@@ -221,6 +222,8 @@ pub struct HipBank<NI: Size<f32>, NO: Size<f32>> {
     /// `tick` / `process` are infallible in FunDSP.  A failed launch (lost device, wrong arity) zeroes the output and is
     /// recorded here -- in release builds too -- for the host to poll with `take_error()`.
     last_error: Option<String>,
+    /// terms of a summing convolver bank ([`Self::convolve_matrix`]: its response rows are per term, not per output), else 0
+    convolve_terms: usize,
     _marker: PhantomData<(NI, NO)>,
 }
 
@@ -241,7 +244,7 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
             return Err(format!("arity mismatch: the bank has {}x{} inputs and {}x{} outputs", voices, i, voices, o));
         }
         let device = unsafe { fdsp_bank_device(bank) };
-        Ok(Self { bank, kind, voices, ring_frames, device, last_error: None, _marker: PhantomData })
+        Ok(Self { bank, kind, voices, ring_frames, device, last_error: None, convolve_terms: 0, _marker: PhantomData })
     }
 
     /// The same without the typenum arity check: for banks far beyond the channel counts `Size` is meant for (65 536 voices),
@@ -251,7 +254,7 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_bank_create_on(device as c_int, kind.as_ptr(), voices, ring_frames, &mut bank) })?;
         let device = unsafe { fdsp_bank_device(bank) };
-        Ok(Self { bank, kind, voices, ring_frames, device, last_error: None, _marker: PhantomData })
+        Ok(Self { bank, kind, voices, ring_frames, device, last_error: None, convolve_terms: 0, _marker: PhantomData })
     }
 
     /// `instances` x `reverb_stereo(room_size, time, damping)` (src/prelude.rs:1732-1762) through the dedicated lane-per-frame FDN kernel
@@ -482,9 +485,39 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         Self::adopt(bank, "convolve", instances)
     }
 
-    /// Convolver::set_response for rows `first` .. : `response` holds [count][channels][len]; the history of the whole bank is cleared
+    /// Several inputs convolved and added into one output, `convolve(&w, 0) + convolve(&w, 1)` (fdsp_convolve_matrix_create): a bank of
+    /// `inputs` inputs, `outputs` outputs and `term_input.len()` terms (1 .. 16); term t convolves input `term_input[t]` with response row
+    /// t into output `term_output[t]` (non-decreasing).  `response` as for [`Self::convolve`] with channels = terms.  The terms of an output
+    /// are summed before its one inverse transform; an output of one term has the bits of [`Self::convolve_routed`].  A true-stereo
+    /// response `(ll + rl) ^ (lr + rr)` is term_input = [0, 1, 0, 1], term_output = [0, 0, 1, 1].  Source only: no Rust toolchain has built it.
+    pub fn convolve_matrix(instances: usize, inputs: usize, outputs: usize, term_input: &[i32], term_output: &[i32], response: &[f32], len: usize,
+                           max_len: usize, per_instance: bool, flush_denormals: bool, device: i32) -> Result<Self, String> {
+        let rows = if per_instance { instances } else { 1 };
+        let terms = term_input.len();
+        if terms < 1 || terms > 16 || term_output.len() != terms || len < 1 || response.len() != rows * terms * len {
+            return Err("HipBank::convolve_matrix: one input and one output index per term, 1 .. 16 terms; response needs rows x terms x len taps (rows = instances with per_instance)".into());
+        }
+        let spec = FdspConvolveSpec {
+            channels: terms as c_int,
+            max_len,
+            len,
+            per_instance: per_instance as c_int,
+            flush_denormals: flush_denormals as c_int,
+            response: response.as_ptr(),
+        };
+        let tin: Vec<c_int> = term_input.iter().map(|&i| i as c_int).collect();
+        let tout: Vec<c_int> = term_output.iter().map(|&i| i as c_int).collect();
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_convolve_matrix_create_on(device as c_int, instances, &spec, inputs as c_int, outputs as c_int, tin.as_ptr(), tout.as_ptr(), &mut bank) })?;
+        let mut b = Self::adopt(bank, "convolve", instances)?;
+        b.convolve_terms = terms;
+        Ok(b)
+    }
+
+    /// Convolver::set_response for rows `first` .. : `response` holds [count][channels][len] (channels = the outputs, or the terms of a
+    /// summing bank); the history of the whole bank is cleared
     pub fn set_response(&mut self, response: &[f32], len: usize, first: usize, count: usize) -> Result<(), String> {
-        let channels = unsafe { fdsp_bank_outputs(self.bank) as usize };
+        let channels = if self.convolve_terms > 0 { self.convolve_terms } else { unsafe { fdsp_bank_outputs(self.bank) as usize } };
         if response.len() != count * channels * len {
             return Err("HipBank::set_response: response needs count x channels x len taps".into());
         }
@@ -493,7 +526,7 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
 
     fn adopt(bank: *mut FdspBank, kind: &str, voices: usize) -> Result<Self, String> {
         let device = unsafe { fdsp_bank_device(bank) };
-        Ok(Self { bank, kind: CString::new(kind).unwrap(), voices, ring_frames: 0, device, last_error: None, _marker: PhantomData })
+        Ok(Self { bank, kind: CString::new(kind).unwrap(), voices, ring_frames: 0, device, last_error: None, convolve_terms: 0, _marker: PhantomData })
     }
 
     fn arity_ok(&self) -> bool {
@@ -746,7 +779,7 @@ impl<NI: Size<f32>, NO: Size<f32>> Clone for HipBank<NI, NO> {
         let rc = unsafe { fdsp_bank_clone(self.bank, &mut bank) };
         assert!(rc == FDSP_OK && !bank.is_null(), "fdsp_bank_clone: {}", last_error());
         Self { bank, kind: self.kind.clone(), voices: self.voices, ring_frames: self.ring_frames, device: self.device,
-               last_error: None, _marker: PhantomData }
+               last_error: None, convolve_terms: self.convolve_terms, _marker: PhantomData }
     }
 }
 
