@@ -474,10 +474,9 @@ hipError_t sync_bank_stream(const fdsp_bank* b) {
     if (e == hipSuccess) b->async_param_pending = false;
     return e;
 }
-int order_after_bank_stream(const fdsp_bank* b, hipStream_t s) {
+int order_after_bank_stream(const fdsp_bank* b, hipStream_t s, bool capturing) {
     if (s == b->stream) return FDSP_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+    if (capturing) {
         if (b->async_param_pending)
             return fail(FDSP_EDEVICE, "a device-side fdsp_bank_set_param_all is still queued on the bank's stream: call fdsp_bank_synchronize before capturing "
                                       "(the capture is refused rather than left to race with the fill)");
@@ -703,14 +702,23 @@ void launch_mix_tree(const float* part, float* mix, size_t R, size_t G, hipStrea
     else hipLaunchKernelGGL((k_mix_tree<16>), dim3((unsigned)((R + 15) / 16)), dim3(256), 0, s, part, mix, R, G, slice(16));
 }
 
+// k_group_partials over [rows][V]: `vec4` (the caller's word that every row is 16-byte aligned) picks the variant with 16-byte loads;
+// `map` (PAN = false only) sends the partials to the columns of a longer launch's buffer
+template <bool PAN>
+void launch_group_partials(const float* x, const float* wl, const float* wr, float* part, size_t rows, size_t V, bool vec4, hipStream_t s,
+                           const PartMap* map = nullptr) {
+    const dim3 grid((unsigned)((V + 63) / 64), (unsigned)((rows + 255) / 256));
+    auto go = [&](auto kernel, PartMap m) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, x, wl, wr, part, rows, V, m); };
+    if constexpr (!PAN)
+        if (map) return vec4 ? go(k_group_partials<false, true, true>, *map) : go(k_group_partials<false, false, true>, *map);
+    return vec4 ? go(k_group_partials<PAN, true>, PartMap{}) : go(k_group_partials<PAN, false>, PartMap{});
+}
+
 // the launch pair behind fdsp_sum_voices / fdsp_mix_stereo: group partials of a voice-out buffer, then the tree
 template <bool PAN>
 hipError_t launch_mix_rows(const float* x, const float* wl, const float* wr, float* part, float* mix, size_t rows, size_t V, hipStream_t s) {
     const size_t G = (V + 63) / 64, R = PAN ? 2 * rows : rows;
-    if (V % 4 == 0 && ((uintptr_t)x & 15) == 0)
-        hipLaunchKernelGGL((k_group_partials<PAN, true>), dim3((unsigned)G, (unsigned)((rows + 255) / 256)), dim3(256), 0, s, x, wl, wr, part, rows, V);
-    else
-        hipLaunchKernelGGL((k_group_partials<PAN, false>), dim3((unsigned)G, (unsigned)((rows + 255) / 256)), dim3(256), 0, s, x, wl, wr, part, rows, V);
+    launch_group_partials<PAN>(x, wl, wr, part, rows, V, V % 4 == 0 && ((uintptr_t)x & 15) == 0, s);
     launch_mix_tree(part, mix, R, G, s);
     return hipGetLastError();
 }
@@ -786,6 +794,83 @@ void resolve_opts(const fdsp_bank* b) {
 }
 bool timing_on(const fdsp_bank* b) { return (b->opt_timing >= 0 ? b->opt_timing : fd::g_timing.load(std::memory_order_relaxed)) != 0; }
 
+// ---- the launch scope: what every render entry point does around its kernels, written once ------------------------------------------
+//     Launch launch(b, stream);   the stream (the caller's, or the bank's own) and whether it is being captured
+//     ... grow what the launch needs: never while launch.capturing ...
+//     launch.begin();             ordering, ring check, the start event, the launch options
+//     ... kernels on launch.s ...
+//     launch.finish();            last_kernel, the launch error, the completion event, timed / ext_pending
+// A call that returns between begin() and finish() launched nothing that e0 brackets: the scope leaves the bank untimed
+// (fdsp_bank_last_kernel_ms fails) and changes nothing else.
+struct Launch {
+    fdsp_bank* const b;
+    const hipStream_t s;
+    bool capturing = false;  // a captured launch waits for nothing on the host and leaves the bank's events and flags alone
+    bool timing;             // the per-launch event pair ("timing"); off: the completion event only where ordering needs it (a caller's stream)
+    bool open = false;       // between begin() and finish()
+    // timed = false (fdsp_bank_reverb_fitness: several launches with an event pair of their own): no event pair, whatever "timing" says
+    Launch(fdsp_bank* bank, void* stream, bool timed = true) : b(bank), s(stream ? (hipStream_t)stream : bank->stream), timing(timed && timing_on(bank)) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (s != b->stream) capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    }
+    Launch(const Launch&) = delete;
+    ~Launch() {
+        if (open) b->timed = false;
+    }
+    int begin() {
+        if (int rc = order_after_bank_stream(b, s, capturing)) return rc;  // behind pending parameter updates
+        if (int rc = check_ring_need(b, capturing)) return rc;
+        // a previous render may still be running on ANOTHER stream (caller streams differ from call to call, or the last one
+        // ran on a caller stream and this one runs on the bank's): it reads and writes the same voice state, so order behind it
+        if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
+        if (timing && !capturing) HIPCHK(hipEventRecord(b->e0, s));
+        resolve_opts(b);
+        open = true;
+        return FDSP_OK;
+    }
+    int finish() {
+        b->last_kernel = fd::tl_opts.last_kernel;
+        HIPCHK(hipGetLastError());
+        open = false;
+        if (!capturing) {
+            if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
+            b->timed = timing;
+            b->ext_pending = s != b->stream;
+        }
+        return FDSP_OK;
+    }
+};
+
+// host-side wait for every render of the bank, on its own stream or a caller's: its buffers may be freed afterwards
+int await_renders(const fdsp_bank* b) {
+    HIPCHK(sync_bank_stream(b));
+    if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));
+    return FDSP_OK;
+}
+// grow-only device scratch of exactly `floats` floats (mix_part, score_scratch): the old buffer goes once no render can still use it
+int scratch_reserve(fdsp_bank* b, float** p, size_t* have, size_t floats, const char* what) {
+    if (floats <= *have) return FDSP_OK;
+    if (int rc = await_renders(b)) return rc;
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    hipError_t e = hipMalloc((void**)p, floats * sizeof(float));
+    if (e != hipSuccess) return fail(FDSP_ENOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
+    *have = floats;
+    return FDSP_OK;
+}
+int mix_reserve(fdsp_bank* b, size_t floats) { return scratch_reserve(b, &b->mix_part, &b->mix_part_n, floats, "partial mixes"); }
+int score_scratch_reserve(fdsp_bank* b, size_t floats) { return scratch_reserve(b, &b->score_scratch, &b->score_scratch_n, floats, "score scratch"); }
+
+// the sequencer clock after `frames` more frames, advanced exactly as the reference does: one f64 addition per block / per sample
+double advance_clock(double t, size_t frames, double sd, int mode) {
+    if (mode == FDSP_MODE_PROCESS)
+        for (size_t t0 = 0; t0 < frames; t0 += 64) t += sd * (double)(frames - t0 < 64 ? frames - t0 : 64);
+    else
+        for (size_t i = 0; i < frames; i++) t += sd;
+    return t;
+}
+
 // ---- scores with one lane per note: what the bank owns for them ----------------------------------------------------------------
 bool score_notes_kind(const fdsp_bank* b) { return !b->fx && b->ops && b->ops->render_score_notes; }
 // the staging image and its flags; never called by a captured launch
@@ -814,18 +899,6 @@ size_t score_chunk_frames(const fdsp_bank* b, size_t frames) {
     }
     const size_t whole = (frames + 63) & ~(size_t)63;
     return chunk < whole ? chunk : whole;
-}
-int score_scratch_reserve(fdsp_bank* b, size_t floats) {
-    if (floats <= b->score_scratch_n) return FDSP_OK;
-    HIPCHK(sync_bank_stream(b));
-    if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));  // a render on a caller's stream may still use the old buffer
-    if (b->score_scratch) hipFree(b->score_scratch);
-    b->score_scratch = nullptr;
-    b->score_scratch_n = 0;
-    hipError_t e = hipMalloc((void**)&b->score_scratch, floats * sizeof(float));
-    if (e != hipSuccess) return fail(FDSP_ENOMEM, std::string("hipMalloc(score scratch): ") + hipGetErrorString(e));
-    b->score_scratch_n = floats;
-    return FDSP_OK;
 }
 }  // namespace
 
@@ -1723,35 +1796,16 @@ int fdsp_bank_process(fdsp_bank* b, size_t frames, const float* d_in, float* d_o
     if (layout != FDSP_LAYOUT_VOICE_MINOR && layout != FDSP_LAYOUT_PLANAR) return fail(FDSP_EINVAL, "bad layout");
     if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
     if (layout == FDSP_LAYOUT_PLANAR && frame_stride < frames) return fail(FDSP_EINVAL, "frame_stride < frames");
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    if (int rc = order_after_bank_stream(b, s)) return rc;  // order after pending parameter updates
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s != b->stream) hipStreamIsCapturing(s, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;  // a captured launch leaves the timing events alone
-    // a previous render may still be running on ANOTHER stream (caller streams differ from call to call, or the last one
-    // ran on a caller stream and this one runs on the bank's): it reads and writes the same voice state, so order behind it
-    if (int rc = check_ring_need(b, capturing)) return rc;
-    if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
-    // the per-launch event pair is optional ("timing" = 0): a real-time host that renders one 64-frame block per call
-    // saves two event records per launch; the completion event is then recorded only where ordering needs it (a
-    // caller's stream)
-    const bool timing = timing_on(b);
-    if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
-    resolve_opts(b);
+    Launch launch(b, stream);
+    if (int rc = launch.begin()) return rc;
+    hipStream_t s = launch.s;
     if (b->fx)
-        b->fx->render(d_in, d_out, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, capturing, s);
+        b->fx->render(d_in, d_out, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, launch.capturing, s);
     else if (b->math == FDSP_MATH_FAST && b->ops->render_fast)
         b->ops->render_fast(b->slots, b->stride, b->V, d_in, d_out, frames, frame_stride, layout, mode, b->aux, b->ring, b->ring_cap, s);
     else
         b->ops->render(b->slots, b->stride, b->V, d_in, d_out, frames, frame_stride, layout, mode, b->aux, b->ring, b->ring_cap, s);
-    b->last_kernel = fd::tl_opts.last_kernel;
-    HIPCHK(hipGetLastError());
-    if (!capturing) {
-        if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
-        b->timed = timing;
-        b->ext_pending = s != b->stream;
-    }
-    return FDSP_OK;
+    return launch.finish();
 }
 
 // ---- reverb_fitness per instance (fd_fitness.hpp) -----------------------------------------------------------------------------------------
@@ -1796,30 +1850,23 @@ int fdsp_bank_reverb_fitness(fdsp_bank* b, float* d_fitness, float* d_terms, voi
     if (int rc = fitness_bank(b, "fdsp_bank_reverb_fitness")) return rc;
     if (!d_fitness) return fail(FDSP_EINVAL, "fdsp_bank_reverb_fitness: d_fitness is NULL");
     DeviceGuard guard(b->device);
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s != b->stream) hipStreamIsCapturing(s, &cap);
-    if (cap != hipStreamCaptureStatusNone)
+    Launch launch(b, stream, false);  // untimed: fit_e0 / fit_e1 bracket the score kernel, "fitness_score_us" reads them
+    if (launch.capturing)
         return fail(FDSP_EINVAL, "fdsp_bank_reverb_fitness during a stream capture: the call resets the bank and may allocate its scratch (capture of a fitness call is out of scope)");
-    if (int rc = order_after_bank_stream(b, s)) return rc;
     if (int rc = fitness_reserve(b)) return rc;
-    if (b->ext_pending) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
-    resolve_opts(b);
+    if (int rc = launch.begin()) return rc;
+    hipStream_t s = launch.s;
     const size_t half = b->V * 2 * (size_t)fd::FIT_N;
     float *imp = b->fit_scratch, *resp = b->fit_scratch + half;
     HIPCHK(b->fx->reset(s));
     fd::fit_launch_impulse(imp, b->V * 2, s);
     b->fx->render(imp, resp, (size_t)fd::FIT_N, (size_t)fd::FIT_N, FDSP_LAYOUT_PLANAR, 0, false, s);   // PROCESS mode, planar
-    b->last_kernel = fd::tl_opts.last_kernel;
     HIPCHK(hipEventRecord(b->fit_e0, s));
     fd::fit_launch_score(resp, b->fit_tables, b->V, d_terms ? d_terms : imp, d_fitness, s);   // (the impulse has been read: its head takes the terms)
     HIPCHK(hipEventRecord(b->fit_e1, s));
     HIPCHK(hipGetLastError());
     HIPCHK(b->fx->reset(s));   // the bank is left as constructed
-    if (s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
-    b->timed = false;
-    b->ext_pending = s != b->stream;
-    return FDSP_OK;
+    return launch.finish();
 }
 
 // ---- render + mix-down in one launch -------------------------------------------------------------------------------
@@ -1834,18 +1881,6 @@ int ensure_panw(fdsp_bank* b) {
                        b->panw + b->stride, b->stride, b->V);
     HIPCHK(hipGetLastError());
     HIPCHK(sync_bank_stream(b));
-    return FDSP_OK;
-}
-int mix_reserve(fdsp_bank* b, size_t floats) {
-    if (floats <= b->mix_part_n) return FDSP_OK;
-    HIPCHK(sync_bank_stream(b));
-    if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));  // a render on a caller's stream may still write the old buffer
-    if (b->mix_part) hipFree(b->mix_part);
-    b->mix_part = nullptr;
-    b->mix_part_n = 0;
-    hipError_t e = hipMalloc((void**)&b->mix_part, floats * sizeof(float));
-    if (e != hipSuccess) return fail(FDSP_ENOMEM, std::string("hipMalloc(partial mixes): ") + hipGetErrorString(e));
-    b->mix_part_n = floats;
     return FDSP_OK;
 }
 }  // namespace
@@ -1898,37 +1933,22 @@ int fdsp_bank_mix_reserve(fdsp_bank* b, size_t frames) {
 namespace {
 // fdsp_bank_process_mix / _planar of an effect bank: the arguments are checked; render into the scratch, partials, tree
 int fx_process_mix(fdsp_bank* b, size_t frames, const float* d_in, size_t frame_stride, int layout, float* d_mix, int mix, int mode, void* stream) {
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s != b->stream) hipStreamIsCapturing(s, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    Launch launch(b, stream);
     const size_t nm = (size_t)mix_channels(b, mix), groups = (b->V + 63) / 64, R = nm * frames;
-    resolve_opts(b);
+    resolve_opts(b);  // mix_reserved reads "fx_mix_chunk_frames"
     if (groups * R > b->mix_part_n || !b->fx->mix_reserved(frames) || (mix == FDSP_MIX_PAN && !b->panw)) {
-        if (capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_mix during a stream capture: call fdsp_bank_mix_reserve (and fdsp_bank_set_pan) before capturing");
+        if (launch.capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_mix during a stream capture: call fdsp_bank_mix_reserve (and fdsp_bank_set_pan) before capturing");
         if (int rc = mix_reserve(b, groups * R)) return rc;
         if (!b->fx->mix_reserved(frames)) {
-            HIPCHK(sync_bank_stream(b));
-            if (b->ext_pending) HIPCHK(hipEventSynchronize(b->e1));  // a mix launch on a caller's stream may still use the old scratch
+            if (int rc = await_renders(b)) return rc;  // a mix launch on a caller's stream may still use the old scratch
             if (int rc = b->fx->mix_reserve(frames)) return rc;
         }
         if (mix == FDSP_MIX_PAN) if (int rc = ensure_panw(b)) return rc;
     }
-    if (int rc = order_after_bank_stream(b, s)) return rc;
-    if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
-    const bool timing = timing_on(b);
-    if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
-    resolve_opts(b);
-    b->fx->render_mix(d_in, b->mix_part, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, mix == FDSP_MIX_PAN ? b->panw : nullptr, b->stride, s);
-    b->last_kernel = fd::tl_opts.last_kernel;
-    launch_mix_tree(b->mix_part, d_mix, R, groups, s);
-    HIPCHK(hipGetLastError());
-    if (!capturing) {
-        if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
-        b->timed = timing;
-        b->ext_pending = s != b->stream;
-    }
-    return FDSP_OK;
+    if (int rc = launch.begin()) return rc;
+    b->fx->render_mix(d_in, b->mix_part, frames, frame_stride, layout, mode == FDSP_MODE_TICK ? 1 : 0, mix == FDSP_MIX_PAN ? b->panw : nullptr, b->stride, launch.s);
+    launch_mix_tree(b->mix_part, d_mix, R, groups, launch.s);
+    return launch.finish();
 }
 // the argument checks the two mix entry points share
 int check_mix_args(const fdsp_bank* b, const float* d_in, const float* d_mix, int mix, int mode) {
@@ -1960,39 +1980,21 @@ int fdsp_bank_process_mix(fdsp_bank* b, size_t frames, const float* d_in, float*
     if (int rc = check_mix_args(b, d_in, d_mix, mix, mode)) return rc;
     if (b->fx) return fx_process_mix(b, frames, d_in, 0, FDSP_LAYOUT_VOICE_MINOR, d_mix, mix, mode, stream);
     const bool fast = b->math == FDSP_MATH_FAST && b->ops->render_mix_fast;
-    const auto& launch = fast ? b->ops->render_mix_fast : b->ops->render_mix;
-    if (!launch) return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' was built without a fused mix-down kernel: render voice-out and call fdsp_sum_voices / fdsp_mix_stereo");
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s != b->stream) hipStreamIsCapturing(s, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const auto& render = fast ? b->ops->render_mix_fast : b->ops->render_mix;
+    if (!render) return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' was built without a fused mix-down kernel: render voice-out and call fdsp_sum_voices / fdsp_mix_stereo");
+    Launch launch(b, stream);
     const size_t nm = (size_t)mix_channels(b, mix), groups = b->stride / 64, R = nm * frames;
     if (groups * R > b->mix_part_n || (mix == FDSP_MIX_PAN && !b->panw)) {
-        if (capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_mix during a stream capture: call fdsp_bank_mix_reserve (and fdsp_bank_set_pan) before capturing");
+        if (launch.capturing) return fail(FDSP_EINVAL, "fdsp_bank_process_mix during a stream capture: call fdsp_bank_mix_reserve (and fdsp_bank_set_pan) before capturing");
         if (int rc = mix_reserve(b, groups * R)) return rc;
         if (mix == FDSP_MIX_PAN) if (int rc = ensure_panw(b)) return rc;
     }
-    if (int rc = order_after_bank_stream(b, s)) return rc;
-    if (int rc = check_ring_need(b, capturing)) return rc;
-    if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
-    const bool timing = timing_on(b);
-    if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
-    resolve_opts(b);
-    const bool done = launch(b->slots, b->stride, b->V, d_in, b->mix_part, frames, mix, mode, b->aux, b->ring, b->ring_cap, b->panw, s);
-    if (!done) {
-        b->timed = false;  // e0 was re-recorded for a launch that did not happen: no event pair to read
+    if (int rc = launch.begin()) return rc;
+    if (!render(b->slots, b->stride, b->V, d_in, b->mix_part, frames, mix, mode, b->aux, b->ring, b->ring_cap, b->panw, launch.s))
         return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "': no fused mix-down kernel for this graph shape (single-stage graphs without inputs, 3+ outputs with FDSP_MIX_PAN)");
-    }
-    b->last_kernel = fd::tl_opts.last_kernel;
     // the groups' partials -> d_mix, aligned binary tree (k_mix_tree); the time it takes is part of the render's event pair
-    launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, s);
-    HIPCHK(hipGetLastError());
-    if (!capturing) {
-        if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
-        b->timed = timing;
-        b->ext_pending = s != b->stream;
-    }
-    return FDSP_OK;
+    launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, launch.s);
+    return launch.finish();
 }
 
 int fdsp_bank_set_ring(fdsp_bank* b, int ring_index, const float* data, size_t frames, size_t first, size_t count) {
@@ -2195,27 +2197,19 @@ int fdsp_bank_events_rewind(fdsp_bank* b, double time) {
 double fdsp_bank_events_time(const fdsp_bank* b) { return b ? b->seq_time : 0.0; }
 
 namespace {
-// fdsp_bank_process_events (d_mix == nullptr: every event's faded samples to d_out) and fdsp_bank_process_events_mix (d_out == nullptr: the
-// Sequencer's output, the sum of the events, to d_mix [outputs][frames]) share everything but the launch
-int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, float* d_mix, int mode, void* stream) {
-    if (!b) return fail(FDSP_EINVAL, "bank is NULL");
-    if (int rc = render_only(b)) return rc;
-    DeviceGuard guard(b->device);
-    if (frames == 0) return FDSP_OK;
-    const bool mixing = d_out == nullptr;
-    const bool scored = b->score_mem != nullptr;  // a score plays instead of events
+// what a scheduler launch is: `mixing` (d_out == nullptr), `scored` (a score plays instead of events), `notes` (one lane per note: asked
+// for, and the kind can -- otherwise today's kernel, silently; mixed: through a voice-out scratch of `chunk` frames)
+struct EventsPlan { bool mixing, scored, notes; size_t nm, R, chunk; };
+// the argument checks of a scheduler launch of `frames` > 0 frames, then what it needs: a captured launch grows nothing
+int events_prepare(fdsp_bank* b, size_t frames, const float* d_in, const float* d_out, const float* d_mix, int mode, bool capturing, EventsPlan* plan) {
+    const bool mixing = d_out == nullptr, scored = b->score_mem != nullptr;
     if (!b->ev && !scored) return fail(FDSP_EINVAL, "no events set (fdsp_bank_set_events) and no score (fdsp_bank_set_score)");
     if (!d_out && !d_mix) return fail(FDSP_EINVAL, mixing ? "d_mix is NULL" : "d_out is NULL");
     if (fdsp_bank_inputs(b) > 0 && !d_in) return fail(FDSP_EINVAL, "d_in is NULL but the graph has inputs");
     if (mode != FDSP_MODE_PROCESS && mode != FDSP_MODE_TICK) return fail(FDSP_EINVAL, "bad mode");
     if (mixing && !(scored ? (bool)b->ops->render_score_mix : (bool)b->ops->render_events_mix))
         return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "' has no fused Sequencer mix: call fdsp_bank_process_events and fdsp_sum_voices");
-    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s != b->stream) hipStreamIsCapturing(s, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;  // a captured launch leaves the timing events alone
     const size_t nm = (size_t)fdsp_bank_outputs(b), groups = b->stride / 64, R = nm * frames;
-    // one lane per note: asked for, and the kind can (otherwise today's kernel, silently); mixed: through a chunked voice-out scratch
     const bool notes = scored && b->score_exec == FDSP_SCORE_NOTES && score_notes_kind(b) && (!mixing || nm <= 2);
     const size_t chunk = notes && mixing ? score_chunk_frames(b, frames) : 0;
     if (mixing && (groups * R > b->mix_part_n || nm * chunk * b->V > b->score_scratch_n)) {
@@ -2227,19 +2221,16 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
         if (capturing) return fail(FDSP_EINVAL, "a scored launch with score_exec = FDSP_SCORE_NOTES during a stream capture: call fdsp_bank_mix_reserve before capturing");
         if (int rc = ensure_score_stage(b)) return rc;
     }
-    if (int rc = order_after_bank_stream(b, s)) return rc;
-    if (int rc = check_ring_need(b, capturing)) return rc;
-    if (b->ext_pending && !capturing) HIPCHK(hipStreamWaitEvent(s, b->e1, 0));
-    const bool timing = timing_on(b);  // the per-launch event pair is optional, as in fdsp_bank_process
-    if (!capturing && timing) HIPCHK(hipEventRecord(b->e0, s));
-    // the clock after this launch, advanced exactly as the reference does: one f64 addition per block / per sample
-    const double sd = 1.0 / b->sr, t_begin = b->seq_time;
-    double t_end = t_begin;
-    if (mode == FDSP_MODE_PROCESS)
-        for (size_t t0 = 0; t0 < frames; t0 += 64) t_end += sd * (double)(frames - t0 < 64 ? frames - t0 : 64);
-    else
-        for (size_t t = 0; t < frames; t++) t_end += sd;
-    if (!scored && b->ev_dirty) {
+    *plan = EventsPlan{mixing, scored, notes, nm, R, chunk};
+    return FDSP_OK;
+}
+// Every voice inside its event from t_begin to t_end and no fade running in any of the blocks between (the kernel's own
+// per-block conditions, evaluated for the first and the last block): the scheduler's output is the units' plain
+// process / tick -- same arithmetic -- so the launch takes the (pipeline) render kernel.  The aggregates over the host
+// mirror of the events are brought up to date first.
+bool events_sustained(fdsp_bank* b, double t_begin, double t_end) {
+    if (b->ev_host.empty()) return false;
+    if (b->ev_dirty) {
         const double inf = std::numeric_limits<double>::infinity();
         b->ev_max_start = -inf; b->ev_min_end = inf; b->ev_max_fade_in_end = -inf; b->ev_min_fade_out_start = inf;
         for (size_t v = 0; v < b->V; v++) {
@@ -2251,12 +2242,24 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
         }
         b->ev_dirty = false;
     }
-    // Every voice inside its event for the whole launch and no fade running in any of its blocks (the kernel's own
-    // per-block conditions, evaluated for the first and the last block): the scheduler's output is the units' plain
-    // process / tick -- same arithmetic -- so the launch takes the (pipeline) render kernel.
-    const bool sustained = !scored && !b->ev_host.empty() && b->ev_max_start <= t_begin && b->ev_min_end >= t_end &&
-                           b->ev_max_fade_in_end <= t_begin && b->ev_min_fade_out_start >= t_end;
-    resolve_opts(b);
+    return b->ev_max_start <= t_begin && b->ev_min_end >= t_end && b->ev_max_fade_in_end <= t_begin && b->ev_min_fade_out_start >= t_end;
+}
+
+// fdsp_bank_process_events (d_mix == nullptr: every event's faded samples to d_out) and fdsp_bank_process_events_mix (d_out == nullptr: the
+// Sequencer's output, the sum of the events, to d_mix [outputs][frames]) share everything but the launch
+int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, float* d_mix, int mode, void* stream) {
+    if (!b) return fail(FDSP_EINVAL, "bank is NULL");
+    if (int rc = render_only(b)) return rc;
+    DeviceGuard guard(b->device);
+    if (frames == 0) return FDSP_OK;
+    Launch launch(b, stream);
+    EventsPlan plan;
+    if (int rc = events_prepare(b, frames, d_in, d_out, d_mix, mode, launch.capturing, &plan)) return rc;
+    if (int rc = launch.begin()) return rc;
+    const auto [mixing, scored, notes, nm, R, chunk] = plan;
+    hipStream_t s = launch.s;
+    const double sd = 1.0 / b->sr, t_begin = b->seq_time, t_end = advance_clock(t_begin, frames, sd, mode);
+    const bool sustained = !scored && events_sustained(b, t_begin, t_end);
     const unsigned commit_grid = (unsigned)((b->V + 255) / 256);
     if (notes && mixing) {
         // Chunks of whole blocks: memset, notes, commit, the groups' partials into columns t0 ... of mix_part; then one tree.  Splitting a
@@ -2269,17 +2272,8 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
                                        b->score, tc, b->sr, mode, b->aux, s);
             hipLaunchKernelGGL(k_score_commit, dim3(commit_grid), dim3(256), 0, s, b->slots, (const float*)b->score_stage, score_flags(b), b->stride, b->V, b->nslots);
             const PartMap map{R, n, frames, t0};
-            const dim3 pgrid((unsigned)((b->V + 63) / 64), (unsigned)((nm * n + 255) / 256));
-            if (b->V % 4 == 0)  // (the scratch is 256-byte aligned)
-                hipLaunchKernelGGL((k_group_partials<false, true, true>), pgrid, dim3(256), 0, s, (const float*)b->score_scratch, (const float*)nullptr, (const float*)nullptr,
-                                   b->mix_part, nm * n, b->V, map);
-            else
-                hipLaunchKernelGGL((k_group_partials<false, false, true>), pgrid, dim3(256), 0, s, (const float*)b->score_scratch, (const float*)nullptr, (const float*)nullptr,
-                                   b->mix_part, nm * n, b->V, map);
-            if (mode == FDSP_MODE_PROCESS)
-                for (size_t t = 0; t < n; t += 64) tc += sd * (double)(n - t < 64 ? n - t : 64);
-            else
-                for (size_t t = 0; t < n; t++) tc += sd;
+            launch_group_partials<false>(b->score_scratch, nullptr, nullptr, b->mix_part, nm * n, b->V, b->V % 4 == 0 /* the scratch is 256-byte aligned */, s, &map);
+            tc = advance_clock(tc, n, sd, mode);
         }
         launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, s);
     } else if (notes) {
@@ -2296,10 +2290,8 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
         else if (!done)
             done = b->ops->render_events_mix(b->slots, b->stride, b->V, d_in, b->mix_part, frames, b->ev, b->ev_fade, b->seq_time, b->sr, mode,
                                              b->aux, b->ring, b->ring_cap, s);
-        if (!done) {
-            b->timed = false;
+        if (!done)
             return fail(FDSP_ENOTSUP, "kind '" + b->ops->name + "': more than two outputs -- no fused Sequencer mix; call fdsp_bank_process_events and fdsp_sum_voices");
-        }
         launch_mix_tree(b->mix_part, d_mix, R, (b->V + 63) / 64, s);
     } else if (scored)
         b->ops->render_score(b->slots, b->stride, b->V, d_in, d_out, frames, b->score, b->seq_time, b->sr, mode, b->aux, b->ring, b->ring_cap, s);
@@ -2309,13 +2301,7 @@ int events_render(fdsp_bank* b, size_t frames, const float* d_in, float* d_out, 
     else
         b->ops->render_events(b->slots, b->stride, b->V, d_in, d_out, frames, b->ev, b->ev_fade, b->seq_time, b->sr, mode,
                               b->aux, b->ring, b->ring_cap, s);
-    b->last_kernel = fd::tl_opts.last_kernel;
-    HIPCHK(hipGetLastError());
-    if (!capturing) {
-        if (timing || s != b->stream) HIPCHK(hipEventRecord(b->e1, s));
-        b->timed = timing;
-        b->ext_pending = s != b->stream;
-    }
+    if (int rc = launch.finish()) return rc;
     b->seq_time = t_end;
     return FDSP_OK;
 }
