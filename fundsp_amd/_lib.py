@@ -34,6 +34,12 @@ class FdnNetwork(C.Structure):
                 ("per_instance", _i), ("delays", C.POINTER(_d)), ("weights", _fp), ("cutoff", _fp), ("q", _fp), ("gain", _fp), ("line_gain", _fp)]
 
 
+class FeedbackDelay(C.Structure):
+    """struct fdsp_feedback_delay (include/fundsp_hip.h)"""
+    _fields_ = [("channels", _i), ("taps", _i), ("filter", _i), ("svf_mode", _i), ("place", _i), ("reverse", _i), ("per_instance", _i),
+                ("delays", C.POINTER(_d)), ("weights", _fp), ("cutoff", _fp), ("q", _fp), ("gain", _fp), ("line_gain", _fp), ("outer_gain", _fp)]
+
+
 RESYNTH_PASS, RESYNTH_BAND, RESYNTH_GAIN = 0, 1, 2   # fdsp_resynth_spec::processor
 
 
@@ -90,6 +96,8 @@ SYMBOLS = {
     "fdsp_fdn_create_on": (_i, [_i, _sz, _i, C.POINTER(_d), _i, C.POINTER(C.c_float), _i, _i, C.POINTER(_P)]),
     "fdsp_fdn_network_create": (_i, [_sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
     "fdsp_fdn_network_create_on": (_i, [_i, _sz, C.POINTER(FdnNetwork), _d, C.POINTER(_P)]),
+    "fdsp_feedback_delay_create": (_i, [_sz, C.POINTER(FeedbackDelay), _d, C.POINTER(_P)]),
+    "fdsp_feedback_delay_create_on": (_i, [_i, _sz, C.POINTER(FeedbackDelay), _d, C.POINTER(_P)]),
     "fdsp_resynth_create": (_i, [_sz, C.POINTER(ResynthSpec), C.POINTER(_P)]),
     "fdsp_resynth_create_on": (_i, [_i, _sz, C.POINTER(ResynthSpec), C.POINTER(_P)]),
     "fdsp_resynth_set_band": (_i, [_P, _fp, _sz, _sz]),

@@ -356,6 +356,86 @@ class Bank:
         return b
 
     @classmethod
+    def feedback_delay(cls, instances, delays, weights=None, filter=None, place="line", cutoff=None, q=1.0, gain=1.0, line_gain=None,
+                       outer_gain=None, reverse=False, sample_rate=None, device=-1):
+        """Bank of `instances` x the identity feedback around one or two delay lines -- echo, comb, ping-pong -- through the lane-per-frame
+        feedback delay kernel (fdsp_feedback_delay_create):
+
+            place="line":  feedback( L [>> reverse()] [* outer_gain] ),  L = line | line_0 | line_1,
+                           line_i = delay(delays[i]) [>> fir(weights[i])] [>> F_i] [* line_gain[i]]
+            place="loop":  feedback2( L [>> reverse()], Y ),  line_i = delay(delays[i]) [>> fir(weights[i])],  Y = stack of F_i [* line_gain[i]]
+
+        The channels N = 1 or 2 are the last extent of `delays` (a scalar is one channel); inputs = outputs = N.  `filter`: None, "lowpole"
+        (lowpole_hz(cutoff[i])) or a FixedSvf mode "lowpass" .. "highshelf" (at cutoff[i], q[i], gain[i]).  `delays`, `cutoff`, `q`, `gain`,
+        `line_gain` are scalars, [N] or [instances, N] arrays; `weights` is None (no Fir node), [taps] (every line), [N, taps] or
+        [instances, N, taps]; `outer_gain` is None (no such node), a scalar or [instances].  Any [instances, ..] array makes the parameters per
+        instance.  The bank is created at `sample_rate` (default DEFAULT_SR), where every delay must be at least 128 samples and no ring may
+        exceed 2^18 slots."""
+        V = int(instances)
+        d = np.asarray(delays, dtype=np.float64)
+        if d.ndim == 0:
+            d = d[None]
+        N = int(d.shape[-1])
+        w = None if weights is None else np.asarray(weights, dtype=np.float32)
+        taps = 0 if w is None else int(w.shape[-1])
+        if w is not None and w.ndim == 1:
+            w = np.broadcast_to(w, (N, taps))
+        arrs = dict(delays=d)
+        if filter is not None:
+            if cutoff is None:
+                raise ValueError("feedback_delay: a filter needs its cutoff")
+            arrs["cutoff"] = np.asarray(cutoff, dtype=np.float32)
+            if filter != "lowpole":
+                arrs["q"] = np.asarray(q, dtype=np.float32)
+                arrs["gain"] = np.asarray(gain, dtype=np.float32)
+        if line_gain is not None:
+            arrs["line_gain"] = np.asarray(line_gain, dtype=np.float32)
+        og = None if outer_gain is None else np.asarray(outer_gain, dtype=np.float32)
+        if og is not None and og.ndim > 1:
+            raise ValueError("feedback_delay: outer_gain takes a scalar or [instances]")
+        per = any(a.ndim == 2 for a in arrs.values()) or (w is not None and w.ndim == 3) or (og is not None and og.ndim == 1)
+        shape = (V, N) if per else (N,)
+        arrs = {k: np.ascontiguousarray(np.broadcast_to(a, shape), dtype=a.dtype) for k, a in arrs.items()}
+        if w is not None:
+            w = np.ascontiguousarray(np.broadcast_to(w, shape + (taps,)), dtype=np.float32)
+        if og is not None:
+            og = np.ascontiguousarray(np.broadcast_to(og, (V,) if per else (1,)), dtype=np.float32)
+        net = _lib.FeedbackDelay()
+        net.channels, net.taps = N, taps
+        net.filter = _lib.FDN_FILTER_NONE if filter is None else _lib.FDN_FILTER_LOWPOLE if filter == "lowpole" else _lib.FDN_FILTER_SVF
+        net.svf_mode = 0 if filter in (None, "lowpole") else int(SVF_MODES[filter] if isinstance(filter, str) else filter)
+        net.place = {"line": _lib.FDN_IN_LINE, "loop": _lib.FDN_IN_LOOP}[place]
+        net.reverse = 1 if reverse else 0
+        net.per_instance = 1 if per else 0
+        net.delays = arrs["delays"].ctypes.data_as(C.POINTER(C.c_double))
+        net.weights = _fptr(w) if w is not None else None
+        for k in ("cutoff", "q", "gain", "line_gain"):
+            setattr(net, k, _fptr(arrs[k]) if k in arrs else None)
+        net.outer_gain = _fptr(og) if og is not None else None
+        h = C.c_void_p()
+        sr = float(sample_rate) if sample_rate is not None else _lib.DEFAULT_SR
+        check(lib().fdsp_feedback_delay_create_on(int(device), V, C.byref(net), sr, C.byref(h)))
+        b = cls("feedback_delay", V, _handle=h)
+        b.sample_rate = sr
+        return b
+
+    @classmethod
+    def feedback_tree(cls, graph, instances, sample_rate=None, device=-1):
+        """The feedback delay bank of `feedback(..)` / `feedback2(..)` around one or two delay lines (graph.feedback_delay_plan): the echo
+        `feedback(delay(1.0) * db_amp(-3.0))`, the ping-pong `feedback((delay(1.0) | delay(1.0)) >> reverse(2) * db_amp(-6.0))`, the combs
+        with a filter in the line or in the loop.  Bank.from_graph keeps compiling these graphs (its banks have slots, set_param and
+        get_state; an effect bank has none): this is the constructor of its own, and a chain is composed by the caller --
+        `Chain(front, Bank.feedback_tree(body, V), construction_hash=probe_hash(front >> body))`.  The bank is created at `sample_rate`
+        (default DEFAULT_SR), where every delay must be at least 128 samples."""
+        from . import graph as G
+
+        plan = G.feedback_delay_plan(graph, int(instances))
+        if plan is None:
+            raise ValueError("feedback_tree: the graph takes feedback(L [>> reverse(2)] [* g]) or feedback2(L [>> reverse(2)], Y) with L one "
+                             "line or a stack of two, line = delay(t) [>> fir(w..)] [>> F] [* g], F = lowpole_hz(c) or one FixedSvf mode")
+        return cls.feedback_delay(instances, **plan, sample_rate=sample_rate, device=device)
+
+    @classmethod
     def resynth(cls, instances, window, inputs=1, outputs=1, processor="pass", source=None, band=None, gain=None, flush_denormals=False,
                 device=-1):
         """Bank of `instances` x resynth::<I, O, _>(window, closure) (resynth.rs:216-372) through the batched FFT kernels

@@ -1277,6 +1277,35 @@ int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_netw
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
     return fdsp_fdn_network_create_on(-1, instances, net, sample_rate, out);
 }
+int fdsp_feedback_delay_create_on(int device, size_t instances, const fdsp_feedback_delay* net, double sample_rate, fdsp_bank** out) {
+    if (out) *out = nullptr;
+    if (!net) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: network NULL");
+    const int N = net->channels;
+    if (N != 1 && N != 2) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: channels takes 1 or 2 (the feedback delay kernel holds one or two lines)");
+    if (net->taps < 0 || net->taps > 3) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: taps takes 0 (no Fir node) .. 3");
+    if (net->filter < FDSP_FDN_FILTER_NONE || net->filter > FDSP_FDN_FILTER_SVF) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: filter takes FDSP_FDN_FILTER_NONE, _LOWPOLE or _SVF");
+    if (net->filter == FDSP_FDN_FILTER_SVF && (net->svf_mode < FDSP_SVF_LOWPASS || net->svf_mode > FDSP_SVF_HIGHSHELF))
+        return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: svf_mode takes FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF");
+    if (net->place != FDSP_FDN_IN_LINE && net->place != FDSP_FDN_IN_LOOP) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: place takes FDSP_FDN_IN_LINE (feedback) or FDSP_FDN_IN_LOOP (feedback2)");
+    if (net->place == FDSP_FDN_IN_LOOP && net->filter == FDSP_FDN_FILTER_NONE) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the loop form (feedback2) needs a filter");
+    if (net->place == FDSP_FDN_IN_LOOP && net->outer_gain) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the loop form (feedback2) has no outer gain (the gain belongs to y: line_gain)");
+    if (net->reverse && N != 2) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: reverse() needs two channels");
+    if (!net->delays) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: delays NULL");
+    if (net->taps > 0 && !net->weights) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: weights NULL");
+    const bool shelf = net->filter == FDSP_FDN_FILTER_SVF && net->svf_mode >= FDSP_SVF_BELL;
+    if (net->filter != FDSP_FDN_FILTER_NONE && !net->cutoff) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the filter's cutoff is missing");
+    if (net->filter == FDSP_FDN_FILTER_SVF && !net->q) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the FixedSvf's q is missing");
+    if (shelf && !net->gain) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: bell / lowshelf / highshelf need a gain");
+    if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: sample_rate must be positive");
+    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: no instances");
+    const size_t M = (net->per_instance ? instances : 1) * (size_t)N;
+    for (size_t i = 0; i < M; i++)
+        if (!(net->delays[i] >= 0.0) || !(net->delays[i] < 1e6)) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+    return fx_bank_create(device, instances, sample_rate, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_feedback_delay(instances, *net, sample_rate, s, fx); });
+}
+int fdsp_feedback_delay_create(size_t instances, const fdsp_feedback_delay* net, double sample_rate, fdsp_bank** out) {
+    return fdsp_feedback_delay_create_on(-1, instances, net, sample_rate, out);
+}
 
 // ---- resynthesizer banks (fd_fxbank.hpp fx_resynth) --------------------------------------------------------------------------------------
 static int rs_check_spec(size_t instances, const fdsp_resynth_spec* sp) {

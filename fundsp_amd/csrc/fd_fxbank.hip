@@ -1,11 +1,12 @@
 // fd_fxbank.hip -- the effect banks of fd_fxbank.hpp: buffers, configuration, clone and launch of each family (host code; the kernels are in
-// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_resynth.hip and fd_convolve.hip; those of the networks' fused mix-down in fd_fxmix.hip).
+// fd_fdn.hip, fd_reverb3.hip, fd_fdnx.hip, fd_fbdelay.hip, fd_resynth.hip and fd_convolve.hip; those of the networks' fused mix-down in fd_fxmix.hip).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "fd_fxbank.hpp"
 #include "fd_convolve.hpp"
+#include "fd_fbdelay.hpp"
 #include "fd_fdnx.hpp"
 #include "fd_opts.hpp"
 #include "fd_resynth.hpp"
@@ -398,6 +399,49 @@ class FdnxFx final : public NetFx {
     FdnxState st_{};
 };
 
+// feedback delay banks (fd_fbdelay.hpp): FdnxFx's life cycle around the identity-feedback kernel.  The new rings start empty, the coefficients
+// follow the rate, and the Fir carry, the filter states and the feedback value stay
+class FeedbackDelayFx final : public NetFx {
+  public:
+    FeedbackDelayFx(const FbDesc& d, size_t V) : NetFx(V, "feedback_delay"), d_(d) { tables_ = 1; }
+    ~FeedbackDelayFx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { fb_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+
+  private:
+    int configure(double sr, hipStream_t s) override {
+        std::vector<FbInst> tab;
+        FbConst c;
+        const int shortest = fb_make_table(d_, V_, sr, tab, &c);
+        if (shortest < 0 || c.cap > (1 << 18))
+            return api_fail(FDSP_EINVAL, "fdsp_feedback_delay_create: no ring may exceed 2^18 slots (a delay too long for the lane-per-frame kernel at this sample rate)");
+        if (shortest < 128)
+            return api_fail(FDSP_EINVAL, "fdsp_feedback_delay_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+        FdnxState st{};
+        hipError_t e = alloc_bufs(bufs(c, st));
+        if (e == hipSuccess && (e = hipMemcpyAsync((void*)c.tab, tab.data(), tab.size() * sizeof(FbInst), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st));
+        if (e != hipSuccess) return hip_fail(e, "fdsp_feedback_delay_create buffers");
+        fb_launch_reset(c, st, V_, s);
+        carry_and_free(bufs(c, st), bufs(c_, st_), 3, s);   // v1, v2, fb, s1, s2 (and the stream drains before `tab` goes)
+        c_ = c; st_ = st; sr_ = sr;
+        nin_ = nout_ = c.lines;
+        return launch_error();
+    }
+    Bufs bufs(FbConst& c, FdnxState& st) const {
+        const size_t n = V_;
+        return {{(void**)&c.tab, (c.tab_stride ? n : 1) * sizeof(FbInst)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)},
+                {(void**)&st.wpos, n * sizeof(int)}, {(void**)&st.v1, n * 32 * sizeof(float)}, {(void**)&st.v2, n * 32 * sizeof(float)},
+                {(void**)&st.fb, n * 32 * sizeof(float)}, {(void**)&st.s1, n * 32 * sizeof(float)}, {(void**)&st.s2, n * 32 * sizeof(float)}};
+    }
+    Bufs bufs() override { return bufs(c_, st_); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<FeedbackDelayFx>(d_, V_); }
+    // Feedback::process is the per-sample tick and these graphs have no join: one arithmetic for both modes
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int, hipStream_t s) override { fb_launch_render(c_, st_, V_, in, out, T, fstride, layout, s, bus_); }
+
+    FbDesc d_;
+    FbConst c_{};
+    FdnxState st_{};
+};
+
 int make_net(std::unique_ptr<NetFx> f, double sr, hipStream_t s, std::unique_ptr<FxBank>* out) {
     if (int rc = f->create(sr, s)) return rc;
     *out = std::move(f);
@@ -622,6 +666,21 @@ int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_
     if (net.filter == FDSP_FDN_FILTER_SVF && net.svf_mode >= FDSP_SVF_BELL) d.gain.assign(net.gain, net.gain + M);
     if (d.has_gain) d.line_gain.assign(net.line_gain, net.line_gain + M);
     return make_net(std::make_unique<FdnxFx>(d, instances), sample_rate, s, out);
+}
+
+int fx_feedback_delay(size_t instances, const fdsp_feedback_delay& net, double sample_rate, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    FbDesc d;
+    d.lines = net.channels; d.taps = net.taps; d.filter = net.filter; d.svf_mode = net.svf_mode; d.place = net.place;
+    d.per_instance = net.per_instance ? 1 : 0; d.has_gain = net.line_gain ? 1 : 0; d.has_outer = net.outer_gain ? 1 : 0; d.reverse = net.reverse ? 1 : 0;
+    const size_t P = d.per_instance ? instances : 1, M = P * (size_t)net.channels;
+    d.delay.assign(net.delays, net.delays + M);
+    if (net.taps > 0) d.w.assign(net.weights, net.weights + M * net.taps);
+    if (net.filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net.cutoff, net.cutoff + M);
+    if (net.filter == FDSP_FDN_FILTER_SVF) d.q.assign(net.q, net.q + M);
+    if (net.filter == FDSP_FDN_FILTER_SVF && net.svf_mode >= FDSP_SVF_BELL) d.gain.assign(net.gain, net.gain + M);
+    if (d.has_gain) d.line_gain.assign(net.line_gain, net.line_gain + M);
+    if (d.has_outer) d.outer.assign(net.outer_gain, net.outer_gain + P);
+    return make_net(std::make_unique<FeedbackDelayFx>(d, instances), sample_rate, s, out);
 }
 
 // the frame ring of a bank: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large

@@ -1,6 +1,6 @@
 // fd_fxbank.hpp -- the effect banks: banks of one stock node per instance instead of a voice graph of slots -- the Hadamard networks
 // (reverb_stereo, reverb4_stereo, the generic `fdn`: fd_fdn.hpp), reverb3_stereo (fd_reverb3.hpp), the filtered / per-instance networks
-// (fd_fdnx.hpp), the resynthesizer (fd_resynth.hpp) and the convolver (fd_convolve.hpp).  fd_capi.hip keeps the bank handle (stream, events, pan weights, launch options)
+// (fd_fdnx.hpp), the feedback delay banks (fd_fbdelay.hpp), the resynthesizer (fd_resynth.hpp) and the convolver (fd_convolve.hpp).  fd_capi.hip keeps the bank handle (stream, events, pan weights, launch options)
 // and the public constructors' argument checks; what a family allocates, configures, copies and launches is behind FxBank (fd_fxbank.hip).
 #pragma once
 
@@ -48,7 +48,7 @@ void fx_launch_stage_in(const float* src, float* dst, size_t V, size_t T, int ch
 void fx_launch_copy_rows(const float* src, size_t sstride, float* dst, size_t dstride, size_t rows, size_t n, hipStream_t stream);
 
 // The factories build and initialise an instance on `stream`.  The arguments are checked by the caller; what can still fail is the
-// kernels' delay rule at the creation rate (44.1 kHz but for fx_fdn_network) and the allocation.
+// kernels' delay rule at the creation rate (44.1 kHz but for fx_fdn_network and fx_feedback_delay) and the allocation.
 // sections 1: reverb_stereo(room_size, time, damping), 2: reverb4_stereo(room_size, time)
 int fx_reverb_stereo(size_t instances, int sections, double room_size, double time, double damping, hipStream_t stream, std::unique_ptr<FxBank>* out);
 // reverb4_stereo_delays(delays, time): `delays` = [32] f32 seconds, or [instances][32] with per_instance (fd_fdn.hpp "PER INSTANCE")
@@ -63,6 +63,8 @@ int fx_fdn(size_t instances, int lines, const double* delays, int taps, const fl
 int fx_reverb3_stereo(size_t instances, double time, double diffusion, int svf_mode, float cutoff, float q, float gain, hipStream_t stream,
                       std::unique_ptr<FxBank>* out);
 int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t stream, std::unique_ptr<FxBank>* out);
+// the feedback delay banks (fd_fbdelay.hpp; the description checked by the caller but for the delay rules at `sample_rate`)
+int fx_feedback_delay(size_t instances, const fdsp_feedback_delay& net, double sample_rate, hipStream_t stream, std::unique_ptr<FxBank>* out);
 int fx_resynth(size_t instances, const fdsp_resynth_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);
 // a closure bank (fd_resynth_fn.hpp): the functor's module is compiled and loaded before anything is allocated; _compile alone needs no device
 int fx_resynth_fn(size_t instances, const fdsp_resynth_fn_spec& spec, hipStream_t stream, std::unique_ptr<FxBank>* out);

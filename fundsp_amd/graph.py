@@ -815,6 +815,169 @@ def fdn_network_plan(g, voices=None):
     return out
 
 
+def _flat_chain(n, path, out):
+    """a Pipe chain of a parsed type, left to right, as (node, parameter path) elements; `x * scalar` as a ("*", path) element behind x's"""
+    if n[0] == "Pipe" and len(n[1]) == 2:
+        _flat_chain(n[1][0], path + (0,), out)
+        _flat_chain(n[1][1], path + (1,), out)
+    elif n[0] == "Unop" and len(n[1]) == 2 and n[1][1][0] == "UMulScalar":
+        _flat_chain(n[1][0], path + (0,), out)
+        out.append((("*", []), path))
+    else:
+        out.append((n, path))
+    return out
+
+
+def feedback_delay_plan(g, voices=None):
+    """The arguments of Bank.feedback_delay (fdsp_feedback_delay_create) when `g` is the identity feedback around one or two delay lines --
+
+        line form:  feedback( L [>> reverse(2)] [* g] )
+        loop form:  feedback2( L [>> reverse(2)], Y )
+          L      = line  |  line_0 | line_1  (also stacki(2, ..))
+          line_i = delay(t_i) [>> fir(w_i..)] [>> F_i] [* g_i]        (loop form: delay [>> fir] only)
+          Y      = F [* g]  |  (F_0 [* g_0]) | (F_1 [* g_1])
+
+    with F lowpole_hz(c) or one FixedSvf mode (lowpass_hz .. highshelf_hz) for the whole network, 1..3 FIR weights, the two lines of one
+    structure, and every parameter a scalar or a per-voice array of length `voices` -- else None.  At one channel the first `* g` behind the
+    line is the line's gain and a second one the outer gain (one multiplication each, in that order).  Bank.feedback_tree builds the bank;
+    Bank.from_graph does not take this route."""
+    fb = _parse_type(g.type)
+    if fb[0] not in ("Feedback", "Feedback2") or fb[1][-1][0] != "FbId" or len(fb[1]) != (3 if fb[0] == "Feedback2" else 2):
+        return None
+    loop = fb[0] == "Feedback2"
+    body = _flat_chain(fb[1][0], (0,), [])
+    head, hpath = body[0]
+    rest = body[1:]
+    # the lines: (parsed type, parameter path) per channel
+    if head[0] == "Stack" and len(head[1]) == 2:
+        lines = [(head[1][0], hpath + (0,)), (head[1][1], hpath + (1,))]
+    elif head[0] == "MultiStack" and len(head[1]) == 2 and head[1][0][0] == "2":
+        lines = [(head[1][1], hpath + (0,)), (head[1][1], hpath + (1,))]
+    else:
+        lines, rest = None, []   # one channel: the body is the line itself (its gains told apart below)
+    if lines is None:
+        n, xs = 1, [body]
+    else:
+        if lines[0][0] != lines[1][0]:
+            return None           # the two lines have one structure (the kernel is instantiated on it)
+        n, xs = 2, [_flat_chain(t, p, []) for t, p in lines]
+    reverse, outer = False, None
+    if rest and rest[0][0] == ("Reverse", [("2", [])]) and n == 2:
+        reverse, rest = True, rest[1:]
+    if rest and rest[0][0][0] == "*":
+        outer, rest = rest[0][1], rest[1:]
+    if rest:
+        return None               # something else behind the lines
+    kinds = [e[0][0] for e in xs[0]]
+    if kinds[0] != "Delay":
+        return None               # (a filter in front of the delay, more than two channels, another network)
+    taps, k = 0, 1
+    if k < len(kinds) and kinds[k] == "Fir":
+        try:
+            taps = int(xs[0][k][0][1][0][0])
+        except (IndexError, ValueError):
+            return None
+        if not 1 <= taps <= 3:
+            return None
+        k += 1
+    if loop:
+        if k != len(kinds) or outer is not None:
+            return None           # feedback2's x: delay [>> fir] [>> reverse] only
+        y = fb[1][1]
+        if n == 1:
+            ys = [_flat_chain(y, (1,), [])]
+        elif y[0] == "Stack" and len(y[1]) == 2 and y[1][0] == y[1][1]:
+            ys = [_flat_chain(y[1][i], (1, i), []) for i in range(2)]
+        elif y[0] == "MultiStack" and len(y[1]) == 2 and y[1][0][0] == "2":
+            ys = [_flat_chain(y[1][1], (1, i), []) for i in range(2)]
+        else:
+            return None
+        tails = ys
+    else:
+        tails = [x[k:] for x in xs]
+
+    def is_filter(e):
+        return e[0][0] == "FixedSvf" or (e[0][0] == "OnePole" and [c[0] for c in e[0][1]] == ["OP_LOWPOLE", "1"])
+
+    filt = gain = None
+    t0 = [e[0][0] for e in tails[0]]
+    pos = 0
+    if pos < len(t0) and is_filter(tails[0][pos]):
+        filt, pos = pos, pos + 1
+    if loop and filt is None:
+        return None
+    if pos < len(t0) and t0[pos] == "*":
+        gain, pos = pos, pos + 1
+    if n == 1 and not loop and pos < len(t0) and t0[pos] == "*":
+        outer_el, pos = tails[0][pos][1], pos + 1
+    else:
+        outer_el = None
+    if pos != len(t0):
+        return None               # something else in the line (pinkpass, a second filter, ..)
+    if outer_el is not None:
+        outer = outer_el
+    vals = {}
+    for path, field, value, _u in g.params:
+        vals[(tuple(path), field)] = np.asarray(value)
+    lens = set()
+    used = 0
+
+    def one(path, field):
+        nonlocal used
+        v = vals[(tuple(path), field)]   # (KeyError: the node lacks the parameter)
+        if v.ndim > 1:
+            raise KeyError(field)
+        if v.ndim == 1:
+            lens.add(len(v))
+        used += 1
+        return v
+
+    def col(elems, field, dtype=np.float32):
+        vs = [one(e[1], field) for e in elems]
+        if all(v.ndim == 0 for v in vs):
+            return np.array([float(np.float32(v)) for v in vs], dtype=dtype)
+        if len({len(v) for v in vs if v.ndim == 1}) > 1:
+            raise KeyError(field)   # per-voice arrays of different lengths
+        m = max(len(v) for v in vs if v.ndim == 1)
+        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float32).astype(dtype), (m,)) for v in vs], axis=1)   # [voices, channels]
+
+    out = dict(place="loop" if loop else "line", reverse=reverse)
+    try:
+        out["delays"] = col([x[0] for x in xs], "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
+        if taps:
+            ws = [col([x[1] for x in xs], f"w[{j}]") for j in range(taps)]
+            if len({w.shape[0] for w in ws if w.ndim == 2}) > 1:
+                return None   # per-voice arrays of different lengths
+            out["weights"] = np.stack(np.broadcast_arrays(*ws), axis=-1)   # [N, taps] | [voices, N, taps]
+        if filt is not None:
+            fe = [t[filt] for t in tails]
+            out["cutoff"] = col(fe, "cutoff")
+            if fe[0][0][0] == "FixedSvf":
+                modes = col(fe, "mode")
+                if modes.ndim != 1 or len(set(modes.tolist())) != 1:
+                    return None   # the mode is a type parameter in Rust: one for the network
+                inv = {v: k for k, v in SVF_MODES.items()}
+                if int(modes[0]) not in inv:
+                    return None
+                out["filter"] = inv[int(modes[0])]
+                out["q"] = col(fe, "q")
+                out["gain"] = col(fe, "gain")
+            else:
+                out["filter"] = "lowpole"
+        if gain is not None:
+            out["line_gain"] = col([t[gain] for t in tails], "scalar")
+        if outer is not None:
+            v = one(outer, "scalar")
+            out["outer_gain"] = float(np.float32(v)) if v.ndim == 0 else np.asarray(v, dtype=np.float32)
+    except KeyError:
+        return None
+    if used != len(g.params):
+        return None               # something else carries parameters (builders on the nodes): not this shape
+    if len(lens) > 1 or (voices is not None and lens and lens != {int(voices)}):
+        return None               # per-voice arrays must have one value per voice
+    return out
+
+
 def lane_per_frame_shape(g):
     """whether `g` is one of the nodes / networks with a lane-per-frame kernel (what Bank.from_graph builds as an FDN / reverb bank)"""
     return (getattr(g, "stock_reverb", None) is not None or getattr(g, "reverb3_plan", None) is not None or fdn_plan(g) is not None

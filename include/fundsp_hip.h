@@ -316,6 +316,44 @@ typedef struct fdsp_fdn_network {
     const float* line_gain;             /* the `* g` behind the filter, NULL = no such node */
 } fdsp_fdn_network;
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out);
+/* Feedback delay banks: the identity-frame feedback around one or two delay lines -- the echo `feedback(delay(1.0) * db_amp(-3.0))`, the
+ * ping-pong `feedback((delay(1.0) | delay(1.0)) >> reverse() * db_amp(-6.0))` and the combs with a filter in the loop.  `instances`
+ * independent networks of `channels` = N = 1 or 2, inputs = outputs = N.  The grammar of the feedback body:
+ *   FDSP_FDN_IN_LINE:  feedback( L [>> reverse()] [* g] )        (Feedback<N, X, FrameId>, src/feedback.rs:108-146)
+ *   FDSP_FDN_IN_LOOP:  feedback2( L [>> reverse()], Y )          (Feedback2<N, X, Y, FrameId>, src/feedback.rs:233-276)
+ *     L      = line  |  line_0 | line_1
+ *     line_i = delay(t_i) [>> fir(w_i..)] [>> F_i] [* g_i]       (loop form: delay [>> fir] only)
+ *     Y      = F [* g]  |  (F_0 [* g_0]) | (F_1 [* g_1])
+ *     F      = lowpole_hz(c) (FDSP_FDN_FILTER_LOWPOLE) | the FixedSvf of `svf_mode` at (cutoff, q, gain) (FDSP_FDN_FILTER_SVF) | nothing
+ *              (FDSP_FDN_FILTER_NONE, line form only)
+ * taps = 0 means the line has no Fir node (1..3 otherwise, oldest tap first); line_gain = NULL that it has no `* g_i`; outer_gain = NULL that
+ * the body has no `* g` (line form only); reverse != 0 puts reverse() behind the two lines (N = 2 only).  Arrays are [channels]
+ * (per_instance = 0) or [instances][channels] (per_instance = 1); outer_gain is [1] or [instances].
+ * Per frame n and channel c, all in f32, one rounding per operation, subnormals flushed (Feedback::new calls prevent_denormals), in this order:
+ *   1. xin_c = in_c[n] + value_c;   2. d_c = Delay::tick(xin_c), len = round(t * sample_rate) + 1;
+ *   3. o_c = Fir::tick if taps, then F if it is in the line, then * g_c if the line has a gain;
+ *   4. p_c = o_perm(c) (identity or reversal), then p_c * g if the body has the outer gain;
+ *   5. line form: output_c = value_c = p_c (FrameId::frame multiplies by nothing);
+ *   6. loop form: output_c = p_c, value_c = F_c(p_c) [* g_c].
+ * FDSP_MODE_TICK and FDSP_MODE_PROCESS give the same bits, and so does every split of an input into launches.
+ * Rules: every delay must be at least 128 samples at the bank's rate (two blocks: the lane-per-frame kernel's rule) and no ring may exceed
+ * 2^18 slots -- FDSP_EINVAL otherwise, at creation and at a later fdsp_bank_set_sample_rate (which then changes nothing).  A change of rate
+ * empties the delay lines and keeps the FIR carry, the filter states and the feedback value, like the reference.  Handle semantics of the
+ * reverb banks: process (both layouts), reset, clone, fdsp_bank_set_bus, the fused mix-down (FDSP_MIX_SUM; FDSP_MIX_PAN for N = 1). */
+typedef struct fdsp_feedback_delay {
+    int channels, taps;                 /* N = 1 | 2; taps 0 = no Fir node */
+    int filter;                         /* FDSP_FDN_FILTER_NONE | _LOWPOLE | _SVF */
+    int svf_mode;                       /* FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF */
+    int place;                          /* FDSP_FDN_IN_LINE (feedback) | FDSP_FDN_IN_LOOP (feedback2) */
+    int reverse;                        /* 1: reverse() behind the lines (N = 2) */
+    int per_instance;                   /* 0: arrays are [channels]; 1: [instances][channels] */
+    const double* delays;               /* seconds */
+    const float* weights;               /* [..][channels][taps] */
+    const float *cutoff, *q, *gain;     /* filter parameters (NULL where the filter has none) */
+    const float* line_gain;             /* the `* g_i` behind the line / the loop filter, NULL = no such node */
+    const float* outer_gain;            /* the `* g` behind the body: [1] | [instances], NULL = no such node */
+} fdsp_feedback_delay;
+int fdsp_feedback_delay_create(size_t instances, const fdsp_feedback_delay* net, double sample_rate, fdsp_bank** out);
 /* Resynthesizer banks: `instances` independent resynth::<I, O, _>(window_length, processor) nodes (src/resynth.rs:216-372, prelude
  * src/prelude.rs:2825-2856) with one of three stock processing closures (o and i in increasing order, bins i = 0 .. window_length/2):
  *   FDSP_RESYNTH_PASS  fft.set(o, i, fft.at(source[o], i))                    -- FftWindow::forward, the reference's criterion bench
@@ -522,6 +560,7 @@ int fdsp_reverb3_stereo_create_on(int device, size_t instances, double time, dou
 int fdsp_reverb3_stereo_svf_create_on(int device, size_t instances, double time, double diffusion, int svf_mode, float cutoff_hz, float q, float gain, fdsp_bank** out);
 int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out);
 int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out);
+int fdsp_feedback_delay_create_on(int device, size_t instances, const fdsp_feedback_delay* net, double sample_rate, fdsp_bank** out);
 int fdsp_bank_device(const fdsp_bank* bank);
 void fdsp_bank_destroy(fdsp_bank* bank);
 /* `Clone` (every AudioNode is Clone, src/audionode.rs:35; Net and Sequencer clone their units): a new bank of the same
@@ -670,8 +709,8 @@ double fdsp_bank_events_time(const fdsp_bank* bank);       /* Sequencer::time() 
  * voice-out and call the functions below, which use the same order. */
 #define FDSP_MIX_SUM 1
 #define FDSP_MIX_PAN 2
-/* EFFECT BANKS.  The lane-per-frame families -- reverb_stereo, reverb4_stereo, fdsp_fdn_create, reverb3_stereo, fdsp_fdn_network_create --
- * mix as well (resynthesizer and convolver banks answer FDSP_ENOTSUP).  One wave of their kernels owns one instance, so the reduction is a
+/* EFFECT BANKS.  The lane-per-frame families -- reverb_stereo, reverb4_stereo, fdsp_fdn_create, reverb3_stereo, fdsp_fdn_network_create,
+ * fdsp_feedback_delay_create -- mix as well (resynthesizer and convolver banks answer FDSP_ENOTSUP).  One wave of their kernels owns one instance, so the reduction is a
  * launch of its own: the instances render PLANAR into a scratch the bank owns, chunk by chunk (whole 64-frame blocks, "fx_mix_chunk_frames"),
  * a kernel adds every group of 64 instances into the partial-mix buffer in the order above, and the tree runs once at the end; no output
  * transpose and no full-length output exist.  The bus (fdsp_bank_set_bus) is part of the render, so the mix is the mix of the bussed output.

@@ -593,6 +593,15 @@ class Bank {
         b.kind_ = "fdn_network";
         return b;
     }
+    // feedback(L [>> reverse()] [* g]) | feedback2(L [>> reverse()], Y) around one or two delay lines -- echo, comb, ping-pong
+    // (fdsp_feedback_delay_create, fundsp_hip.h): `net` points at [channels] or [instances][channels] arrays the call copies; the bank runs
+    // at `sample_rate` from the start, where every delay must be at least 128 samples
+    static Bank feedback_delay(size_t instances, const fdsp_feedback_delay& net, double sample_rate) {
+        Bank b;
+        check(fdsp_feedback_delay_create(instances, &net, sample_rate, &b.h_));
+        b.kind_ = "feedback_delay";
+        return b;
+    }
     // resynth::<I, O, _>(window_length, |fft| ...) with the caller's closure as a C++ functor in source form (fdsp_resynth_fn_create,
     // fundsp_amd/csrc/fd_resynth_fn.hpp): compiled here, at creation; set_resynth_params replaces parameter rows between launches
     static Bank resynth_fn(size_t instances, const fdsp_resynth_fn_spec& spec) {

@@ -51,6 +51,24 @@ pub mod ffi {
         pub gain: *const f32,
         pub line_gain: *const f32,
     }
+    /// `struct fdsp_feedback_delay` (fdsp_feedback_delay_create): the identity feedback around one or two delay lines
+    #[repr(C)]
+    pub struct FdspFeedbackDelay {
+        pub channels: c_int,
+        pub taps: c_int,
+        pub filter: c_int,
+        pub svf_mode: c_int,
+        pub place: c_int,
+        pub reverse: c_int,
+        pub per_instance: c_int,
+        pub delays: *const f64,
+        pub weights: *const f32,
+        pub cutoff: *const f32,
+        pub q: *const f32,
+        pub gain: *const f32,
+        pub line_gain: *const f32,
+        pub outer_gain: *const f32,
+    }
     /// `struct fdsp_resynth_spec` (fdsp_resynth_create): a resynthesizer with a stock processing closure
     #[repr(C)]
     pub struct FdspResynthSpec {
@@ -125,6 +143,7 @@ pub mod ffi {
         pub fn fdsp_reverb3_stereo_svf_create_on(device: c_int, instances: usize, time: f64, diffusion: f64, svf_mode: c_int, cutoff_hz: f32, q: f32, gain: f32, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_create_on(device: c_int, instances: usize, lines: c_int, delays: *const f64, taps: c_int, weights: *const f32, inputs: c_int, outputs: c_int, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_fdn_network_create_on(device: c_int, instances: usize, net: *const FdspFdnNetwork, sample_rate: f64, out: *mut *mut FdspBank) -> c_int;
+        pub fn fdsp_feedback_delay_create_on(device: c_int, instances: usize, net: *const FdspFeedbackDelay, sample_rate: f64, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_resynth_create_on(device: c_int, instances: usize, spec: *const FdspResynthSpec, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_resynth_fn_create_on(device: c_int, instances: usize, spec: *const FdspResynthFnSpec, out: *mut *mut FdspBank) -> c_int;
         pub fn fdsp_resynth_set_params(bank: *mut FdspBank, values: *const f32, first: usize, count: usize) -> c_int;
@@ -194,6 +213,25 @@ pub struct FdnNetwork<'a> {
     pub q: Option<&'a [f32]>,
     pub gain: Option<&'a [f32]>,
     pub line_gain: Option<&'a [f32]>,
+}
+
+/// The network of `HipBank::feedback_delay` (see there): filter = FDSP_FDN_FILTER_*, svf_mode = FDSP_SVF_* order, place = FDSP_FDN_IN_LINE
+/// (`feedback`) | FDSP_FDN_IN_LOOP (`feedback2`); `taps` = 0 means no Fir node, `line_gain` / `outer_gain` = None no such `* g` node.
+pub struct FeedbackDelay<'a> {
+    pub channels: usize,
+    pub taps: usize,
+    pub filter: c_int,
+    pub svf_mode: c_int,
+    pub place: c_int,
+    pub reverse: bool,
+    pub per_instance: bool,
+    pub delays: &'a [f64],
+    pub weights: &'a [f32],
+    pub cutoff: Option<&'a [f32]>,
+    pub q: Option<&'a [f32]>,
+    pub gain: Option<&'a [f32]>,
+    pub line_gain: Option<&'a [f32]>,
+    pub outer_gain: Option<&'a [f32]>,
 }
 
 /// The engine's last error message for this thread.
@@ -365,6 +403,42 @@ impl<NI: Size<f32>, NO: Size<f32>> HipBank<NI, NO> {
         let mut bank: *mut FdspBank = core::ptr::null_mut();
         check(unsafe { fdsp_fdn_network_create_on(device as c_int, instances, &c, sample_rate, &mut bank) })?;
         Self::adopt(bank, "fdn_network", instances)
+    }
+
+    /// `instances` x the identity feedback around one or two delay lines (include/fundsp_hip.h `fdsp_feedback_delay`): the echo
+    /// `feedback(delay(t) * g)`, the ping-pong `feedback((delay(t) | delay(t)) >> reverse() * g)`, combs with `lowpole_hz` or a `FixedSvf` in
+    /// the line (`place` = FDSP_FDN_IN_LINE) or in `feedback2`'s loop (FDSP_FDN_IN_LOOP).  Every slice holds one value per channel, or with
+    /// `per_instance` one per instance and channel (`weights`: `taps` per channel; `outer_gain`: one per bank or per instance); the bank is
+    /// created at `sample_rate`, where every delay must be at least 128 samples.  Source only: no Rust toolchain has built it.
+    pub fn feedback_delay(instances: usize, net: &FeedbackDelay, sample_rate: f64, device: i32) -> Result<Self, String> {
+        let sets = if net.per_instance { instances } else { 1 };
+        let n = net.channels;
+        let per_line = |a: Option<&[f32]>, k: usize| a.map_or(true, |a| a.len() == sets * n * k);
+        if net.delays.len() != sets * n || !per_line(Some(net.weights), net.taps) || !per_line(net.cutoff, 1) || !per_line(net.q, 1)
+            || !per_line(net.gain, 1) || !per_line(net.line_gain, 1) || net.outer_gain.map_or(false, |a| a.len() != sets)
+        {
+            return Err("HipBank::feedback_delay: every slice needs one value per channel (per instance and channel with per_instance)".into());
+        }
+        let ptr = |a: Option<&[f32]>| a.map_or(core::ptr::null(), |a| a.as_ptr());
+        let c = FdspFeedbackDelay {
+            channels: n as c_int,
+            taps: net.taps as c_int,
+            filter: net.filter,
+            svf_mode: net.svf_mode,
+            place: net.place,
+            reverse: net.reverse as c_int,
+            per_instance: net.per_instance as c_int,
+            delays: net.delays.as_ptr(),
+            weights: if net.taps > 0 { net.weights.as_ptr() } else { core::ptr::null() },
+            cutoff: ptr(net.cutoff),
+            q: ptr(net.q),
+            gain: ptr(net.gain),
+            line_gain: ptr(net.line_gain),
+            outer_gain: ptr(net.outer_gain),
+        };
+        let mut bank: *mut FdspBank = core::ptr::null_mut();
+        check(unsafe { fdsp_feedback_delay_create_on(device as c_int, instances, &c, sample_rate, &mut bank) })?;
+        Self::adopt(bank, "feedback_delay", instances)
     }
 
     /// `instances` x `resynth::<I, O, _>(window_length, closure)` (src/resynth.rs) with a stock closure (include/fundsp_hip.h
