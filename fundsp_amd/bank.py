@@ -35,6 +35,41 @@ def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _line_net(net, who, V, N, delays, weights, filter, place, cutoff, q, gain, line_gain, also_per=False):
+    """The fields fdsp_fdn_network and fdsp_feedback_delay share, from the arguments Bank.fdn_network and Bank.feedback_delay share: `weights`
+    to [N, taps], every array broadcast to [N] or -- where one has an instance axis, or `also_per` says another input has -- to [V, N].
+    Returns (per instance?, the arrays `net` points into: keep them until the create call)."""
+    w = None if weights is None else np.asarray(weights, dtype=np.float32)
+    taps = 0 if w is None else int(w.shape[-1])
+    if w is not None and w.ndim == 1:
+        w = np.broadcast_to(w, (N, taps))
+    arrs = dict(delays=np.asarray(delays, dtype=np.float64))
+    if filter is not None:
+        if cutoff is None:
+            raise ValueError(f"{who}: a filter needs its cutoff")
+        arrs["cutoff"] = np.asarray(cutoff, dtype=np.float32)
+        if filter != "lowpole":
+            arrs["q"] = np.asarray(q, dtype=np.float32)
+            arrs["gain"] = np.asarray(gain, dtype=np.float32)
+    if line_gain is not None:
+        arrs["line_gain"] = np.asarray(line_gain, dtype=np.float32)
+    per = any(a.ndim == 2 for a in arrs.values()) or (w is not None and w.ndim == 3) or also_per
+    shape = (V, N) if per else (N,)
+    arrs = {k: np.ascontiguousarray(np.broadcast_to(a, shape), dtype=a.dtype) for k, a in arrs.items()}
+    if w is not None:
+        w = np.ascontiguousarray(np.broadcast_to(w, shape + (taps,)), dtype=np.float32)
+    net.taps = taps
+    net.filter = _lib.FDN_FILTER_NONE if filter is None else _lib.FDN_FILTER_LOWPOLE if filter == "lowpole" else _lib.FDN_FILTER_SVF
+    net.svf_mode = 0 if filter in (None, "lowpole") else int(SVF_MODES[filter] if isinstance(filter, str) else filter)
+    net.place = {"line": _lib.FDN_IN_LINE, "loop": _lib.FDN_IN_LOOP}[place]
+    net.per_instance = 1 if per else 0
+    net.delays = arrs["delays"].ctypes.data_as(C.POINTER(C.c_double))
+    net.weights = _fptr(w) if w is not None else None
+    for k in ("cutoff", "q", "gain", "line_gain"):
+        setattr(net, k, _fptr(arrs[k]) if k in arrs else None)
+    return per, (arrs, w)
+
+
 class Bank:
     """V voices of one compiled voice graph on the current HIP device."""
 
@@ -319,35 +354,9 @@ class Bank:
         [lines, taps] or [instances, lines, taps].  Any [instances, ..] array makes the parameters per instance.  The bank is created at
         `sample_rate` (default DEFAULT_SR), where every delay must be at least 128 samples."""
         V, N = int(instances), int(lines)
-        w = None if weights is None else np.asarray(weights, dtype=np.float32)
-        taps = 0 if w is None else int(w.shape[-1])
-        if w is not None and w.ndim == 1:
-            w = np.broadcast_to(w, (N, taps))
-        arrs = dict(delays=np.asarray(delays, dtype=np.float64))
-        if filter is not None:
-            if cutoff is None:
-                raise ValueError("fdn_network: a filter needs its cutoff")
-            arrs["cutoff"] = np.asarray(cutoff, dtype=np.float32)
-            if filter != "lowpole":
-                arrs["q"] = np.asarray(q, dtype=np.float32)
-                arrs["gain"] = np.asarray(gain, dtype=np.float32)
-        if line_gain is not None:
-            arrs["line_gain"] = np.asarray(line_gain, dtype=np.float32)
-        per = any(a.ndim == 2 for a in arrs.values()) or (w is not None and w.ndim == 3)
-        shape = (V, N) if per else (N,)
-        arrs = {k: np.ascontiguousarray(np.broadcast_to(a, shape), dtype=a.dtype) for k, a in arrs.items()}
-        if w is not None:
-            w = np.ascontiguousarray(np.broadcast_to(w, shape + (taps,)), dtype=np.float32)
         net = _lib.FdnNetwork()
-        net.lines, net.inputs, net.outputs, net.taps = N, int(inputs), int(outputs), taps
-        net.filter = _lib.FDN_FILTER_NONE if filter is None else _lib.FDN_FILTER_LOWPOLE if filter == "lowpole" else _lib.FDN_FILTER_SVF
-        net.svf_mode = 0 if filter in (None, "lowpole") else int(SVF_MODES[filter] if isinstance(filter, str) else filter)
-        net.place = {"line": _lib.FDN_IN_LINE, "loop": _lib.FDN_IN_LOOP}[place]
-        net.per_instance = 1 if per else 0
-        net.delays = arrs["delays"].ctypes.data_as(C.POINTER(C.c_double))
-        net.weights = _fptr(w) if w is not None else None
-        for k in ("cutoff", "q", "gain", "line_gain"):
-            setattr(net, k, _fptr(arrs[k]) if k in arrs else None)
+        net.lines, net.inputs, net.outputs = N, int(inputs), int(outputs)
+        _per, _keep = _line_net(net, "fdn_network", V, N, delays, weights, filter, place, cutoff, q, gain, line_gain)
         h = C.c_void_p()
         sr = float(sample_rate) if sample_rate is not None else _lib.DEFAULT_SR
         check(lib().fdsp_fdn_network_create_on(int(device), V, C.byref(net), sr, C.byref(h)))
@@ -376,41 +385,14 @@ class Bank:
         if d.ndim == 0:
             d = d[None]
         N = int(d.shape[-1])
-        w = None if weights is None else np.asarray(weights, dtype=np.float32)
-        taps = 0 if w is None else int(w.shape[-1])
-        if w is not None and w.ndim == 1:
-            w = np.broadcast_to(w, (N, taps))
-        arrs = dict(delays=d)
-        if filter is not None:
-            if cutoff is None:
-                raise ValueError("feedback_delay: a filter needs its cutoff")
-            arrs["cutoff"] = np.asarray(cutoff, dtype=np.float32)
-            if filter != "lowpole":
-                arrs["q"] = np.asarray(q, dtype=np.float32)
-                arrs["gain"] = np.asarray(gain, dtype=np.float32)
-        if line_gain is not None:
-            arrs["line_gain"] = np.asarray(line_gain, dtype=np.float32)
         og = None if outer_gain is None else np.asarray(outer_gain, dtype=np.float32)
         if og is not None and og.ndim > 1:
             raise ValueError("feedback_delay: outer_gain takes a scalar or [instances]")
-        per = any(a.ndim == 2 for a in arrs.values()) or (w is not None and w.ndim == 3) or (og is not None and og.ndim == 1)
-        shape = (V, N) if per else (N,)
-        arrs = {k: np.ascontiguousarray(np.broadcast_to(a, shape), dtype=a.dtype) for k, a in arrs.items()}
-        if w is not None:
-            w = np.ascontiguousarray(np.broadcast_to(w, shape + (taps,)), dtype=np.float32)
+        net = _lib.FeedbackDelay()
+        net.channels, net.reverse = N, 1 if reverse else 0
+        per, _keep = _line_net(net, "feedback_delay", V, N, d, weights, filter, place, cutoff, q, gain, line_gain, also_per=og is not None and og.ndim == 1)
         if og is not None:
             og = np.ascontiguousarray(np.broadcast_to(og, (V,) if per else (1,)), dtype=np.float32)
-        net = _lib.FeedbackDelay()
-        net.channels, net.taps = N, taps
-        net.filter = _lib.FDN_FILTER_NONE if filter is None else _lib.FDN_FILTER_LOWPOLE if filter == "lowpole" else _lib.FDN_FILTER_SVF
-        net.svf_mode = 0 if filter in (None, "lowpole") else int(SVF_MODES[filter] if isinstance(filter, str) else filter)
-        net.place = {"line": _lib.FDN_IN_LINE, "loop": _lib.FDN_IN_LOOP}[place]
-        net.reverse = 1 if reverse else 0
-        net.per_instance = 1 if per else 0
-        net.delays = arrs["delays"].ctypes.data_as(C.POINTER(C.c_double))
-        net.weights = _fptr(w) if w is not None else None
-        for k in ("cutoff", "q", "gain", "line_gain"):
-            setattr(net, k, _fptr(arrs[k]) if k in arrs else None)
         net.outer_gain = _fptr(og) if og is not None else None
         h = C.c_void_p()
         sr = float(sample_rate) if sample_rate is not None else _lib.DEFAULT_SR

@@ -1248,30 +1248,45 @@ int fdsp_fdn_create_on(int device, size_t instances, int lines, const double* de
 int fdsp_fdn_create(size_t instances, int lines, const double* delays, int taps, const float* weights, int inputs, int outputs, fdsp_bank** out) {
     return fdsp_fdn_create_on(-1, instances, lines, delays, taps, weights, inputs, outputs, out);
 }
+// The checks the two line-network constructors share (fdsp_fdn_network and fdsp_feedback_delay name these fields alike), in the order each
+// has always made them.  `who`: the constructor named in the messages; `line`, `loop`: its two forms' names; `lines`: its lines or channels.
+// A constructor's own checks are made by the caller; `after_taps` / `after_forms` is the message of one that failed (else NULL), reported
+// where that constructor's order has it.
+extern "C++" {
+template <class Net>
+static int line_check_net(const std::string& who, const Net* net, int lines, size_t instances, double sample_rate, const char* line, const char* loop,
+                          const char* after_taps, const char* after_forms) {
+    if (net->taps < 0 || net->taps > 3) return fail(FDSP_EINVAL, who + "taps takes 0 (no Fir node) .. 3");
+    if (after_taps) return fail(FDSP_EINVAL, who + after_taps);
+    if (net->filter < FDSP_FDN_FILTER_NONE || net->filter > FDSP_FDN_FILTER_SVF) return fail(FDSP_EINVAL, who + "filter takes FDSP_FDN_FILTER_NONE, _LOWPOLE or _SVF");
+    if (net->filter == FDSP_FDN_FILTER_SVF && (net->svf_mode < FDSP_SVF_LOWPASS || net->svf_mode > FDSP_SVF_HIGHSHELF))
+        return fail(FDSP_EINVAL, who + "svf_mode takes FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF");
+    if (net->place != FDSP_FDN_IN_LINE && net->place != FDSP_FDN_IN_LOOP)
+        return fail(FDSP_EINVAL, who + "place takes FDSP_FDN_IN_LINE (" + line + ") or FDSP_FDN_IN_LOOP (" + loop + ")");
+    if (net->place == FDSP_FDN_IN_LOOP && net->filter == FDSP_FDN_FILTER_NONE) return fail(FDSP_EINVAL, who + "the loop form (" + loop + ") needs a filter");
+    if (after_forms) return fail(FDSP_EINVAL, who + after_forms);
+    if (!net->delays) return fail(FDSP_EINVAL, who + "delays NULL");
+    if (net->taps > 0 && !net->weights) return fail(FDSP_EINVAL, who + "weights NULL");
+    const bool shelf = net->filter == FDSP_FDN_FILTER_SVF && net->svf_mode >= FDSP_SVF_BELL;
+    if (net->filter != FDSP_FDN_FILTER_NONE && !net->cutoff) return fail(FDSP_EINVAL, who + "the filter's cutoff is missing");
+    if (net->filter == FDSP_FDN_FILTER_SVF && !net->q) return fail(FDSP_EINVAL, who + "the FixedSvf's q is missing");
+    if (shelf && !net->gain) return fail(FDSP_EINVAL, who + "bell / lowshelf / highshelf need a gain");
+    if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, who + "sample_rate must be positive");
+    if (instances == 0) return fail(FDSP_EINVAL, who + "no instances");
+    const size_t M = (net->per_instance ? instances : 1) * (size_t)lines;
+    for (size_t i = 0; i < M; i++)
+        if (!(net->delays[i] >= 0.0) || !(net->delays[i] < 1e6)) return fail(FDSP_EINVAL, who + "a delay is negative or not a number (Delay::new asserts time >= 0)");
+    return FDSP_OK;
+}
+}  // extern "C++"
 int fdsp_fdn_network_create_on(int device, size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
     if (out) *out = nullptr;
     if (!net) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: network NULL");
     const int N = net->lines;
     if (N != 2 && N != 4 && N != 8 && N != 16 && N != 32) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: lines takes 2, 4, 8, 16 or 32 (FrameHadamard needs a power of two; the kernel holds at most 32 lines in registers)");
-    if (net->taps < 0 || net->taps > 3) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: taps takes 0 (no Fir node) .. 3");
-    if ((net->inputs != 1 && net->inputs != 2) || (net->outputs != 1 && net->outputs != 2))
-        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: inputs / outputs take 1 (split / join) or 2 (multisplit::<U2, _> / multijoin::<U2, _>)");
-    if (net->filter < FDSP_FDN_FILTER_NONE || net->filter > FDSP_FDN_FILTER_SVF) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: filter takes FDSP_FDN_FILTER_NONE, _LOWPOLE or _SVF");
-    if (net->filter == FDSP_FDN_FILTER_SVF && (net->svf_mode < FDSP_SVF_LOWPASS || net->svf_mode > FDSP_SVF_HIGHSHELF))
-        return fail(FDSP_EINVAL, "fdsp_fdn_network_create: svf_mode takes FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF");
-    if (net->place != FDSP_FDN_IN_LINE && net->place != FDSP_FDN_IN_LOOP) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: place takes FDSP_FDN_IN_LINE (fdn) or FDSP_FDN_IN_LOOP (fdn2)");
-    if (net->place == FDSP_FDN_IN_LOOP && net->filter == FDSP_FDN_FILTER_NONE) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the loop form (fdn2) needs a filter");
-    if (!net->delays) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays NULL");
-    if (net->taps > 0 && !net->weights) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: weights NULL");
-    const bool shelf = net->filter == FDSP_FDN_FILTER_SVF && net->svf_mode >= FDSP_SVF_BELL;
-    if (net->filter != FDSP_FDN_FILTER_NONE && !net->cutoff) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the filter's cutoff is missing");
-    if (net->filter == FDSP_FDN_FILTER_SVF && !net->q) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: the FixedSvf's q is missing");
-    if (shelf && !net->gain) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: bell / lowshelf / highshelf need a gain");
-    if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: sample_rate must be positive");
-    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: no instances");
-    const size_t M = (net->per_instance ? instances : 1) * (size_t)N;
-    for (size_t i = 0; i < M; i++)
-        if (!(net->delays[i] >= 0.0) || !(net->delays[i] < 1e6)) return fail(FDSP_EINVAL, "fdsp_fdn_network_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+    const char* io = (net->inputs != 1 && net->inputs != 2) || (net->outputs != 1 && net->outputs != 2)
+                         ? "inputs / outputs take 1 (split / join) or 2 (multisplit::<U2, _> / multijoin::<U2, _>)" : nullptr;
+    if (int rc = line_check_net("fdsp_fdn_network_create: ", net, N, instances, sample_rate, "fdn", "fdn2", io, nullptr)) return rc;
     return fx_bank_create(device, instances, sample_rate, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_fdn_network(instances, *net, sample_rate, s, fx); });
 }
 int fdsp_fdn_network_create(size_t instances, const fdsp_fdn_network* net, double sample_rate, fdsp_bank** out) {
@@ -1282,25 +1297,9 @@ int fdsp_feedback_delay_create_on(int device, size_t instances, const fdsp_feedb
     if (!net) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: network NULL");
     const int N = net->channels;
     if (N != 1 && N != 2) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: channels takes 1 or 2 (the feedback delay kernel holds one or two lines)");
-    if (net->taps < 0 || net->taps > 3) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: taps takes 0 (no Fir node) .. 3");
-    if (net->filter < FDSP_FDN_FILTER_NONE || net->filter > FDSP_FDN_FILTER_SVF) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: filter takes FDSP_FDN_FILTER_NONE, _LOWPOLE or _SVF");
-    if (net->filter == FDSP_FDN_FILTER_SVF && (net->svf_mode < FDSP_SVF_LOWPASS || net->svf_mode > FDSP_SVF_HIGHSHELF))
-        return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: svf_mode takes FDSP_SVF_LOWPASS .. FDSP_SVF_HIGHSHELF");
-    if (net->place != FDSP_FDN_IN_LINE && net->place != FDSP_FDN_IN_LOOP) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: place takes FDSP_FDN_IN_LINE (feedback) or FDSP_FDN_IN_LOOP (feedback2)");
-    if (net->place == FDSP_FDN_IN_LOOP && net->filter == FDSP_FDN_FILTER_NONE) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the loop form (feedback2) needs a filter");
-    if (net->place == FDSP_FDN_IN_LOOP && net->outer_gain) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the loop form (feedback2) has no outer gain (the gain belongs to y: line_gain)");
-    if (net->reverse && N != 2) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: reverse() needs two channels");
-    if (!net->delays) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: delays NULL");
-    if (net->taps > 0 && !net->weights) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: weights NULL");
-    const bool shelf = net->filter == FDSP_FDN_FILTER_SVF && net->svf_mode >= FDSP_SVF_BELL;
-    if (net->filter != FDSP_FDN_FILTER_NONE && !net->cutoff) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the filter's cutoff is missing");
-    if (net->filter == FDSP_FDN_FILTER_SVF && !net->q) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: the FixedSvf's q is missing");
-    if (shelf && !net->gain) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: bell / lowshelf / highshelf need a gain");
-    if (!(sample_rate > 0.0)) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: sample_rate must be positive");
-    if (instances == 0) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: no instances");
-    const size_t M = (net->per_instance ? instances : 1) * (size_t)N;
-    for (size_t i = 0; i < M; i++)
-        if (!(net->delays[i] >= 0.0) || !(net->delays[i] < 1e6)) return fail(FDSP_EINVAL, "fdsp_feedback_delay_create: a delay is negative or not a number (Delay::new asserts time >= 0)");
+    const char* own = net->place == FDSP_FDN_IN_LOOP && net->outer_gain ? "the loop form (feedback2) has no outer gain (the gain belongs to y: line_gain)"
+                      : net->reverse && N != 2                          ? "reverse() needs two channels" : nullptr;
+    if (int rc = line_check_net("fdsp_feedback_delay_create: ", net, N, instances, sample_rate, "feedback", "feedback2", nullptr, own)) return rc;
     return fx_bank_create(device, instances, sample_rate, out, [&](hipStream_t s, FxPtr* fx) { return fd::fx_feedback_delay(instances, *net, sample_rate, s, fx); });
 }
 int fdsp_feedback_delay_create(size_t instances, const fdsp_feedback_delay* net, double sample_rate, fdsp_bank** out) {

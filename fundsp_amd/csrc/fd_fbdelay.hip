@@ -4,42 +4,19 @@
 
 #include "fd_fbdelay.hpp"
 #include "fd_fdn_frames.hpp"
+#include "fd_line_table.hpp"   // (fd_nodes.hpp: SvfCore, host + device)
 #include "fd_opts.hpp"
-#include "fd_math.hpp"
-#include "fd_nodes.hpp"   // svf_coefs, SvfCore (host + device)
 
 namespace fd {
 
-int fb_make_table(const FbDesc& d, size_t instances, double sample_rate, std::vector<FbInst>& tab, FbConst* c) {
-    const size_t P = d.per_instance ? instances : 1;
-    const int N = d.lines;
-    tab.assign(P, FbInst{});
-    const float sr = (float)sample_rate;   // the filters' coefficients are computed in F = f32 (filter.rs:35-38, svf.rs:236-239)
-    int maxlen = 0, shortest = 1 << 30;
-    for (size_t p = 0; p < P; p++) {
-        FbInst& e = tab[p];
-        for (int k = 0; k < N; k++) {
-            const size_t i = p * N + k;
-            const double samples = std::round(d.delay[i] * sample_rate);   // Delay::new / set_sample_rate (delay.rs:104-112)
-            if (samples + 1.0 > (double)(1 << 18)) return -1;
-            e.len[k] = (int)samples + 1;
-            maxlen = e.len[k] > maxlen ? e.len[k] : maxlen;
-            shortest = e.len[k] - 1 < shortest ? e.len[k] - 1 : shortest;
-            for (int j = 0; j < d.taps; j++) e.w[j][k] = d.w[i * d.taps + j];
-            if (d.filter == FDNX_LOWPOLE) {
-                e.co[0][k] = expf_musl(-F32_TAU * d.cutoff[i] / sr);   // Lowpole::set_cutoff (filter.rs:35-38)
-                e.co[1][k] = 1.0f - e.co[0][k];                         // (1 - coeff) as tick computes it (:65)
-            } else if (d.filter == FDNX_SVF) {
-                const SvfCoefs s = svf_coefs(d.svf_mode, sr, d.cutoff[i], d.q[i], d.gain.empty() ? 1.0f : d.gain[i]);
-                e.co[0][k] = s.a1; e.co[1][k] = s.a2; e.co[2][k] = s.a3; e.co[3][k] = s.m0; e.co[4][k] = s.m1; e.co[5][k] = s.m2;
-            }
-            e.g[k] = d.has_gain ? d.line_gain[i] : 1.0f;
-        }
-        if (N == 1) e.len[1] = e.len[0];
-        e.outer = d.has_outer ? d.outer[p] : 1.0f;
+int fb_make_table(const FdnxDesc& d, size_t instances, double sample_rate, std::vector<FbInst>& tab, FbConst* c) {
+    const LineSpan span = line_table_fill(d, instances, sample_rate, tab);
+    if (span.shortest < 0) return -1;
+    const int N = d.lines, cap = line_ring_cap(span.longest);
+    for (size_t p = 0; p < tab.size(); p++) {
+        if (N == 1) tab[p].len[1] = tab[p].len[0];
+        tab[p].outer = d.has_outer ? d.outer[p] : 1.0f;
     }
-    int cap = 256;
-    while (cap < maxlen) cap <<= 1;
     *c = FbConst{};
     c->lines = N;
     c->taps = d.taps;
@@ -52,7 +29,7 @@ int fb_make_table(const FbDesc& d, size_t instances, double sample_rate, std::ve
     c->ring_stride = (size_t)N * ((size_t)cap + 64);
     c->tab_stride = d.per_instance ? 1 : 0;
     c->tab = nullptr;
-    return shortest;
+    return span.shortest - 1;
 }
 
 // the lines' parameters of this kernel: a row of the device table (wave-uniform: scalar loads)
@@ -128,33 +105,11 @@ __global__ __launch_bounds__(256) void k_fb_frames(FbConst c, FdnxState s, size_
             for (int k = 0; k < NL; k++) o[k] = f[k];
         }
         if (filter != FDNX_NONE) {
-            // lane = frame -> lane = channel: each of lanes 0 .. NL-1 runs its channel's 64-step recurrence in registers.  The same walk stands
-            // in k_fdn_frames_filtered (fd_fdnx.hip): a fix to one is a fix to both.  Not a shared step: that kernel's code object stays as it is.
+            // lane = frame -> lane = channel: each of lanes 0 .. NL-1 runs its channel's 64-step recurrence in registers
 #pragma unroll
             for (int k = 0; k < NL; k++) fbr[k * HS + 4 + lane] = f[k];
             fdn_wave_sync();
-            if (serial) {
-                float* row = fbr + lane * HS + 4;
-                if (filter == FDNX_SVF) {   // FixedSvf::tick, the reference's operations in the reference's order (svf.rs:995-1006)
-#pragma unroll 8
-                    for (int n = 0; n < 64; n++) {
-                        const float i1 = svf.ic1eq, i2 = svf.ic2eq;
-                        row[n] = svf.tick(row[n]);
-                        if (n >= size) { svf.ic1eq = i1; svf.ic2eq = i2; }   // a ragged last block: the filter stops where the launch does
-                    }
-                } else {                    // Lowpole::tick: value = (1 - coeff) * x + coeff * value (filter.rs:64-66)
-                    float v = svf.ic1eq;
-#pragma unroll 8
-                    for (int n = 0; n < 64; n++) {
-                        const float a = pomc * row[n];
-                        const float b = pc * v;
-                        const float nv = a + b;
-                        v = n < size ? nv : v;
-                        row[n] = nv;
-                    }
-                    svf.ic1eq = v;
-                }
-            }
+            if (serial) fdn_filter_walk(fbr + lane * HS + 4, filter == FDNX_SVF, svf, pc, pomc, size);
             fdn_wave_sync();
 #pragma unroll
             for (int k = 0; k < NL; k++) f[k] = fbr[k * HS + 4 + lane];

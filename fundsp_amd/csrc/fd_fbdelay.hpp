@@ -14,7 +14,7 @@
 //
 // Every delay is at least two blocks long, so all ring reads of a 64-frame block are known at its head: the kernel is the block steps of
 // fd_fdn_frames.hpp with the permutation and the outer gain where the Hadamard networks have their butterflies, and the filter walked by
-// lanes 0 .. N-1 over the LDS row as in fd_fdnx.hip.  Parameters live in a device table of FbInst rows: one for the bank or one per instance.
+// lanes 0 .. N-1 over the LDS row (fdn_filter_walk, as in fd_fdnx.hip).  Parameters live in a device table of FbInst rows: one for the bank or one per instance.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 
 #include <vector>
 
-#include "fd_fdnx.hpp"   // FDNX_NONE .. FDNX_IN_LOOP, FdnxState, FdnBus
+#include "fd_fdnx.hpp"   // FDNX_NONE .. FDNX_IN_LOOP, FdnxDesc, FdnxState, FdnBus
 
 namespace fd {
 
@@ -46,21 +46,10 @@ struct FbConst {
     const FbInst* tab;
 };
 
-struct FbDesc {                   // host side: the network as created (P = per_instance ? instances : 1 parameter sets)
-    int lines = 0, taps = 0;
-    int filter = FDNX_NONE, svf_mode = 0, place = FDNX_IN_LINE, per_instance = 0, has_gain = 0, has_outer = 0, reverse = 0;
-    std::vector<double> delay;    // [P][lines] seconds
-    std::vector<float> w;         // [P][lines][taps]
-    std::vector<float> cutoff, q, gain, line_gain;   // [P][lines] (empty where the network has none)
-    std::vector<float> outer;     // [P]
-};
-
-// host: the parameter table at `sample_rate` (instances rows, or 1) and the constants; returns the shortest delay in samples over all
-// instances and channels (the caller applies the two-block rule) and -1 when a ring would exceed 2^18 slots
-int fb_make_table(const FbDesc& d, size_t instances, double sample_rate, std::vector<FbInst>& tab, FbConst* c);
-inline void fb_launch_reset(const FbConst& c, const FdnxState& s, size_t instances, hipStream_t stream) {
-    fdn_launch_reset_state(s, s.s1, s.s2, c.ring_stride, instances, stream);   // Feedback(2)::reset: fd_fdn.hpp's kernel, with the filters
-}
+// host: the parameter table at `sample_rate` (instances rows, or 1) and the constants, from the description the two families share (FdnxDesc,
+// lines = channels); returns the shortest delay in samples over all instances and channels (the caller applies the two-block rule) and -1
+// when a ring would exceed 2^18 slots.  Reset is fdnx_launch_reset.
+int fb_make_table(const FdnxDesc& d, size_t instances, double sample_rate, std::vector<FbInst>& tab, FbConst* c);
 void fb_launch_render(const FbConst& c, const FdnxState& s, size_t instances, const float* in, float* out, size_t T, size_t fstride, int layout,
                       hipStream_t stream, const FdnBus& bus = FdnBus());
 

@@ -1,5 +1,6 @@
-// fd_fdn_frames.hpp -- the steps of a 64-frame block that the lane = FRAME Hadamard kernels share: k_fdn_render_frames and
-// k_fdn_frames_generic (fd_fdn.hip) and k_fdn_frames_filtered (fd_fdnx.hip); device functions, and at the end the host-side launch ladder.  One wave renders one instance, lane = frame,
+// fd_fdn_frames.hpp -- the steps of a 64-frame block that the lane = FRAME feedback kernels share: k_fdn_render_frames and
+// k_fdn_frames_generic (fd_fdn.hip), k_fdn_frames_filtered (fd_fdnx.hip) and k_fb_frames (fd_fbdelay.hip); device functions, and at the end
+// the host-side launch ladder.  One wave renders one instance, lane = frame,
 // the lines of the network in registers; every delay is at least two blocks (128 samples), so all ring reads of a block are known at its head.
 // These are the steps that have to match the reference bit for bit (the order of the FIR terms, the butterfly stage order, tick against
 // process in the joins, the mirror zone): each is written ONCE here, and a kernel is a sequence of them with its own parts in between (the
@@ -94,6 +95,34 @@ __device__ __forceinline__ void fdn_fir_lines(float (&o)[NL], const float (&d)[N
     }
 #pragma unroll
     for (int k = 0; k < NL; k++) o[k] = fdn_fir<K>(hist + k * HS + lane, d[k], p.w(0, k), p.w(1, k), p.w(2, k));
+}
+
+// The one time-serial step of the filtered kernels (k_fdn_frames_filtered, k_fb_frames): a serial lane (lane = line) walks its line's 64
+// frames through the line's filter, in place in the LDS `row`, eight frames at a time: the loads do not depend on the recurrence and run
+// ahead of it, and the 64 frames never sit in registers at once.  `svf` is the lane's SvfCore (fd_nodes.hpp; a template parameter so that
+// this header needs no node), which also carries the Lowpole's value in ic1eq; pc, pomc: the Lowpole's coeff and 1 - coeff.  A ragged last
+// block: the filter stops where the launch does (its state after frame size - 1).
+template <class Svf>
+__device__ __forceinline__ void fdn_filter_walk(float* row, bool is_svf, Svf& svf, float pc, float pomc, int size) {
+    if (is_svf) {   // FixedSvf::tick, the reference's operations in the reference's order (svf.rs:995-1006)
+#pragma unroll 8
+        for (int n = 0; n < 64; n++) {
+            const float i1 = svf.ic1eq, i2 = svf.ic2eq;
+            row[n] = svf.tick(row[n]);
+            if (n >= size) { svf.ic1eq = i1; svf.ic2eq = i2; }
+        }
+    } else {        // Lowpole::tick: value = (1 - coeff) * x + coeff * value (filter.rs:64-66)
+        float v = svf.ic1eq;
+#pragma unroll 8
+        for (int n = 0; n < 64; n++) {
+            const float a = pomc * row[n];
+            const float b = pc * v;
+            const float nv = a + b;
+            v = n < size ? nv : v;
+            row[n] = nv;
+        }
+        svf.ic1eq = v;
+    }
 }
 
 // FrameHadamard feedback.rs:35-57: in-place butterflies h = 1, 2, 4, .. < NL, (x, y) -> (x + y, x - y), over every NL-line network of the

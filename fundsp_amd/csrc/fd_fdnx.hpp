@@ -47,12 +47,14 @@ struct FdnxConst {
     const FdnxInst* tab;
 };
 
-struct FdnxDesc {                 // host side: the network as created (P = per_instance ? instances : 1 parameter sets)
-    int lines = 0, taps = 0, nin = 1, nout = 1;
+struct FdnxDesc {                 // host side: a line network as created (P = per_instance ? instances : 1 parameter sets), of this family
+    int lines = 0, taps = 0, nin = 1, nout = 1;   // or of fd_fbdelay.hpp's (nin = nout = lines there)
     int filter = FDNX_NONE, svf_mode = 0, place = FDNX_IN_LINE, per_instance = 0, has_gain = 0;
+    int has_outer = 0, reverse = 0;   // the feedback delay banks' outer gain and reverse()
     std::vector<double> delay;    // [P][lines] seconds
     std::vector<float> w;         // [P][lines][taps]
     std::vector<float> cutoff, q, gain, line_gain;   // [P][lines] (empty where the network has none)
+    std::vector<float> outer;     // [P] (has_outer)
 };
 
 struct FdnxState : FdnState {     // the rings, the write position, the Fir carry and the feedback value of fd_fdn.hpp, and the filters' state
@@ -61,10 +63,12 @@ struct FdnxState : FdnState {     // the rings, the write position, the Fir carr
 };
 
 // host: the parameter table at `sample_rate` (instances entries, or 1) and the constants; returns the shortest delay in samples over all
-// instances and lines (the caller applies the two-block rule) and -1 when a ring would exceed 2^18 slots
+// instances and lines (the caller applies the two-block rule) and -1 when a ring would exceed 2^18 slots (the per-line part of the table
+// is fd_line_table.hpp's, for this family and the feedback delay banks)
 int fdnx_make_table(const FdnxDesc& d, size_t instances, double sample_rate, std::vector<FdnxInst>& tab, FdnxConst* c);
-inline void fdnx_launch_reset(const FdnxConst& c, const FdnxState& s, size_t instances, hipStream_t stream) {
-    fdn_launch_reset_state(s, s.s1, s.s2, c.ring_stride, instances, stream);   // Feedback(2)::reset: fd_fdn.hpp's kernel, with the filters
+// Feedback(2)::reset of either family (`ring_stride`: its constants'): fd_fdn.hpp's kernel, with the filters
+inline void fdnx_launch_reset(size_t ring_stride, const FdnxState& s, size_t instances, hipStream_t stream) {
+    fdn_launch_reset_state(s, s.s1, s.s2, ring_stride, instances, stream);
 }
 void fdnx_launch_render(const FdnxConst& c, const FdnxState& s, size_t instances, const float* in, float* out, size_t T, size_t fstride,
                         int layout, int tick_mode, hipStream_t stream, const FdnBus& bus = FdnBus());

@@ -357,88 +357,85 @@ class Reverb3Fx final : public NetFx {
     Rv3State st_{};
 };
 
-// filtered / per-instance networks (fd_fdnx.hpp): the table and the lines for a sample rate.  The new rings start empty (Delay::set_sample_rate,
-// delay.rs:105-113), the coefficients follow the rate (filter.rs:58-61, svf.rs:989-992), and the Fir carry, the filter states and the feedback
-// value stay (fir.rs:52-54, feedback.rs:125-127, 254-257)
-class FdnxFx final : public NetFx {
-  public:
-    FdnxFx(const FdnxDesc& d, size_t V) : NetFx(V, "network"), d_(d) { tables_ = 1; }
-    ~FdnxFx() override { free_bufs(bufs()); }
-    hipError_t reset(hipStream_t s) override { fdnx_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
-
-  private:
-    int configure(double sr, hipStream_t s) override {
-        std::vector<FdnxInst> tab;
-        FdnxConst c;
-        const int shortest = fdnx_make_table(d_, V_, sr, tab, &c);
-        if (shortest < 0) return api_fail(FDSP_EINVAL, "fdsp_fdn_network_create: delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)");
-        if (shortest < 128)
-            return api_fail(FDSP_EINVAL, "fdsp_fdn_network_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
-        FdnxState st{};
-        hipError_t e = alloc_bufs(bufs(c, st));
-        if (e == hipSuccess && (e = hipMemcpyAsync((void*)c.tab, tab.data(), tab.size() * sizeof(FdnxInst), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st));
-        if (e != hipSuccess) return hip_fail(e, "fdsp_fdn_network_create buffers");
-        fdnx_launch_reset(c, st, V_, s);
-        carry_and_free(bufs(c, st), bufs(c_, st_), 3, s);   // v1, v2, fb, s1, s2 (and the stream drains before `tab` goes)
-        c_ = c; st_ = st; sr_ = sr;
-        nin_ = c.nin; nout_ = c.nout;
-        return launch_error();
+// The line networks -- filtered / per-instance Hadamard networks (fd_fdnx.hpp) and feedback delay banks (fd_fbdelay.hpp): one life cycle
+// around one description (FdnxDesc).  What a family supplies: its table row and constants, how to make them, when a table is refused and
+// in which words, its inputs and outputs, and its launch.
+struct FdnxFamily {
+    using Row = FdnxInst;
+    using Const = FdnxConst;
+    static constexpr const char* what = "network";
+    static constexpr const char* who = "fdsp_fdn_network_create";
+    static constexpr const char* too_long = ": delays of more than 2^18 samples (too long for the lane-per-frame kernel at this sample rate)";
+    static int make_table(const FdnxDesc& d, size_t V, double sr, std::vector<Row>& tab, Const* c) { return fdnx_make_table(d, V, sr, tab, c); }
+    static bool refused(int shortest, const Const&) { return shortest < 0; }
+    static int nin(const Const& c) { return c.nin; }
+    static int nout(const Const& c) { return c.nout; }
+    static void launch(const Const& c, const FdnxState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout, int tick,
+                       hipStream_t s, const FdnBus& bus) {
+        fdnx_launch_render(c, st, V, in, out, T, fstride, layout, tick, s, bus);
     }
-    Bufs bufs(FdnxConst& c, FdnxState& st) const {
-        const size_t n = V_;
-        return {{(void**)&c.tab, (c.tab_stride ? n : 1) * sizeof(FdnxInst)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)},
-                {(void**)&st.wpos, n * sizeof(int)}, {(void**)&st.v1, n * 32 * sizeof(float)}, {(void**)&st.v2, n * 32 * sizeof(float)},
-                {(void**)&st.fb, n * 32 * sizeof(float)}, {(void**)&st.s1, n * 32 * sizeof(float)}, {(void**)&st.s2, n * 32 * sizeof(float)}};
+};
+struct FbFamily {
+    using Row = FbInst;
+    using Const = FbConst;
+    static constexpr const char* what = "feedback_delay";
+    static constexpr const char* who = "fdsp_feedback_delay_create";
+    static constexpr const char* too_long = ": no ring may exceed 2^18 slots (a delay too long for the lane-per-frame kernel at this sample rate)";
+    static int make_table(const FdnxDesc& d, size_t V, double sr, std::vector<Row>& tab, Const* c) { return fb_make_table(d, V, sr, tab, c); }
+    static bool refused(int shortest, const Const& c) { return shortest < 0 || c.cap > (1 << 18); }
+    static int nin(const Const& c) { return c.lines; }
+    static int nout(const Const& c) { return c.lines; }
+    // Feedback::process is the per-sample tick and these graphs have no join: one arithmetic for both modes
+    static void launch(const Const& c, const FdnxState& st, size_t V, const float* in, float* out, size_t T, size_t fstride, int layout, int,
+                       hipStream_t s, const FdnBus& bus) {
+        fb_launch_render(c, st, V, in, out, T, fstride, layout, s, bus);
     }
-    Bufs bufs() override { return bufs(c_, st_); }
-    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<FdnxFx>(d_, V_); }
-    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) override { fdnx_launch_render(c_, st_, V_, in, out, T, fstride, layout, tick, s, bus_); }
-
-    FdnxDesc d_;
-    FdnxConst c_{};
-    FdnxState st_{};
 };
 
-// feedback delay banks (fd_fbdelay.hpp): FdnxFx's life cycle around the identity-feedback kernel.  The new rings start empty, the coefficients
-// follow the rate, and the Fir carry, the filter states and the feedback value stay
-class FeedbackDelayFx final : public NetFx {
+// the table and the lines for a sample rate.  The new rings start empty (Delay::set_sample_rate, delay.rs:105-113), the coefficients follow
+// the rate (filter.rs:58-61, svf.rs:989-992), and the Fir carry, the filter states and the feedback value stay (fir.rs:52-54,
+// feedback.rs:125-127, 254-257)
+template <class F>
+class LineFx final : public NetFx {
+    using Row = typename F::Row;
+    using Const = typename F::Const;
+
   public:
-    FeedbackDelayFx(const FbDesc& d, size_t V) : NetFx(V, "feedback_delay"), d_(d) { tables_ = 1; }
-    ~FeedbackDelayFx() override { free_bufs(bufs()); }
-    hipError_t reset(hipStream_t s) override { fb_launch_reset(c_, st_, V_, s); return hipGetLastError(); }
+    LineFx(const FdnxDesc& d, size_t V) : NetFx(V, F::what), d_(d) { tables_ = 1; }
+    ~LineFx() override { free_bufs(bufs()); }
+    hipError_t reset(hipStream_t s) override { fdnx_launch_reset(c_.ring_stride, st_, V_, s); return hipGetLastError(); }
 
   private:
     int configure(double sr, hipStream_t s) override {
-        std::vector<FbInst> tab;
-        FbConst c;
-        const int shortest = fb_make_table(d_, V_, sr, tab, &c);
-        if (shortest < 0 || c.cap > (1 << 18))
-            return api_fail(FDSP_EINVAL, "fdsp_feedback_delay_create: no ring may exceed 2^18 slots (a delay too long for the lane-per-frame kernel at this sample rate)");
+        const std::string who = F::who;
+        std::vector<Row> tab;
+        Const c;
+        const int shortest = F::make_table(d_, V_, sr, tab, &c);
+        if (F::refused(shortest, c)) return api_fail(FDSP_EINVAL, who + F::too_long);
         if (shortest < 128)
-            return api_fail(FDSP_EINVAL, "fdsp_feedback_delay_create: every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
+            return api_fail(FDSP_EINVAL, who + ": every delay must be at least 128 samples at the bank's sample rate (two blocks: the lane-per-frame kernel's rule)");
         FdnxState st{};
         hipError_t e = alloc_bufs(bufs(c, st));
-        if (e == hipSuccess && (e = hipMemcpyAsync((void*)c.tab, tab.data(), tab.size() * sizeof(FbInst), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st));
-        if (e != hipSuccess) return hip_fail(e, "fdsp_feedback_delay_create buffers");
-        fb_launch_reset(c, st, V_, s);
+        if (e == hipSuccess && (e = hipMemcpyAsync((void*)c.tab, tab.data(), tab.size() * sizeof(Row), hipMemcpyHostToDevice, s)) != hipSuccess) free_bufs(bufs(c, st));
+        if (e != hipSuccess) return hip_fail(e, who + " buffers");
+        fdnx_launch_reset(c.ring_stride, st, V_, s);
         carry_and_free(bufs(c, st), bufs(c_, st_), 3, s);   // v1, v2, fb, s1, s2 (and the stream drains before `tab` goes)
         c_ = c; st_ = st; sr_ = sr;
-        nin_ = nout_ = c.lines;
+        nin_ = F::nin(c); nout_ = F::nout(c);
         return launch_error();
     }
-    Bufs bufs(FbConst& c, FdnxState& st) const {
+    Bufs bufs(Const& c, FdnxState& st) const {
         const size_t n = V_;
-        return {{(void**)&c.tab, (c.tab_stride ? n : 1) * sizeof(FbInst)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)},
+        return {{(void**)&c.tab, (c.tab_stride ? n : 1) * sizeof(Row)}, {(void**)&st.rings, n * c.ring_stride * sizeof(float)},
                 {(void**)&st.wpos, n * sizeof(int)}, {(void**)&st.v1, n * 32 * sizeof(float)}, {(void**)&st.v2, n * 32 * sizeof(float)},
                 {(void**)&st.fb, n * 32 * sizeof(float)}, {(void**)&st.s1, n * 32 * sizeof(float)}, {(void**)&st.s2, n * 32 * sizeof(float)}};
     }
     Bufs bufs() override { return bufs(c_, st_); }
-    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<FeedbackDelayFx>(d_, V_); }
-    // Feedback::process is the per-sample tick and these graphs have no join: one arithmetic for both modes
-    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int, hipStream_t s) override { fb_launch_render(c_, st_, V_, in, out, T, fstride, layout, s, bus_); }
+    std::unique_ptr<NetFx> fresh() const override { return std::make_unique<LineFx>(d_, V_); }
+    void launch(const float* in, float* out, size_t T, size_t fstride, int layout, int tick, hipStream_t s) override { F::launch(c_, st_, V_, in, out, T, fstride, layout, tick, s, bus_); }
 
-    FbDesc d_;
-    FbConst c_{};
+    FdnxDesc d_;
+    Const c_{};
     FdnxState st_{};
 };
 
@@ -656,31 +653,31 @@ int fx_reverb3_stereo(size_t instances, double time, double diffusion, int svf_m
     const Rv3Filter f{svf_mode < 0 ? 0 : 1, svf_mode < 0 ? 0 : svf_mode, cutoff, q, gain};
     return make_net(std::make_unique<Reverb3Fx>(time, diffusion, f, instances), FDSP_DEFAULT_SR, s, out);
 }
-int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t s, std::unique_ptr<FxBank>* out) {
-    FdnxDesc d{net.lines, net.taps, net.inputs, net.outputs, net.filter, net.svf_mode, net.place, net.per_instance ? 1 : 0, net.line_gain ? 1 : 0};
-    const size_t M = (d.per_instance ? instances : 1) * (size_t)net.lines;
+// the [P][lines] arrays of a C description (fdsp_fdn_network, fdsp_feedback_delay: the same fields) into `d`, whose lines are set
+template <class Net>
+static void line_desc(FdnxDesc& d, const Net& net, size_t instances) {
+    d.taps = net.taps; d.filter = net.filter; d.svf_mode = net.svf_mode; d.place = net.place;
+    d.per_instance = net.per_instance ? 1 : 0; d.has_gain = net.line_gain ? 1 : 0;
+    const size_t M = (d.per_instance ? instances : 1) * (size_t)d.lines;
     d.delay.assign(net.delays, net.delays + M);
     if (net.taps > 0) d.w.assign(net.weights, net.weights + M * net.taps);
     if (net.filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net.cutoff, net.cutoff + M);
     if (net.filter == FDSP_FDN_FILTER_SVF) d.q.assign(net.q, net.q + M);
     if (net.filter == FDSP_FDN_FILTER_SVF && net.svf_mode >= FDSP_SVF_BELL) d.gain.assign(net.gain, net.gain + M);
     if (d.has_gain) d.line_gain.assign(net.line_gain, net.line_gain + M);
-    return make_net(std::make_unique<FdnxFx>(d, instances), sample_rate, s, out);
 }
-
+int fx_fdn_network(size_t instances, const fdsp_fdn_network& net, double sample_rate, hipStream_t s, std::unique_ptr<FxBank>* out) {
+    FdnxDesc d;
+    d.lines = net.lines; d.nin = net.inputs; d.nout = net.outputs;
+    line_desc(d, net, instances);
+    return make_net(std::make_unique<LineFx<FdnxFamily>>(d, instances), sample_rate, s, out);
+}
 int fx_feedback_delay(size_t instances, const fdsp_feedback_delay& net, double sample_rate, hipStream_t s, std::unique_ptr<FxBank>* out) {
-    FbDesc d;
-    d.lines = net.channels; d.taps = net.taps; d.filter = net.filter; d.svf_mode = net.svf_mode; d.place = net.place;
-    d.per_instance = net.per_instance ? 1 : 0; d.has_gain = net.line_gain ? 1 : 0; d.has_outer = net.outer_gain ? 1 : 0; d.reverse = net.reverse ? 1 : 0;
-    const size_t P = d.per_instance ? instances : 1, M = P * (size_t)net.channels;
-    d.delay.assign(net.delays, net.delays + M);
-    if (net.taps > 0) d.w.assign(net.weights, net.weights + M * net.taps);
-    if (net.filter != FDSP_FDN_FILTER_NONE) d.cutoff.assign(net.cutoff, net.cutoff + M);
-    if (net.filter == FDSP_FDN_FILTER_SVF) d.q.assign(net.q, net.q + M);
-    if (net.filter == FDSP_FDN_FILTER_SVF && net.svf_mode >= FDSP_SVF_BELL) d.gain.assign(net.gain, net.gain + M);
-    if (d.has_gain) d.line_gain.assign(net.line_gain, net.line_gain + M);
-    if (d.has_outer) d.outer.assign(net.outer_gain, net.outer_gain + P);
-    return make_net(std::make_unique<FeedbackDelayFx>(d, instances), sample_rate, s, out);
+    FdnxDesc d;
+    d.lines = net.channels; d.has_outer = net.outer_gain ? 1 : 0; d.reverse = net.reverse ? 1 : 0;
+    line_desc(d, net, instances);
+    if (d.has_outer) d.outer.assign(net.outer_gain, net.outer_gain + (d.per_instance ? instances : 1));
+    return make_net(std::make_unique<LineFx<FbFamily>>(d, instances), sample_rate, s, out);
 }
 
 // the frame ring of a bank: at least 8 slots, at most a 64 Ki-sample chunk, within 256 MiB where the bank is large

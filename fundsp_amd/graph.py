@@ -604,26 +604,24 @@ def _parse_type(t):
     return node()
 
 
-def fdn_plan(g):
-    """The arguments of fdsp_fdn_create when `g` is the Hadamard feedback delay network the prelude documents (prelude.rs:1323-1345,
-    the "Mono Reverb" example :1334) --
+# ---- what the recognisers of the line networks share (fdn_plan, fdn_network_plan, feedback_delay_plan): a network is N lines
+# `delay [>> fir] [>> F] [* g]`, the filter in the line or in the loop; a plan function is its family's grammar around these ----
+def _flat_chain(n, path, out):
+    """a Pipe chain of a parsed type, left to right, as (node, parameter path) elements; `x * scalar` as a ("*", path) element behind x's"""
+    if n[0] == "Pipe" and len(n[1]) == 2:
+        _flat_chain(n[1][0], path + (0,), out)
+        _flat_chain(n[1][1], path + (1,), out)
+    elif n[0] == "Unop" and len(n[1]) == 2 and n[1][1][0] == "UMulScalar":
+        _flat_chain(n[1][0], path + (0,), out)
+        out.append((("*", []), path))
+    else:
+        out.append((n, path))
+    return out
 
-        split(N) | multisplit(2, N/2)  >>  fdn(stacki(N, lambda i: delay(t_i) >> fir(w..)))  >>  join(N) | multijoin(2, N/2)
 
-    with N in 2, 4, 8, 16, 32, one to three FIR weights shared by all lines, and every parameter a scalar (the same network in every
-    instance) -- else None.  Such a graph renders through the lane-per-frame FDN kernel (one wave per instance, the lines in registers,
-    coalesced ring rows) instead of lane-per-voice; Bank.from_graph takes that route when every delay exceeds two blocks."""
-    name, kids = _parse_type(g.type)
-    chain = []
-
-    def flat(n, path):  # the Pipe chain, left to right, with the parameter path of every element
-        if n[0] == "Pipe" and len(n[1]) == 2:
-            flat(n[1][0], path + (0,))
-            flat(n[1][1], path + (1,))
-        else:
-            chain.append((n, path))
-
-    flat((name, kids), ())
+def _split_join(g):
+    """`split(N) | multisplit(2, N/2)  >>  X  >>  join(N) | multijoin(2, N/2)` -> (X, X's parameter path, inputs, outputs, N), else None"""
+    chain = _flat_chain(_parse_type(g.type), (), [])
     if len(chain) != 3:
         return None
     (sp, _), (fb, fpath), (jn, _) = chain
@@ -640,19 +638,119 @@ def fdn_plan(g):
             nout, n_out = 2, 2 * int(jn[1][1][0])
         else:
             return None
+    except (IndexError, ValueError):
+        return None
+    return (fb, fpath, nin, nout, n_in) if n_in == n_out else None
+
+
+def _line_head(xs):
+    """`delay(t) [>> fir(w..)]` at the head of a line's elements -> (taps, elements taken), taps 0 without a Fir node; else None"""
+    kinds = [e[0][0] for e in xs]
+    if not kinds or kinds[0] != "Delay":
+        return None
+    if len(kinds) == 1 or kinds[1] != "Fir":
+        return 0, 1
+    try:
+        taps = int(xs[1][0][1][0][0])
+    except (IndexError, ValueError):
+        return None
+    return (taps, 2) if 1 <= taps <= 3 else None
+
+
+def _is_filter(e):
+    return e[0][0] == "FixedSvf" or (e[0][0] == "OnePole" and [c[0] for c in e[0][1]] == ["OP_LOWPOLE", "1"])
+
+
+def _line_tail(tail):
+    """`[F] [* g]` at the head of `tail` -> (index of F or None, index of `* g` or None, elements taken)"""
+    filt = gain = None
+    pos = 0
+    if pos < len(tail) and _is_filter(tail[pos]):
+        filt, pos = pos, pos + 1
+    if pos < len(tail) and tail[pos][0][0] == "*":
+        gain, pos = pos, pos + 1
+    return filt, gain, pos
+
+
+class _LineParams:
+    """The parameters of a graph as a plan takes them: each a scalar or a per-voice array, each taken once.  A parameter that is missing or of
+    another shape raises KeyError."""
+
+    def __init__(self, g):
+        self.vals = {(tuple(path), field): np.asarray(value) for path, field, value, _u in g.params}
+        self.total, self.used, self.lens = len(g.params), 0, set()
+
+    def one(self, path, field):
+        v = self.vals[(tuple(path), field)]   # (KeyError: the node lacks the parameter)
+        if v.ndim > 1:
+            raise KeyError(field)
+        if v.ndim == 1:
+            self.lens.add(len(v))
+        self.used += 1
+        return v
+
+    def col(self, paths, field, dtype=np.float32):
+        """`field` of the node at every path (one per line): [lines], or [voices, lines] where a line's is a per-voice array"""
+        vs = [self.one(p, field) for p in paths]
+        if all(v.ndim == 0 for v in vs):
+            return np.array([float(np.float32(v)) for v in vs], dtype=dtype)
+        if len({len(v) for v in vs if v.ndim == 1}) > 1:
+            raise KeyError(field)   # per-voice arrays of different lengths
+        m = max(len(v) for v in vs if v.ndim == 1)
+        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float32).astype(dtype), (m,)) for v in vs], axis=1)
+
+    def weights(self, paths, taps):
+        """the Fir nodes' weights: [lines, taps] | [voices, lines, taps]"""
+        ws = [self.col(paths, f"w[{j}]") for j in range(taps)]
+        if len({w.shape[0] for w in ws if w.ndim == 2}) > 1:
+            raise KeyError("w")     # per-voice arrays of different lengths
+        return np.stack(np.broadcast_arrays(*ws), axis=-1)
+
+    def filter(self, out, paths, ftype):
+        """`cutoff`, `filter` and a FixedSvf's `q`, `gain` of `out` from the lines' filter nodes (of type `ftype`)"""
+        out["cutoff"] = self.col(paths, "cutoff")
+        if ftype != "FixedSvf":
+            out["filter"] = "lowpole"
+            return
+        modes = self.col(paths, "mode")
+        inv = {v: k for k, v in SVF_MODES.items()}
+        if modes.ndim != 1 or len(set(modes.tolist())) != 1 or int(modes[0]) not in inv:
+            raise KeyError("mode")  # the mode is a type parameter in Rust: one for the network
+        out["filter"] = inv[int(modes[0])]
+        out["q"] = self.col(paths, "q")
+        out["gain"] = self.col(paths, "gain")
+
+    def complete(self, voices):
+        """nothing else carries parameters (builders on the nodes: not this shape), and per-voice arrays have one value per voice"""
+        return self.used == self.total and len(self.lens) <= 1 and (voices is None or not self.lens or self.lens == {int(voices)})
+
+
+def fdn_plan(g):
+    """The arguments of fdsp_fdn_create when `g` is the Hadamard feedback delay network the prelude documents (prelude.rs:1323-1345,
+    the "Mono Reverb" example :1334) --
+
+        split(N) | multisplit(2, N/2)  >>  fdn(stacki(N, lambda i: delay(t_i) >> fir(w..)))  >>  join(N) | multijoin(2, N/2)
+
+    with N in 2, 4, 8, 16, 32, one to three FIR weights shared by all lines, and every parameter a scalar (the same network in every
+    instance) -- else None.  Such a graph renders through the lane-per-frame FDN kernel (one wave per instance, the lines in registers,
+    coalesced ring rows) instead of lane-per-voice; Bank.from_graph takes that route when every delay exceeds two blocks."""
+    sj = _split_join(g)
+    if sj is None:
+        return None
+    fb, fpath, nin, nout, n = sj
+    try:
         if fb[0] != "Feedback" or fb[1][1][0] != "FbHadamard":
             return None
         st = fb[1][0]
-        if st[0] != "MultiStack":
+        if st[0] != "MultiStack" or int(st[1][0][0]) != n or n not in (2, 4, 8, 16, 32):
             return None
-        n, line = int(st[1][0][0]), st[1][1]
-        if line[0] != "Pipe" or line[1][0][0] != "Delay" or line[1][1][0] != "Fir":
-            return None
-        taps = int(line[1][1][1][0][0])
+        xs = _flat_chain(st[1][1], (), [])
     except (IndexError, ValueError):
         return None
-    if n not in (2, 4, 8, 16, 32) or n_in != n or n_out != n or not 1 <= taps <= 3:
-        return None
+    head = _line_head(xs)
+    if head is None or head[1] != 2 or len(xs) != 2:
+        return None           # the line is `delay >> fir` and nothing else
+    taps = head[0]
     vals = {}
     for path, field, value, _u in g.params:
         v = np.asarray(value)
@@ -681,152 +779,48 @@ def fdn_network_plan(g, voices=None):
     with N in 2, 4, 8, 16, 32, F_i lowpole_hz(c_i) or one FixedSvf mode (lowpass_hz .. highshelf_hz) for all lines, FIR weights per line and
     every parameter a scalar or a per-voice array of length `voices` -- else None.  (fdn_plan's uniform `delay >> fir(w)` network is one of
     these too; Bank.from_graph takes fdn_plan's kernel for it.)"""
-    name, kids = _parse_type(g.type)
-    chain = []
-
-    def flat(n, path, out):  # a Pipe chain, left to right, with the parameter path of every element; `* g` as a ("*", path) element
-        if n[0] == "Pipe" and len(n[1]) == 2:
-            flat(n[1][0], path + (0,), out)
-            flat(n[1][1], path + (1,), out)
-        elif n[0] == "Unop" and len(n[1]) == 2 and n[1][1][0] == "UMulScalar":
-            flat(n[1][0], path + (0,), out)
-            out.append((("*", []), path))
-        else:
-            out.append((n, path))
-        return out
-
-    chain = flat((name, kids), (), [])
-    if len(chain) != 3:
+    sj = _split_join(g)
+    if sj is None:
         return None
-    (sp, _), (fb, fpath), (jn, _) = chain
-    try:
-        if sp[0] == "Split":
-            nin, n_in = 1, int(sp[1][0][0])
-        elif sp[0] == "MultiSplit" and int(sp[1][0][0]) == 2:
-            nin, n_in = 2, 2 * int(sp[1][1][0])
-        else:
-            return None
-        if jn[0] == "Join":
-            nout, n_out = 1, int(jn[1][0][0])
-        elif jn[0] == "MultiJoin" and int(jn[1][0][0]) == 2:
-            nout, n_out = 2, 2 * int(jn[1][1][0])
-        else:
-            return None
-    except (IndexError, ValueError):
-        return None
+    fb, fpath, nin, nout, n = sj
     loop = fb[0] == "Feedback2"
     if fb[0] not in ("Feedback", "Feedback2") or fb[1][-1][0] != "FbHadamard":
         return None
     stacks = fb[1][:-1]
     if any(st[0] != "MultiStack" for st in stacks):
         return None
-    n = int(stacks[0][1][0][0])
-    if n not in (2, 4, 8, 16, 32) or n_in != n or n_out != n or any(int(st[1][0][0]) != n for st in stacks):
+    if n not in (2, 4, 8, 16, 32) or any(int(st[1][0][0]) != n for st in stacks):
         return None
     # the elements of one line: x's (and y's) Pipe chain, with parameter paths relative to line i's
-    xs = flat(stacks[0][1][1], (), [])
-    ys = flat(stacks[1][1][1], (), []) if loop else []
-    kinds = [e[0][0] for e in xs]
-    if not kinds or kinds[0] != "Delay":
+    xs = _flat_chain(stacks[0][1][1], (), [])
+    head = _line_head(xs)
+    if head is None:
         return None
-    taps, k = 0, 1
-    if k < len(kinds) and kinds[k] == "Fir":
-        try:
-            taps = int(xs[k][0][1][0][0])
-        except (IndexError, ValueError):
-            return None
-        if not 1 <= taps <= 3:
-            return None
-        k += 1
-    tail = xs[k:] if not loop else ys
+    taps, k = head
     if loop and k != len(xs):
         return None           # fdn2's x: delay [>> fir] only
-    filt = None
-    if tail and (tail[0][0][0] == "FixedSvf" or (tail[0][0][0] == "OnePole" and [c[0] for c in tail[0][0][1]] == ["OP_LOWPOLE", "1"])):
-        filt = tail[0]
-        tail = tail[1:]
-    if loop and filt is None:
-        return None
-    gain = None
-    if tail and tail[0][0][0] == "*":
-        gain = tail[0]
-        tail = tail[1:]
-    if tail:
-        return None           # something else in the line
-    # parameters: one value per (side, line, path within the line, field)
-    vals = {}
-    for path, field, value, _u in g.params:
-        vals[(tuple(path), field)] = np.asarray(value)
-    lens = set()
-    used = 0
+    tail = _flat_chain(stacks[1][1][1], (), []) if loop else xs[k:]
+    filt, gain, pos = _line_tail(tail)
+    if pos != len(tail) or (loop and filt is None):
+        return None           # something else in the line; fdn2 needs its filter
+    fside = 1 if loop else 0   # where the filter and its gain stand: in x's line, or in y
 
-    def col(side, path, field, dtype=np.float32):
-        nonlocal used
-        vs = []
-        for i in range(n):
-            key = (fpath + (side, i) + path, field)
-            if key not in vals:
-                raise KeyError(key)
-            v = vals[key]
-            if v.ndim > 1:
-                raise KeyError(key)
-            if v.ndim == 1:
-                lens.add(len(v))
-            vs.append(v)
-        used += n
-        if all(v.ndim == 0 for v in vs):
-            return np.array([float(np.float32(v)) for v in vs], dtype=dtype)
-        if len({len(v) for v in vs if v.ndim == 1}) > 1:
-            raise KeyError(field)   # per-voice arrays of different lengths
-        m = max(len(v) for v in vs if v.ndim == 1)
-        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float32).astype(dtype), (m,)) for v in vs], axis=1)   # [voices, lines]
+    def at(side, e):          # element `e` of x (side 0) or y (side 1) in every line
+        return [fpath + (side, i) + e[1] for i in range(n)]
 
+    params = _LineParams(g)
     out = dict(lines=n, inputs=nin, outputs=nout, place="loop" if loop else "line")
     try:
-        out["delays"] = col(0, xs[0][1], "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
+        out["delays"] = params.col(at(0, xs[0]), "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
         if taps:
-            ws = [col(0, xs[1][1], f"w[{j}]") for j in range(taps)]
-            out["weights"] = np.stack(ws, axis=-1)              # [lines, taps] | [voices, lines, taps]
-        side = 1 if loop else 0
+            out["weights"] = params.weights(at(0, xs[1]), taps)
         if filt is not None:
-            ftype = filt[0][0]
-            out["cutoff"] = col(side, filt[1], "cutoff")
-            if ftype == "FixedSvf":
-                modes = col(side, filt[1], "mode")
-                if modes.ndim != 1 or len(set(modes.tolist())) != 1:
-                    return None   # the mode is a type parameter in Rust: one for the network
-                mode = int(modes[0])
-                inv = {v: k for k, v in SVF_MODES.items()}
-                if mode not in inv:
-                    return None
-                out["filter"] = inv[mode]
-                out["q"] = col(side, filt[1], "q")
-                out["gain"] = col(side, filt[1], "gain")
-            else:
-                out["filter"] = "lowpole"
+            params.filter(out, at(fside, tail[filt]), tail[filt][0][0])
         if gain is not None:
-            out["line_gain"] = col(side, gain[1], "scalar")
+            out["line_gain"] = params.col(at(fside, tail[gain]), "scalar")
     except KeyError:
         return None
-    if used != len(g.params):
-        return None           # something else carries parameters (builders on the nodes): not this shape
-    if len(lens) > 1 or (voices is not None and lens and lens != {int(voices)}):
-        return None           # per-voice arrays must have one value per voice
-    return out
-
-
-def _flat_chain(n, path, out):
-    """a Pipe chain of a parsed type, left to right, as (node, parameter path) elements; `x * scalar` as a ("*", path) element behind x's"""
-    if n[0] == "Pipe" and len(n[1]) == 2:
-        _flat_chain(n[1][0], path + (0,), out)
-        _flat_chain(n[1][1], path + (1,), out)
-    elif n[0] == "Unop" and len(n[1]) == 2 and n[1][1][0] == "UMulScalar":
-        _flat_chain(n[1][0], path + (0,), out)
-        out.append((("*", []), path))
-    else:
-        out.append((n, path))
-    return out
-
+    return out if params.complete(voices) else None
 
 def feedback_delay_plan(g, voices=None):
     """The arguments of Bank.feedback_delay (fdsp_feedback_delay_create) when `g` is the identity feedback around one or two delay lines --
@@ -868,115 +862,48 @@ def feedback_delay_plan(g, voices=None):
         outer, rest = rest[0][1], rest[1:]
     if rest:
         return None               # something else behind the lines
-    kinds = [e[0][0] for e in xs[0]]
-    if kinds[0] != "Delay":
+    head = _line_head(xs[0])
+    if head is None:
         return None               # (a filter in front of the delay, more than two channels, another network)
-    taps, k = 0, 1
-    if k < len(kinds) and kinds[k] == "Fir":
-        try:
-            taps = int(xs[0][k][0][1][0][0])
-        except (IndexError, ValueError):
-            return None
-        if not 1 <= taps <= 3:
-            return None
-        k += 1
+    taps, k = head
     if loop:
-        if k != len(kinds) or outer is not None:
+        if k != len(xs[0]) or outer is not None:
             return None           # feedback2's x: delay [>> fir] [>> reverse] only
         y = fb[1][1]
         if n == 1:
-            ys = [_flat_chain(y, (1,), [])]
+            tails = [_flat_chain(y, (1,), [])]
         elif y[0] == "Stack" and len(y[1]) == 2 and y[1][0] == y[1][1]:
-            ys = [_flat_chain(y[1][i], (1, i), []) for i in range(2)]
+            tails = [_flat_chain(y[1][i], (1, i), []) for i in range(2)]
         elif y[0] == "MultiStack" and len(y[1]) == 2 and y[1][0][0] == "2":
-            ys = [_flat_chain(y[1][1], (1, i), []) for i in range(2)]
+            tails = [_flat_chain(y[1][1], (1, i), []) for i in range(2)]
         else:
             return None
-        tails = ys
     else:
         tails = [x[k:] for x in xs]
-
-    def is_filter(e):
-        return e[0][0] == "FixedSvf" or (e[0][0] == "OnePole" and [c[0] for c in e[0][1]] == ["OP_LOWPOLE", "1"])
-
-    filt = gain = None
-    t0 = [e[0][0] for e in tails[0]]
-    pos = 0
-    if pos < len(t0) and is_filter(tails[0][pos]):
-        filt, pos = pos, pos + 1
+    t0 = tails[0]
+    filt, gain, pos = _line_tail(t0)
     if loop and filt is None:
         return None
-    if pos < len(t0) and t0[pos] == "*":
-        gain, pos = pos, pos + 1
-    if n == 1 and not loop and pos < len(t0) and t0[pos] == "*":
-        outer_el, pos = tails[0][pos][1], pos + 1
-    else:
-        outer_el = None
+    if n == 1 and not loop and pos < len(t0) and t0[pos][0][0] == "*":
+        outer, pos = t0[pos][1], pos + 1
     if pos != len(t0):
         return None               # something else in the line (pinkpass, a second filter, ..)
-    if outer_el is not None:
-        outer = outer_el
-    vals = {}
-    for path, field, value, _u in g.params:
-        vals[(tuple(path), field)] = np.asarray(value)
-    lens = set()
-    used = 0
-
-    def one(path, field):
-        nonlocal used
-        v = vals[(tuple(path), field)]   # (KeyError: the node lacks the parameter)
-        if v.ndim > 1:
-            raise KeyError(field)
-        if v.ndim == 1:
-            lens.add(len(v))
-        used += 1
-        return v
-
-    def col(elems, field, dtype=np.float32):
-        vs = [one(e[1], field) for e in elems]
-        if all(v.ndim == 0 for v in vs):
-            return np.array([float(np.float32(v)) for v in vs], dtype=dtype)
-        if len({len(v) for v in vs if v.ndim == 1}) > 1:
-            raise KeyError(field)   # per-voice arrays of different lengths
-        m = max(len(v) for v in vs if v.ndim == 1)
-        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float32).astype(dtype), (m,)) for v in vs], axis=1)   # [voices, channels]
-
+    params = _LineParams(g)
     out = dict(place="loop" if loop else "line", reverse=reverse)
     try:
-        out["delays"] = col([x[0] for x in xs], "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
+        out["delays"] = params.col([x[0][1] for x in xs], "time", np.float64)   # delay(t: f32) -> Delay::new(t as f64)
         if taps:
-            ws = [col([x[1] for x in xs], f"w[{j}]") for j in range(taps)]
-            if len({w.shape[0] for w in ws if w.ndim == 2}) > 1:
-                return None   # per-voice arrays of different lengths
-            out["weights"] = np.stack(np.broadcast_arrays(*ws), axis=-1)   # [N, taps] | [voices, N, taps]
+            out["weights"] = params.weights([x[1][1] for x in xs], taps)
         if filt is not None:
-            fe = [t[filt] for t in tails]
-            out["cutoff"] = col(fe, "cutoff")
-            if fe[0][0][0] == "FixedSvf":
-                modes = col(fe, "mode")
-                if modes.ndim != 1 or len(set(modes.tolist())) != 1:
-                    return None   # the mode is a type parameter in Rust: one for the network
-                inv = {v: k for k, v in SVF_MODES.items()}
-                if int(modes[0]) not in inv:
-                    return None
-                out["filter"] = inv[int(modes[0])]
-                out["q"] = col(fe, "q")
-                out["gain"] = col(fe, "gain")
-            else:
-                out["filter"] = "lowpole"
+            params.filter(out, [t[filt][1] for t in tails], t0[filt][0][0])
         if gain is not None:
-            out["line_gain"] = col([t[gain] for t in tails], "scalar")
+            out["line_gain"] = params.col([t[gain][1] for t in tails], "scalar")
         if outer is not None:
-            v = one(outer, "scalar")
+            v = params.one(outer, "scalar")
             out["outer_gain"] = float(np.float32(v)) if v.ndim == 0 else np.asarray(v, dtype=np.float32)
     except KeyError:
         return None
-    if used != len(g.params):
-        return None               # something else carries parameters (builders on the nodes): not this shape
-    if len(lens) > 1 or (voices is not None and lens and lens != {int(voices)}):
-        return None               # per-voice arrays must have one value per voice
-    return out
-
+    return out if params.complete(voices) else None
 
 def lane_per_frame_shape(g):
     """whether `g` is one of the nodes / networks with a lane-per-frame kernel (what Bank.from_graph builds as an FDN / reverb bank)"""
