@@ -1,5 +1,5 @@
 """The fused mix-down of the effect banks (fdsp_bank_process_mix / fdsp_bank_process_mix_planar on reverb_stereo, reverb4_stereo, the
-generic fdn, reverb3_stereo and the filtered / per-instance networks) and of chains that end in one.
+generic fdn, reverb3_stereo, the filtered / per-instance networks and the feedback delay banks) and of chains that end in one.
 
 Bar: bit for bit.  The fused mix equals fdsp_sum_voices / fdsp_mix_stereo of the same bank's voice-minor render and the summation order's
 numpy statement (tests/mix_order.py) applied to it; the planar entry gives the same bits; the state after a mix launch is the state after a
@@ -13,6 +13,7 @@ from fundsp_amd import LAYOUT_PLANAR, LAYOUT_VOICE_MINOR, MIX_PAN, MIX_SUM, MODE
 from fundsp_amd import graph as GR
 from test_gpu_fdn import delays_of
 from test_gpu_fdn_network import params as network_params
+from test_gpu_feedback_delay import params as feedback_params
 from test_gpu_parity import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,8 @@ def _at_rate(b):
     return b
 
 
-# every delay is at least 128 samples at 44.1 kHz and at 48 kHz (the constructor arguments of test_gpu_reverb / _fdn / _reverb3 / _fdn_network)
+# every delay is at least 128 samples at 44.1 kHz and at 48 kHz (the constructor arguments of test_gpu_reverb / _fdn / _reverb3 / _fdn_network /
+# _feedback_delay)
 FAMILIES = {
     "reverb_stereo": lambda gpu, V: _at_rate(gpu.Bank.reverb_stereo(V, 10.0, 1.0, 0.5)),
     "reverb4_stereo": lambda gpu, V: _at_rate(gpu.Bank.reverb4_stereo(V, 20.0, 2.0)),
@@ -37,6 +39,9 @@ FAMILIES = {
                                                             **network_params(16, V, "lowpass", 0, True, False, 16)),
     "network_per_instance": lambda gpu, V: gpu.Bank.fdn_network(V, 32, place="loop", inputs=2, outputs=2, sample_rate=SR,
                                                                 **network_params(32, V, "lowpole", 3, True, True, 35)),
+    # k_fb_frames<1, 2>: line form, lowpole, line gain and outer gain | k_fb_frames<2, 3>: loop form, reversed, every parameter per instance
+    "feedback_delay_mono": lambda gpu, V: gpu.Bank.feedback_delay(V, sample_rate=SR, **feedback_params(1, "line", "lowpole", 2, True, True, False)),
+    "feedback_delay_stereo": lambda gpu, V: gpu.Bank.feedback_delay(V, sample_rate=SR, **feedback_params(2, "loop", "lowpole", 3, True, False, True, V=V)),
 }
 V_GRID, T_GRID = (1, 5, 63, 64, 65, 64 * 3 + 21), (1, 64, 65, 64 * 5 + 9)
 SUBSET = [(65, 64 * 5 + 9), (5, 65), (64 * 3 + 21, 64), (1, 1)]   # every family: a ragged second group over ragged blocks, fewer than a quarter
@@ -115,7 +120,7 @@ def test_every_family_mixes(gpu, name, V, T, mode):
     check_family(gpu, name, V, T, mode)
 
 
-@pytest.mark.parametrize("name", ["fdn8_1x1", "network_filtered"])
+@pytest.mark.parametrize("name", ["fdn8_1x1", "network_filtered", "feedback_delay_mono"])
 def test_mix_pan_on_mono_banks(gpu, name):
     import torch
 
