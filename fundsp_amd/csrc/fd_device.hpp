@@ -20,6 +20,7 @@
 #include "fd_nodes.hpp"
 #include "fd_plan.hpp"  // LAYOUT_* / MODE_* / MIX_*, GraphTraits
 #include "fd_seq.hpp"   // the Sequencer's clock arithmetic (host + device)
+#include "fd_seq_steps.hpp"  // ... and the steps the scheduler kernels share (host + device)
 
 namespace fd {
 
@@ -841,7 +842,8 @@ __global__ __launch_bounds__(64 * WPB) void k_render(float* __restrict__ slots, 
 // over voices is fdsp_sum_voices.  Exactly as in the reference, a unit is processed in the part of each 64-frame
 // sequencer block that its event overlaps -- a SHORTER process() block at its start and end -- and the fade factors
 // are re-derived per block from the f64 clock and accumulated in f32 inside the block.
-// (the clock arithmetic -- block windows, fade phases, Fade::at -- is fd_seq.hpp, shared with the score kernels below)
+// (the clock arithmetic -- block windows, fade phases, Fade::at -- is fd_seq.hpp; the kernels are the score kernels' body under
+// another source of notes: render_sched_body with EventNotes, below the mix-down pieces)
 
 // ---- fused mix-down ("mode B" of SURVEY.md 8(d): on-device reduction of the voices to [channels][frames]) ------------
 // The LAST stage of a voice group does not store its samples to HBM; it parks them in a small LDS tile
@@ -939,15 +941,115 @@ FD_D void mix_flush_pan(const float* tile, float* dst, size_t T, int nf, int lan
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-// MIXE (k_render_events_mix, fdsp_bank_process_events_mix): the Sequencer's OUTPUT -- the sum of its events (sequencer.rs:838-951) -- leaves the
-// launch instead of every event's own samples: a wave parks its block in an LDS tile [channel][64 frames][64 voices + 4] and flushes it as
-// the voice group's partial mix (mix_flush, the mix-down's fixed order); `out` is then the partial buffer [groups][channels][T].  Every lane
-// of a live group takes part in the flush; a padded voice of the last group is an event that never plays.
-template <class G, int MODE, bool MIXE = false>
-FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
-                             float* __restrict__ out, size_t T, const double* __restrict__ ev,
-                             const int* __restrict__ fade, double time0, double sample_rate, const void* aux, float* ring,
-                             uint32_t ring_cap) {
+// ---- scores: a pool of voices, each playing one note after another (fdsp_bank_set_score) ---------------------------------
+// The Sequencer with MANY events per voice: lane = voice, and the lane walks its voice's notes (fd_seq.hpp ScoreData; sorted,
+// end_k <= start_{k+1}, so their frame windows never overlap).  Note k plays exactly like a Sequencer event whose unit is a
+// fresh unit with the voice's hash and parameters and the note's row written over the named slots: in the first block (tick)
+// in which the note is active the lane writes the row into its node, runs update(sr) and reset() -- what lifecycle ops 1 and 2
+// do.  Where a voice stands is a function of the clock alone (seq_first_live / seq_note_begun): nothing but the clock carries
+// over between launches, a note that straddles a launch boundary continues with the state it has.  Parameters and
+// coefficients therefore go back to the slots with the state at the end of the launch.
+// A block in which every lane of the wave is inside its current note for the whole block, no fade running, takes the packed
+// two-frame path (fd_seq_steps.hpp seq_steady_block); in any other block the wave goes frame by frame and a lane may finish note k
+// and start notes k+1, k+2 ... -- each with its own begin_block(n) -- with +0.0 between them.
+struct VSetRow {  // counts slots like VLoad / VStore and overwrites the score's
+    const float* params;
+    const int* param_slot;
+    int nparams;
+    size_t N, note;
+    int slot;
+    FD_D void put(float& x) {
+        for (int j = 0; j < nparams; j++)
+            if (param_slot[j] == slot) x = params[(size_t)j * N + note];
+        slot++;
+    }
+    FD_D void f(float& x, FieldKind, const char*) { put(x); }
+    FD_D void fi(float& x, FieldKind, const char*, int) { put(x); }
+    FD_D void u32(uint32_t&, FieldKind, const char*) { slot++; }
+    FD_D void u64(uint64_t&, FieldKind, const char*) { slot += 2; }
+    FD_D void enter(int) {}
+    FD_D void leave() {}
+};
+
+// ---- where a lane = voice gets its notes from: the two policies of render_sched_body ----------------------------------------
+// A policy holds the lane's current note (e_start, e_end, e_fin, e_fout, ease; behind the last one: a note that never plays) and says
+//   first(v, voice, time0, sd)  the note the voice stands at when the launch starts (a padded voice of the last group has none)
+//   skip_over(time, sd)         at a block / tick starting at `time`: move on to the first note that is not over
+//   next(end_time, sd)          the current note's window in this block is done: take the NEXT note if it is ready in the block
+//   begun(time, sd)             the current note was begun in an earlier block (or needs no beginning)
+//   begin(g, sr)                a fresh unit with the note's parameters (fd_seq_steps.hpp seq_note_begin)
+//   STORE_ALL                   what goes back to the slots at the end of the launch: everything, or the state only
+// Events: ONE note per voice, ev[4][stride] and fade[V] (NULL: curve 1 everywhere).  An event is a score of one note per voice that is
+// never begun -- no row, no update, no reset: the unit plays on with what the slots hold -- and that stores its state only
+// (tests/test_gpu_score.py test_one_note_per_voice_without_rows_equals_set_events).  An event that is over never plays again
+// (seq_block: not active), so there is nothing to skip and nothing behind it.
+struct EventNotes {
+    static constexpr bool STORE_ALL = false;
+    const double* ev;
+    const int* fade;
+    size_t stride;
+    double e_start, e_end, e_fin, e_fout;
+    int ease;
+    FD_D void first(size_t v, bool voice, double, double) {
+        const double inf_ = __builtin_huge_val();
+        e_start = voice ? ev[v] : inf_;
+        e_end = voice ? ev[stride + v] : -inf_;
+        e_fin = voice ? ev[2 * stride + v] : 0.0;
+        e_fout = voice ? ev[3 * stride + v] : 0.0;
+        ease = (fade && voice) ? fade[v] : 1;
+    }
+    FD_D void skip_over(double, double) {}
+    FD_D bool next(double, double) { return false; }
+    FD_D bool begun(double, double) const { return true; }
+    template <class G> FD_D void begin(G&, double) {}
+};
+// Scores: the voice's range of the sorted score, one note after the other.
+struct ScoreNotes {
+    static constexpr bool STORE_ALL = true;  // a note's row and the coefficients derived from it belong to the note that goes on in the next launch
+    ScoreData sc;
+    int k, ne;
+    double e_start, e_end, e_fin, e_fout;
+    int ease;
+    FD_D void load_note(int j) {  // the lane's current note; behind the voice's last one: a note that never plays
+        const double inf_ = __builtin_huge_val();
+        const size_t N = (size_t)sc.N;
+        const bool on = j < ne;
+        e_start = on ? sc.ev[j] : inf_;
+        e_end = on ? sc.ev[N + j] : -inf_;
+        e_fin = on ? sc.ev[2 * N + j] : 0.0;
+        e_fout = on ? sc.ev[3 * N + j] : 0.0;
+        ease = on ? sc.fade[j] : 1;
+    }
+    FD_D void first(size_t v, bool voice, double time0, double sd) {
+        ne = voice ? sc.note_begin[v + 1] : 0;
+        k = voice ? seq_first_live(sc.ev + (size_t)sc.N, sc.note_begin[v], ne, time0, sd) : 0;
+        load_note(k);
+    }
+    FD_D void skip_over(double time, double sd) {
+        while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
+    }
+    FD_D bool next(double end_time, double sd) {
+        const double next_start = k + 1 < ne ? sc.ev[k + 1] : __builtin_huge_val();
+        if (!seq_note_ready(next_start, end_time, sd)) return false;
+        load_note(++k);
+        return true;
+    }
+    FD_D bool begun(double time, double sd) const { return seq_note_begun(e_start, time, sd); }
+    template <class G> FD_D void begin(G& g, double sample_rate) {
+        VSetRow row{sc.params, sc.param_slot, sc.nparams, (size_t)sc.N, (size_t)k, 0};
+        seq_note_begin(g, row, sample_rate);
+    }
+};
+
+// The lane-per-voice scheduler body: four waves per workgroup, a wave is a voice group, the steps are fd_seq_steps.hpp's.
+// MIXE (k_render_events_mix / k_render_score_mix, fdsp_bank_process_events_mix): the Sequencer's OUTPUT -- the sum of its events
+// (sequencer.rs:838-951) -- leaves the launch instead of every event's own samples: a wave parks its block in an LDS tile
+// [channel][64 frames][64 voices + 4] and flushes it as the voice group's partial mix (mix_flush, the mix-down's fixed order); `out` is
+// then the partial buffer [groups][channels][T].  Every lane of a live group takes part in the flush; a padded voice of the last group
+// has a note that never plays.
+template <class G, int MODE, class NOTES, bool MIXE>
+FD_D void render_sched_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ out,
+                            size_t T, NOTES notes, double time0, double sample_rate, const void* aux, float* ring, uint32_t ring_cap) {
     constexpr int NI = G::IN, NO = G::OUT;
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -966,11 +1068,8 @@ FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V,
         VLoad ld{slots + v, stride, 0};
         g.visit(ld);
     }
-    const double inf_ = __builtin_huge_val();
-    const double e_start = voice ? ev[v] : inf_, e_end = voice ? ev[stride + v] : -inf_, e_fin = voice ? ev[2 * stride + v] : 0.0,
-                 e_fout = voice ? ev[3 * stride + v] : 0.0;
-    const int ease = (fade && voice) ? fade[v] : 1;
     const double sd = 1.0 / sample_rate;  // Sequencer::set_sample_rate :752-753
+    notes.first(v, voice, time0, sd);
     double time = time0;
     const float* inv = in + v;
     float* outv = out + v;
@@ -982,88 +1081,50 @@ FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V,
         for (size_t t0 = 0; t0 < T; t0 += 64) {
             const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
             const double end_time = time + sd * (double)size;
-            const SeqBlock w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
-            const bool act = w.act, fin_on = w.fin_on, fout_on = w.fout_on;
-            const long long start_index = w.start_index, end_index = w.end_index, fin_end_i = w.fin_end_i, fout_i = w.fout_i;
-            const int n = act ? (int)(end_index - start_index) : 0;
-            const int full = n & ~7;
-            float fin_cur = w.fin_cur, fout_cur = w.fout_cur;
-            const float fin_d = w.fin_d, fout_d = w.fout_d;
-            // Steady state -- every voice of the wave inside its event for the whole block, no fade running: the block is a
+            notes.skip_over(time, sd);
+            SeqBlock w = seq_block(notes.e_start, notes.e_end, notes.e_fin, notes.e_fout, time, size, sample_rate);
+            // Steady state -- every voice of the wave inside a note it has begun, for the whole block, no fade running: the block is a
             // plain process(size) of the unit, so it takes the packed two-frame path of render_body (same arithmetic).
-            const bool steady = act && start_index == 0 && end_index == size && !fin_on && !fout_on;
+            const bool steady = w.act && w.start_index == 0 && w.end_index == size && !w.fin_on && !w.fout_on && notes.begun(time, sd);
             if (__builtin_amdgcn_ballot_w64(steady) == __builtin_amdgcn_ballot_w64(true)) {
-                g.begin_block(size);
-                const G snap = g;
-                for (int i = 0; i < full; i += 2) {
-                    const size_t t = t0 + i;
-                    v2f pi[NI > 0 ? NI : 1], po[NO];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) pi[c] = v2f{inv[((size_t)c * T + t) * V], inv[((size_t)c * T + t + 1) * V]};
-                    g.template step2<PH_SIMD>(pi, po);
-#pragma unroll
-                    for (int c = 0; c < NO; c++) {
-                        put(c, t, po[c].x);
-                        put(c, t + 1, po[c].y);
+                seq_steady_block(g, size, [&](int c, int i) { return inv[((size_t)c * T + t0 + i) * V]; },
+                                 [&](int c, int i, float x) { put(c, t0 + i, x); });
+            } else {
+                // Frame by frame, the wave in step: a lane crosses from one note to the next where its window ends.  [si, ei) is the window of
+                // the lane's current note in this block (empty: the note does not play in it); behind it the NEXT note joins the block only if
+                // it is ready in it -- then the current one is over by the next block, so the lane's one set of note registers can move on.
+                int si = 0, ei = 0;
+                SeqWindow win{0, 0.0f, 0.0f};
+                auto open = [&]() {  // the current note's window in this block; if it plays, its own process() block begins (no frame of the
+                    si = w.act ? (int)w.start_index : 0;  // unit lies between here and the window's first one)
+                    ei = w.act ? (int)w.end_index : 0;
+                    if (w.act) {
+                        if (!notes.begun(time, sd)) notes.begin(g, sample_rate);
+                        win = seq_window_begin(g, w, ei - si);
                     }
-                }
-                if (__builtin_expect(g.tripped(), 0)) {  // a packed-path shortcut left its exact domain: redo the block
-                    g = snap;
-                    for (int i = 0; i < full; i++) {
-                        const size_t t = t0 + i;
-                        float fi[NI > 0 ? NI : 1], fo[NO];
+                };
+                open();
+                bool look = true;
+                for (int i = 0; i < size; i++) {
+                    const size_t t = t0 + i;
+                    while (look && i >= ei) {
+                        look = notes.next(end_time, sd);
+                        if (!look) break;
+                        w = seq_block(notes.e_start, notes.e_end, notes.e_fin, notes.e_fout, time, size, sample_rate);
+                        open();
+                    }
+                    float fo[NO];
+#pragma unroll
+                    for (int c = 0; c < NO; c++) fo[c] = 0.0f;
+                    if (i >= si && i < ei) {
+                        float fi[NI > 0 ? NI : 1];
 #pragma unroll
                         for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                        g.template step<PH_SIMD>(fi, fo);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) put(c, t, fo[c]);
+                        seq_window_frame(g, w, win, notes.ease, i - si, fi, fo);  // (i - si: the index in the note's own sub-block buffer)
                     }
-                }
-                g.end_simd();
-                for (int i = full; i < size; i++) {
-                    const size_t t = t0 + i;
-                    float fi[NI > 0 ? NI : 1], fo[NO];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                    g.template step<PH_REM>(fi, fo);
 #pragma unroll
                     for (int c = 0; c < NO; c++) put(c, t, fo[c]);
                 }
-                if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
-                time = end_time;
-                continue;
-            }
-            if (act) {
-                g.begin_block(n);
-                if (full == 0) g.end_simd();
-            }
-            for (int i = 0; i < size; i++) {
-                const size_t t = t0 + i;
-                float fo[NO];
-#pragma unroll
-                for (int c = 0; c < NO; c++) fo[c] = 0.0f;
-                if (act && i >= start_index && i < end_index) {
-                    const int k = i - (int)start_index;  // index in the event's own sub-block buffer
-                    float fi[NI > 0 ? NI : 1];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                    if (k < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
-                    if (k + 1 == full) g.end_simd();
-                    if (fin_on && k < fin_end_i) {
-                        const float e = fade_at(ease, fin_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fin_cur += fin_d;
-                    }
-                    if (fout_on && k >= fout_i && k < end_index) {
-                        const float e = fade_at(ease, 1.0f - fout_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fout_cur += fout_d;
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < NO; c++) put(c, t, fo[c]);
             }
             if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
             time = end_time;
@@ -1071,32 +1132,18 @@ FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V,
     } else {
         for (size_t t = 0; t < T; t++) {  // Sequencer::tick :769-836
             const double end_time = time + sd;
-            const double threshold = end_time - sd * 0.5;
-            const bool act = e_start < threshold && !(e_end <= time + 0.5 * sd);
+            notes.skip_over(time, sd);
+            const bool act = seq_note_ready(notes.e_start, end_time, sd) && !seq_note_over(notes.e_end, time, sd);
             float fo[NO];
 #pragma unroll
             for (int c = 0; c < NO; c++) fo[c] = 0.0f;
             if (act) {
+                if (!notes.begun(time, sd)) notes.begin(g, sample_rate);
                 float fi[NI > 0 ? NI : 1];
 #pragma unroll
                 for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
                 g.template step<PH_TICK>(fi, fo);
-                if (e_fin > 0.0) {
-                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
-                    if (f < 1.0f) {
-                        const float e = fade_at(ease, f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
-                if (e_fout > 0.0) {
-                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
-                    if (f > 0.0f) {
-                        const float e = fade_at(ease, 1.0f - f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
+                seq_tick_fades<NO>(notes.e_start, notes.e_end, notes.e_fin, notes.e_fout, notes.ease, time, fo);
             }
 #pragma unroll
             for (int c = 0; c < NO; c++) put(c, t, fo[c]);
@@ -1107,9 +1154,21 @@ FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V,
         }
     }
     if (voice) {
-        VStore<false> st{slots + v, stride, 0};
+        VStore<NOTES::STORE_ALL> st{slots + v, stride, 0};
         g.visit(st);
     }
+}
+
+template <class G, int MODE, bool MIXE = false>
+FD_D void render_events_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ out,
+                             size_t T, const double* __restrict__ ev, const int* __restrict__ fade, double time0, double sample_rate,
+                             const void* aux, float* ring, uint32_t ring_cap) {
+    render_sched_body<G, MODE, EventNotes, MIXE>(slots, stride, V, in, out, T, EventNotes{ev, fade, stride}, time0, sample_rate, aux, ring, ring_cap);
+}
+template <class G, int MODE, bool MIXE = false>
+FD_D void render_score_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in, float* __restrict__ out,
+                            size_t T, const ScoreData sc, double time0, double sample_rate, const void* aux, float* ring, uint32_t ring_cap) {
+    render_sched_body<G, MODE, ScoreNotes, MIXE>(slots, stride, V, in, out, T, ScoreNotes{sc}, time0, sample_rate, aux, ring, ring_cap);
 }
 
 template <class G, int MODE>
@@ -1130,236 +1189,6 @@ __global__ __launch_bounds__(256) void k_render_events(float* __restrict__ slots
     render_events_body<G, MODE>(slots, stride, V, in, out, T, ev, fade, time0, sample_rate, aux, ring, ring_cap);
 }
 
-// ---- scores: a pool of voices, each playing one note after another (fdsp_bank_set_score) ---------------------------------
-// The Sequencer with MANY events per voice: lane = voice, and the lane walks its voice's notes (fd_seq.hpp ScoreData; sorted,
-// end_k <= start_{k+1}, so their frame windows never overlap).  Note k plays exactly like a Sequencer event whose unit is a
-// fresh unit with the voice's hash and parameters and the note's row written over the named slots: in the first block (tick)
-// in which the note is active the lane writes the row into its node, runs update(sr) and reset() -- what lifecycle ops 1 and 2
-// do.  Where a voice stands is a function of the clock alone (seq_first_live / seq_note_begun): nothing but the clock carries
-// over between launches, a note that straddles a launch boundary continues with the state it has.  Parameters and
-// coefficients therefore go back to the slots with the state at the end of the launch.
-// A block in which every lane of the wave is inside its current note for the whole block, no fade running, takes the packed
-// two-frame path like render_events_body; in any other block the wave goes frame by frame and a lane may finish note k and start
-// notes k+1, k+2 ... -- each with its own begin_block(n) -- with +0.0 between them.
-struct VSetRow {  // counts slots like VLoad / VStore and overwrites the score's
-    const float* params;
-    const int* param_slot;
-    int nparams;
-    size_t N, note;
-    int slot;
-    FD_D void put(float& x) {
-        for (int j = 0; j < nparams; j++)
-            if (param_slot[j] == slot) x = params[(size_t)j * N + note];
-        slot++;
-    }
-    FD_D void f(float& x, FieldKind, const char*) { put(x); }
-    FD_D void fi(float& x, FieldKind, const char*, int) { put(x); }
-    FD_D void u32(uint32_t&, FieldKind, const char*) { slot++; }
-    FD_D void u64(uint64_t&, FieldKind, const char*) { slot += 2; }
-    FD_D void enter(int) {}
-    FD_D void leave() {}
-};
-
-template <class G, int MODE, bool MIXE = false>
-FD_D void render_score_body(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
-                            float* __restrict__ out, size_t T, const ScoreData sc, double time0, double sample_rate,
-                            const void* aux, float* ring, uint32_t ring_cap) {
-    constexpr int NI = G::IN, NO = G::OUT;
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const size_t v0 = ((size_t)blockIdx.x * 4 + wib) * 64;
-    const size_t v = v0 + lane;
-    if (v0 >= stride) return;
-    const bool voice = v < V;
-    if (!MIXE && !voice) return;
-    __shared__ __attribute__((aligned(16))) float etile[MIXE ? 4 : 1][MIXE ? NO * 64 * MIX_ROW : 4];
-    float* tile = &etile[MIXE ? wib : 0][0];
-    float* part = MIXE ? out + (v0 / 64) * (size_t)NO * T : nullptr;  // this group's partial mix [channel][T]
-    G g;
-    Ctx ctx{static_cast<const Aux*>(aux), ring + v, ring_cap, stride, 0};
-    g.bind(ctx);
-    {
-        VLoad ld{slots + v, stride, 0};
-        g.visit(ld);
-    }
-    const double inf_ = __builtin_huge_val();
-    const double sd = 1.0 / sample_rate;  // Sequencer::set_sample_rate :752-753
-    const size_t N = (size_t)sc.N;
-    const int ne = voice ? sc.note_begin[v + 1] : 0;  // a padded voice of the last group has no notes
-    int k = voice ? seq_first_live(sc.ev + N, sc.note_begin[v], ne, time0, sd) : 0;
-    double e_start, e_end, e_fin, e_fout;
-    int ease;
-    auto load_note = [&](int j) {  // the lane's current note; behind the voice's last one: a note that never plays
-        const bool on = j < ne;
-        e_start = on ? sc.ev[j] : inf_;
-        e_end = on ? sc.ev[N + j] : -inf_;
-        e_fin = on ? sc.ev[2 * N + j] : 0.0;
-        e_fout = on ? sc.ev[3 * N + j] : 0.0;
-        ease = on ? sc.fade[j] : 1;
-    };
-    auto begin_note = [&](int j) {  // a fresh unit with the note's parameters
-        VSetRow row{sc.params, sc.param_slot, sc.nparams, N, (size_t)j, 0};
-        g.visit(row);
-        g.update(sample_rate);
-        g.reset();
-    };
-    load_note(k);
-    double time = time0;
-    const float* inv = in + v;
-    float* outv = out + v;
-    auto put = [&](int c, size_t t, float x) {  // frame t of the launch, channel c
-        if constexpr (MIXE) tile[(c * 64 + (int)(t & 63)) * MIX_ROW + lane] = x;
-        else outv[((size_t)c * T + t) * V] = x;
-    };
-    if (MODE == MODE_PROCESS) {
-        for (size_t t0 = 0; t0 < T; t0 += 64) {
-            const int size = (int)((T - t0) < 64 ? (T - t0) : 64);
-            const double end_time = time + sd * (double)size;
-            while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
-            SeqBlock w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
-            // Steady state -- every voice of the wave inside a note it has begun, for the whole block, no fade running
-            const bool steady = w.act && w.start_index == 0 && w.end_index == size && !w.fin_on && !w.fout_on && seq_note_begun(e_start, time, sd);
-            if (__builtin_amdgcn_ballot_w64(steady) == __builtin_amdgcn_ballot_w64(true)) {
-                const int full = size & ~7;
-                g.begin_block(size);
-                const G snap = g;
-                for (int i = 0; i < full; i += 2) {
-                    const size_t t = t0 + i;
-                    v2f pi[NI > 0 ? NI : 1], po[NO];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) pi[c] = v2f{inv[((size_t)c * T + t) * V], inv[((size_t)c * T + t + 1) * V]};
-                    g.template step2<PH_SIMD>(pi, po);
-#pragma unroll
-                    for (int c = 0; c < NO; c++) {
-                        put(c, t, po[c].x);
-                        put(c, t + 1, po[c].y);
-                    }
-                }
-                if (__builtin_expect(g.tripped(), 0)) {  // a packed-path shortcut left its exact domain: redo the block
-                    g = snap;
-                    for (int i = 0; i < full; i++) {
-                        const size_t t = t0 + i;
-                        float fi[NI > 0 ? NI : 1], fo[NO];
-#pragma unroll
-                        for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                        g.template step<PH_SIMD>(fi, fo);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) put(c, t, fo[c]);
-                    }
-                }
-                g.end_simd();
-                for (int i = full; i < size; i++) {
-                    const size_t t = t0 + i;
-                    float fi[NI > 0 ? NI : 1], fo[NO];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                    g.template step<PH_REM>(fi, fo);
-#pragma unroll
-                    for (int c = 0; c < NO; c++) put(c, t, fo[c]);
-                }
-                if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
-                time = end_time;
-                continue;
-            }
-            // Frame by frame, the wave in step: a lane crosses from one note to the next where its window ends.  [si, ei) is the window of the
-            // lane's current note in this block (empty: the note does not play in it); behind it the NEXT note joins the block only if it is
-            // ready in it -- then the current one is over by the next block, so the lane's one set of note registers can move on.
-            int si = w.act ? (int)w.start_index : 0, ei = w.act ? (int)w.end_index : 0, full = 0;
-            bool look = true;
-            float fin_cur = 0.0f, fout_cur = 0.0f;
-            for (int i = 0; i < size; i++) {
-                const size_t t = t0 + i;
-                while (look && i >= ei) {
-                    const double next_start = k + 1 < ne ? sc.ev[k + 1] : inf_;
-                    look = seq_note_ready(next_start, end_time, sd);
-                    if (!look) break;
-                    load_note(++k);
-                    w = seq_block(e_start, e_end, e_fin, e_fout, time, size, sample_rate);
-                    si = w.act ? (int)w.start_index : 0;
-                    ei = w.act ? (int)w.end_index : 0;
-                }
-                float fo[NO];
-#pragma unroll
-                for (int c = 0; c < NO; c++) fo[c] = 0.0f;
-                if (i >= si && i < ei) {
-                    if (i == si) {  // the note's own process() block begins
-                        if (!seq_note_begun(e_start, time, sd)) begin_note(k);
-                        full = (ei - si) & ~7;
-                        g.begin_block(ei - si);
-                        if (full == 0) g.end_simd();
-                        fin_cur = w.fin_cur;
-                        fout_cur = w.fout_cur;
-                    }
-                    const int kk = i - si;  // index in the note's own sub-block buffer
-                    float fi[NI > 0 ? NI : 1];
-#pragma unroll
-                    for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                    if (kk < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
-                    if (kk + 1 == full) g.end_simd();
-                    if (w.fin_on && kk < w.fin_end_i) {
-                        const float e = fade_at(ease, fin_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fin_cur += w.fin_d;
-                    }
-                    if (w.fout_on && kk >= w.fout_i && kk < w.end_index) {
-                        const float e = fade_at(ease, 1.0f - fout_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fout_cur += w.fout_d;
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < NO; c++) put(c, t, fo[c]);
-            }
-            if constexpr (MIXE) mix_flush<NO, 64>(tile, part + t0, T, size, lane);
-            time = end_time;
-        }
-    } else {
-        for (size_t t = 0; t < T; t++) {  // Sequencer::tick :769-836
-            const double end_time = time + sd;
-            while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
-            const bool act = seq_note_ready(e_start, end_time, sd) && !seq_note_over(e_end, time, sd);
-            float fo[NO];
-#pragma unroll
-            for (int c = 0; c < NO; c++) fo[c] = 0.0f;
-            if (act) {
-                if (!seq_note_begun(e_start, time, sd)) begin_note(k);
-                float fi[NI > 0 ? NI : 1];
-#pragma unroll
-                for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * T + t) * V];
-                g.template step<PH_TICK>(fi, fo);
-                if (e_fin > 0.0) {
-                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
-                    if (f < 1.0f) {
-                        const float e = fade_at(ease, f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
-                if (e_fout > 0.0) {
-                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
-                    if (f > 0.0f) {
-                        const float e = fade_at(ease, 1.0f - f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < NO; c++) put(c, t, fo[c]);
-            if constexpr (MIXE) {
-                if ((t & 63) == 63 || t + 1 == T) mix_flush<NO, 64>(tile, part + (t & ~(size_t)63), T, (int)(t & 63) + 1, lane);
-            }
-            time = end_time;
-        }
-    }
-    if (voice) {  // everything: a note's row and the coefficients derived from it belong to the note that goes on in the next launch
-        VStore<true> st{slots + v, stride, 0};
-        g.visit(st);
-    }
-}
-
 template <class G, int MODE>
 __global__ __launch_bounds__(256) void k_render_score_mix(float* __restrict__ slots, size_t stride, size_t V, const float* __restrict__ in,
                                                          float* __restrict__ part, size_t T, const ScoreData sc, double time0,
@@ -1377,8 +1206,8 @@ __global__ __launch_bounds__(256) void k_render_score(float* __restrict__ slots,
 // ---- scores, one lane per NOTE ("score_exec" = FDSP_SCORE_NOTES) ------------------------------------------------------------
 // The score's contract makes the notes of a voice independent: each starts from the voice's slots as they stand, its row written
 // over them, update(sr), reset().  So lane j of the grid is note j of the sorted score, and it walks only the launch blocks its
-// note lives in -- the frame-by-frame part of render_score_body restricted to one note: the same seq_block windows, the same
-// begin_block(n) / PH_SIMD / PH_REM / end_simd sequence, the fades accumulated in f32, hence the same bits.  The lanes of a wave
+// note lives in -- the frame-by-frame part of render_sched_body restricted to one note: the same seq_block windows and the same
+// steps of fd_seq_steps.hpp (seq_window_begin / seq_window_frame, seq_tick_fades, seq_note_begin), hence the same bits.  The lanes of a wave
 // stand in DIFFERENT blocks of the launch at the same instruction; they share nothing (no LDS, no atomics, no cross-lane traffic).
 // The block clock is the serial kernel's: the lane walks the f64 additions from time0 (1 500 of them for 96 000 frames -- a few
 // microseconds next to the note's frames; tick mode pays one per sample).  Frames no note plays are zeroed by the host before the launch.
@@ -1431,9 +1260,7 @@ FD_D void render_score_notes_body(const float* __restrict__ slots, float* __rest
     }
     auto begin_note = [&]() {  // a fresh unit with the note's parameters
         VSetRow row{sc.params, sc.param_slot, sc.nparams, N, j, 0};
-        g.visit(row);
-        g.update(sample_rate);
-        g.reset();
+        seq_note_begin(g, row, sample_rate);
     };
     const float* inv = in + v;
     float* outv = out + v;
@@ -1448,10 +1275,7 @@ FD_D void render_score_notes_body(const float* __restrict__ slots, float* __rest
             if (w.act) {  // the note's own process() block: [si, ei) of this block
                 const int si = (int)w.start_index, ei = (int)w.end_index;
                 if (!seq_note_begun(e_start, time, sd)) begin_note();
-                const int full = (ei - si) & ~7;
-                g.begin_block(ei - si);
-                if (full == 0) g.end_simd();
-                float fin_cur = w.fin_cur, fout_cur = w.fout_cur;
+                SeqWindow win = seq_window_begin(g, w, ei - si);
                 for (int kk = 0; kk < ei - si; kk++) {
                     const size_t t = t0 + (size_t)(si + kk);
                     float fi[NI > 0 ? NI : 1], fo[NO];
@@ -1459,20 +1283,7 @@ FD_D void render_score_notes_body(const float* __restrict__ slots, float* __rest
                     for (int c = 0; c < NO; c++) fo[c] = 0.0f;
 #pragma unroll
                     for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * in_T + t) * V];
-                    if (kk < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
-                    if (kk + 1 == full) g.end_simd();
-                    if (w.fin_on && kk < w.fin_end_i) {
-                        const float e = fade_at(ease, fin_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fin_cur += w.fin_d;
-                    }
-                    if (w.fout_on && kk >= w.fout_i && kk < w.end_index) {
-                        const float e = fade_at(ease, 1.0f - fout_cur);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                        fout_cur += w.fout_d;
-                    }
+                    seq_window_frame(g, w, win, ease, kk, fi, fo);
 #pragma unroll
                     for (int c = 0; c < NO; c++) outv[((size_t)c * T + t) * V] = fo[c];
                 }
@@ -1493,22 +1304,7 @@ FD_D void render_score_notes_body(const float* __restrict__ slots, float* __rest
 #pragma unroll
                 for (int c = 0; c < NI; c++) fi[c] = inv[((size_t)c * in_T + t0) * V];
                 g.template step<PH_TICK>(fi, fo);
-                if (e_fin > 0.0) {
-                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
-                    if (f < 1.0f) {
-                        const float e = fade_at(ease, f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
-                if (e_fout > 0.0) {
-                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
-                    if (f > 0.0f) {
-                        const float e = fade_at(ease, 1.0f - f);
-#pragma unroll
-                        for (int c = 0; c < NO; c++) fo[c] *= e;
-                    }
-                }
+                seq_tick_fades<NO>(e_start, e_end, e_fin, e_fout, ease, time, fo);
 #pragma unroll
                 for (int c = 0; c < NO; c++) outv[((size_t)c * T + t0) * V] = fo[c];
                 rendered = true;

@@ -78,17 +78,17 @@ struct KindOps {
     // small banks take live in the kind's second module; `fast`: the tolerance-mode twin FastOf<G>, a module of its own) -- called when a
     // bank is created and when fdsp_bank_set_option switches its arithmetic, so that no render compiles anything.
     std::function<void(size_t voices, bool fast)> prepare_render;
-    // ... and the Sequencer's mixed output in one launch (render_events_body MIXE): part as above, [groups][outputs][T]; graphs of
+    // ... and the Sequencer's mixed output in one launch (render_sched_body MIXE): part as above, [groups][outputs][T]; graphs of
     // at most two outputs (the block tiles of four waves must fit the CU's LDS)
     std::function<bool(float* slots, size_t stride, size_t V, const float* in, float* part, size_t T, const double* ev,
                        const int* fade, double time0, double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s)>
         render_events_mix;
-    // Sequencer-style rendering (fd_device.hpp render_events_body): ev = device [4][stride] f64, fade = device [V] or null
+    // Sequencer-style rendering (fd_device.hpp render_sched_body with EventNotes): ev = device [4][stride] f64, fade = device [V] or null
     std::function<void(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const double* ev,
                        const int* fade, double time0, double sr, int mode, const void* aux, float* ring,
                        uint32_t ring_cap, hipStream_t s)>
         render_events;
-    // ... and scores (fd_device.hpp render_score_body, fdsp_bank_set_score): sc = the score on the device; the mix variant like
+    // ... and scores (the same body with ScoreNotes, fdsp_bank_set_score): sc = the score on the device; the mix variant like
     // render_events_mix (false / empty: more than two outputs, or a kind built without the mix kernels)
     std::function<void(float* slots, size_t stride, size_t V, const float* in, float* out, size_t T, const ScoreData& sc, double time0,
                        double sr, int mode, const void* aux, float* ring, uint32_t ring_cap, hipStream_t s)>

@@ -534,8 +534,8 @@ int jit_compile_src(const std::string& src, const std::string& type_expr, std::v
             }
         }
     }
-    static const char* const names[6] = {"fd_math.hpp", "fd_seq.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_plan.hpp", "fd_opts.hpp"};
-    return compile_program(src, "graph type `" + type_expr + "`", names, 6, ftz, wide_ilp, code, log);
+    static const char* const names[7] = {"fd_math.hpp", "fd_seq.hpp", "fd_seq_steps.hpp", "fd_nodes.hpp", "fd_device.hpp", "fd_plan.hpp", "fd_opts.hpp"};
+    return compile_program(src, "graph type `" + type_expr + "`", names, 7, ftz, wide_ilp, code, log);
 }
 
 // The process module of a resynthesizer bank's closure (fd_resynth_fn.hpp): the functor's source in namespace fd and rs_process around it.

@@ -28,7 +28,8 @@ enum FieldKind { PARAM = 0, COEF = 1, STATE = 2 };
 // level) says so at the top of its visit(): note_stale(v).  A describing visitor that has a stale() member hears it (VDescribe,
 // VDescribeDev); the loading and storing visitors have none and the call is nothing.  A graph without such a node -- and without
 // rings -- is NOTE-FRESH: after a score's row, update(sr) and reset() no field depends on earlier rendering, so the notes of a
-// voice may be rendered independently of each other (fd_device.hpp render_score_notes_body).  DESIGN.md 6.18 lists the audit.
+// voice may be rendered independently of each other (fd_device.hpp render_score_notes_body; what beginning a note does is
+// fd_seq_steps.hpp seq_note_begin).  DESIGN.md 6.18 lists the audit.
 template <class V> FD_HD auto note_stale(V& v, int) -> decltype(v.stale(), void()) { v.stale(); }
 template <class V> FD_HD void note_stale(V&, long) {}
 

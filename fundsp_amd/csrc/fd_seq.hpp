@@ -1,6 +1,7 @@
-// fd_seq.hpp -- the reference Sequencer's clock arithmetic, host + device, shared by the voice scheduler's two kernels
-// (fd_device.hpp render_events_body: one event per voice; render_score_body: a voice plays one note after another) and by the
-// CPU check tests/host/check_score_blocks.hip.  Follows src/sequencer.rs: ready_to_active :584-605, process :838-951,
+// fd_seq.hpp -- the reference Sequencer's clock arithmetic, host + device, shared by the voice scheduler's kernels (fd_device.hpp
+// render_sched_body, a lane is a voice: one event per voice, or a voice plays one note of a score after another;
+// render_score_notes_body, a lane is a note), by the steps they are built from (fd_seq_steps.hpp) and by the CPU checks
+// tests/host/check_score_blocks.hip and check_score_notes.hip.  Follows src/sequencer.rs: ready_to_active :584-605, process :838-951,
 // fade_in / fade_out :122-216, Fade::at :51-56, smooth5 / sine_ease math.rs:418-420,453-458.  Needs fd_math.hpp only.
 #pragma once
 

@@ -1,7 +1,10 @@
 // tests/host/check_score_blocks.hip -- host-side check (hipcc, host only, its own main): the clock arithmetic the score kernels share with the
 // events kernels (fundsp_amd/csrc/fd_seq.hpp: seq_block, seq_first_live, seq_note_over / _begun / _ready) and the note-advance rule of
-// render_score_body, walked on the CPU over random scores -- block by block and tick by tick, in one launch and in split launches -- next to the
-// oracle's Sequencer (oracle/o_sequencer.c).
+// the lane-per-voice body (fd_device.hpp render_sched_body with ScoreNotes), walked on the CPU over random scores -- block by block and tick by
+// tick, in one launch and in split launches -- next to the oracle's Sequencer (oracle/o_sequencer.c).  What happens to a frame inside a note's
+// window, in a tick and when a note begins is the kernels' own source: the steps of fundsp_amd/csrc/fd_seq_steps.hpp.  The WALK itself --
+// load_note, the advance over notes that are over, the look loop, open() -- is still a restatement of render_sched_body's (the kernel's takes
+// its notes through a policy and works on a wave): a change of the walk has to be made in both places, and this check pins this copy of it.
 // Every note's unit is a constant: note k outputs k + 1, so a frame's sample says which note owns it and carries the bits of its fade factors.
 // The walk also counts how often each note is begun (row written, update, reset): exactly once for a note that plays, right at its first frame --
 // except a note that is already running when a walk starts in its middle (a launch boundary), which must continue instead.
@@ -9,7 +12,8 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
-#include "fd_seq.hpp"
+#define FD_HOST_ONLY 1
+#include "fd_seq_steps.hpp"
 extern "C" {
 #include "fundsp_oracle.h"
 }
@@ -27,11 +31,26 @@ struct Walk {  // one voice's lane state between launches: nothing but what the 
     std::vector<long> first_frame;    // per note: the first frame it played (-1: never)
     std::vector<long> begun_frame;    // per note: the frame index at which it was begun
 };
+// The unit the kernels' steps (fd_seq_steps.hpp) run over here: a constant that says which note owns the frame.  Beginning it -- the
+// reset() at the end of seq_note_begin -- is what the walk counts.
+struct NoteUnit {
+    static constexpr int IN = 0, OUT = 1;
+    Walk* w;
+    int note;    // the lane's current note
+    long frame;  // where it is begun
+    template <class V> void visit(V&) {}
+    void update(double) {}
+    void reset() { w->begun[note]++; w->begun_frame[note] = frame; }
+    void begin_block(int) {}
+    void end_simd() {}
+    template <int PH> void step(const float*, float* out) { out[0] = (float)(note + 1); }
+};
+struct NoRow {};  // these scores have no parameter rows
 
 static unsigned rs = 12345;
 static double rnd() { rs = rs * 1664525u + 1013904223u; return (double)(rs >> 8) * (1.0 / 16777216.0); }
 
-// one launch of `T` frames of voice v from clock time0, the way render_score_body walks it; out[T] gets the voice's samples
+// one launch of `T` frames of voice v from clock time0, the way render_sched_body walks it; out[T] gets the voice's samples
 static double walk_launch(const Score& sc, int v, size_t T, double time0, double sr, bool process, float* out, Walk& w, long frame0) {
     const int N = sc.N(), ne = sc.nb[v + 1];
     const double sd = 1.0 / sr, inf_ = __builtin_huge_val();
@@ -46,7 +65,9 @@ static double walk_launch(const Score& sc, int v, size_t T, double time0, double
         e_fout = on ? sc.ev[3 * N + j] : 0.0;
         ease = on ? sc.fade[j] : 1;
     };
-    auto begin_note = [&](int j, long frame) { w.begun[j]++; w.begun_frame[j] = frame; };
+    NoteUnit u{&w, 0, 0};
+    NoRow row;
+    auto begin_note = [&](int j, long frame) { u.note = j; u.frame = frame; seq_note_begin(u, row, sr); };
     auto played = [&](int j, long frame) { if (w.first_frame[j] < 0) w.first_frame[j] = frame; };
     load_note(k);
     double time = time0;
@@ -56,9 +77,18 @@ static double walk_launch(const Score& sc, int v, size_t T, double time0, double
             const double end_time = time + sd * (double)size;
             while (k < ne && seq_note_over(e_end, time, sd)) load_note(++k);
             SeqBlock b = seq_block(e_start, e_end, e_fin, e_fout, time, size, sr);
-            int si = b.act ? (int)b.start_index : 0, ei = b.act ? (int)b.end_index : 0;
+            int si = 0, ei = 0;
+            SeqWindow win{0, 0.0f, 0.0f};
+            auto open = [&]() {  // the window of the current note; the note is begun where the window is found, what counts is its first frame
+                si = b.act ? (int)b.start_index : 0;
+                ei = b.act ? (int)b.end_index : 0;
+                if (b.act) {
+                    if (!seq_note_begun(e_start, time, sd)) begin_note(k, frame0 + (long)t0 + si);
+                    win = seq_window_begin(u, b, ei - si);
+                }
+            };
+            open();
             bool look = true;
-            float fin_cur = 0.0f, fout_cur = 0.0f;
             for (int i = 0; i < size; i++) {
                 while (look && i >= ei) {
                     const double next_start = k + 1 < ne ? sc.ev[k + 1] : inf_;
@@ -66,21 +96,13 @@ static double walk_launch(const Score& sc, int v, size_t T, double time0, double
                     if (!look) break;
                     load_note(++k);
                     b = seq_block(e_start, e_end, e_fin, e_fout, time, size, sr);
-                    si = b.act ? (int)b.start_index : 0;
-                    ei = b.act ? (int)b.end_index : 0;
+                    open();
                 }
                 float x = 0.0f;
                 if (i >= si && i < ei) {
-                    if (i == si) {
-                        if (!seq_note_begun(e_start, time, sd)) begin_note(k, frame0 + (long)t0 + si);
-                        fin_cur = b.fin_cur;
-                        fout_cur = b.fout_cur;
-                    }
-                    const int kk = i - si;
-                    x = (float)(k + 1);
+                    u.note = k;
                     played(k, frame0 + (long)t0 + i);
-                    if (b.fin_on && kk < b.fin_end_i) { x *= fade_at(ease, fin_cur); fin_cur += b.fin_d; }
-                    if (b.fout_on && kk >= b.fout_i && kk < b.end_index) { x *= fade_at(ease, 1.0f - fout_cur); fout_cur += b.fout_d; }
+                    seq_window_frame(u, b, win, ease, i - si, nullptr, &x);
                 }
                 out[t0 + i] = x;
             }
@@ -95,15 +117,9 @@ static double walk_launch(const Score& sc, int v, size_t T, double time0, double
             if (act) {
                 if (!seq_note_begun(e_start, time, sd)) begin_note(k, frame0 + (long)t);
                 played(k, frame0 + (long)t);
-                x = (float)(k + 1);
-                if (e_fin > 0.0) {
-                    const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
-                    if (f < 1.0f) x *= fade_at(ease, f);
-                }
-                if (e_fout > 0.0) {
-                    const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
-                    if (f > 0.0f) x *= fade_at(ease, 1.0f - f);
-                }
+                u.note = k;
+                u.step<PH_TICK>(nullptr, &x);
+                seq_tick_fades<1>(e_start, e_end, e_fin, e_fout, ease, time, &x);
             }
             out[t] = x;
             time = end_time;

@@ -1,9 +1,10 @@
 // tests/host/check_score_notes.hip -- host-side check (hipcc, host only) of the two ways to execute a score (fd_device.hpp):
-//   render_score_body        a lane is a VOICE: it walks the launch block by block and plays its notes one after the other;
+//   render_sched_body        a lane is a VOICE: it walks the launch block by block and plays its notes one after the other (render_score_body);
 //   render_score_notes_body  a lane is a NOTE: it starts from the voice's slots as they stand at the launch start, walks only the blocks
 //                            its note lives in, and the last note of the voice that rendered a frame (fd_seq.hpp seq_note_owns_state)
 //                            stores the voice's state to a staging image that is committed after the launch.
-// Both walks are restated here on the CPU over a real node type, the FM + SVF voice, with the shared clock arithmetic of fd_seq.hpp, and
+// Both walks are restated here on the CPU over a real node type, the FM + SVF voice, with the shared clock arithmetic of fd_seq.hpp; what
+// happens inside a note's window, in a tick and when a note begins is NOT restated: it is the kernels' own source, fd_seq_steps.hpp.  They
 // run over random scores -- legato pairs, several notes in one block, notes of zero length (one directly behind the last rendered note
 // of a voice), notes carried across a split, off-grid times -- in one launch and in split launches, process and tick.  Every sample and
 // the slot image of every voice after every launch must be bit-equal.  Also pinned: the block clock is the ACCUMULATED one
@@ -13,8 +14,7 @@
 #include <cstring>
 #include <vector>
 #define FD_HOST_ONLY 1
-#include "fd_nodes.hpp"
-#include "fd_seq.hpp"
+#include "fd_seq_steps.hpp"
 using namespace fd;
 
 using G = Pipe<Pipe<Unop<Pipe<Constant<1>, Sine>, UAddScalar>, Sine>, FixedSvf>;  // the FM + SVF voice (fm_svf)
@@ -66,34 +66,23 @@ struct Score {  // sorted by (voice, start)
 };
 static void begin_note(G& g, const Score& sc, int j) {
     HSetRow row{&sc.slot_of, &sc.rows[(size_t)j * sc.slot_of.size()], 0};
-    g.visit(row);
-    g.update(SR);
-    g.reset();
+    seq_note_begin(g, row, SR);
 }
-static void fades_tick(const Score& sc, int j, double time, float* fo) {
+// one tick of note j at clock `time`: the unit's tick and the kernels' tick-mode fades
+static float tick_frame(G& g, const Score& sc, int j, double time) {
     const size_t N = sc.N();
-    const double e_start = sc.ev[j], e_end = sc.ev[N + j], e_fin = sc.ev[2 * N + j], e_fout = sc.ev[3 * N + j];
-    if (e_fin > 0.0) {
-        const float f = (float)((time - e_start) / ((e_start + e_fin) - e_start));
-        if (f < 1.0f) fo[0] *= fade_at(sc.fade[j], f);
-    }
-    if (e_fout > 0.0) {
-        const float f = (float)((time - (e_end - e_fout)) / (e_end - (e_end - e_fout)));
-        if (f > 0.0f) fo[0] *= fade_at(sc.fade[j], 1.0f - f);
-    }
+    float fi[1] = {0.0f}, fo[1] = {0.0f};
+    g.template step<PH_TICK>(fi, fo);
+    seq_tick_fades<1>(sc.ev[j], sc.ev[N + j], sc.ev[2 * N + j], sc.ev[3 * N + j], sc.fade[j], time, fo);
+    return fo[0];
 }
-// the note's own sub-block [si, ei) of a launch block starting at frame t0: begin_block, PH_SIMD below `full`, PH_REM above, fades in f32
-static void play_window(G& g, const Score& sc, int j, const SeqBlock& w, size_t t0, float* out) {
-    const int si = (int)w.start_index, ei = (int)w.end_index, full = (ei - si) & ~7;
-    g.begin_block(ei - si);
-    if (full == 0) g.end_simd();
-    float fin_cur = w.fin_cur, fout_cur = w.fout_cur;
+// the note's own sub-block [si, ei) of a launch block starting at frame t0, by the kernels' window steps
+static void window_frames(G& g, const Score& sc, int j, const SeqBlock& w, size_t t0, float* out) {
+    const int si = (int)w.start_index, ei = (int)w.end_index;
+    SeqWindow win = seq_window_begin(g, w, ei - si);
     for (int kk = 0; kk < ei - si; kk++) {
         float fi[1] = {0.0f}, fo[1] = {0.0f};
-        if (kk < full) g.template step<PH_SIMD>(fi, fo); else g.template step<PH_REM>(fi, fo);
-        if (kk + 1 == full) g.end_simd();
-        if (w.fin_on && kk < w.fin_end_i) { fo[0] *= fade_at(sc.fade[j], fin_cur); fin_cur += w.fin_d; }
-        if (w.fout_on && kk >= w.fout_i && kk < w.end_index) { fo[0] *= fade_at(sc.fade[j], 1.0f - fout_cur); fout_cur += w.fout_d; }
+        seq_window_frame(g, w, win, sc.fade[j], kk, fi, fo);
         out[t0 + (size_t)(si + kk)] = fo[0];
     }
 }
@@ -117,7 +106,7 @@ static void serial_voice(G& g, const Score& sc, int v, double time0, size_t T, b
                     const SeqBlock w = seq_block(sc.ev[k], sc.ev[N + k], sc.ev[2 * N + k], sc.ev[3 * N + k], time, size, SR);
                     if (w.act) {
                         if (!seq_note_begun(sc.ev[k], time, sd)) begin_note(g, sc, k);
-                        play_window(g, sc, k, w, t0, out);
+                        window_frames(g, sc, k, w, t0, out);
                     }
                 }
                 if (!seq_note_ready(start(k + 1), end_time, sd)) break;
@@ -131,10 +120,7 @@ static void serial_voice(G& g, const Score& sc, int v, double time0, size_t T, b
             while (k < ne && seq_note_over(end(k), time, sd)) k++;
             if (seq_note_ready(start(k), end_time, sd) && !seq_note_over(end(k), time, sd)) {
                 if (!seq_note_begun(sc.ev[k], time, sd)) begin_note(g, sc, k);
-                float fi[1] = {0.0f}, fo[1] = {0.0f};
-                g.template step<PH_TICK>(fi, fo);
-                fades_tick(sc, k, time, fo);
-                out[t] = fo[0];
+                out[t] = tick_frame(g, sc, k, time);
             }
             time = end_time;
         }
@@ -168,7 +154,7 @@ static bool note_lane(G& g, const Score& sc, int v, int j, double time0, size_t 
             const SeqBlock w = seq_block(e_start, e_end, sc.ev[2 * N + j], sc.ev[3 * N + j], time, size, SR);
             if (w.act) {
                 if (!seq_note_begun(e_start, time, sd)) begin_note(g, sc, j);
-                play_window(g, sc, j, w, t0, out);
+                window_frames(g, sc, j, w, t0, out);
                 rendered = true;
                 time_last = time;
                 t_last = t0;
@@ -180,10 +166,7 @@ static bool note_lane(G& g, const Score& sc, int v, int j, double time0, size_t 
             const double end_time = time + sd;
             if (seq_note_ready(e_start, end_time, sd)) {
                 if (!seq_note_begun(e_start, time, sd)) begin_note(g, sc, j);
-                float fi[1] = {0.0f}, fo[1] = {0.0f};
-                g.template step<PH_TICK>(fi, fo);
-                fades_tick(sc, j, time, fo);
-                out[t0] = fo[0];
+                out[t0] = tick_frame(g, sc, j, time);
                 rendered = true;
                 time_last = time;
                 t_last = t0;
