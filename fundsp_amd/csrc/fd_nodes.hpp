@@ -2086,13 +2086,18 @@ FD_HD float rs_clamp(float lo, float hi, float x) {  // math.rs:130-132: x.max(l
 
 struct Shape {
     float kind, p0, p1;        // params: Clip(p0) ClipTo(p0,p1) Tanh(p0) Atan(p0) Softsign(p0) Crush(p0) SoftCrush(p0); Adaptive<S>: S's own
-    float smoothing, state;    // Adaptive only: smoothing is a host-computed coefficient (f64 pow, shape.rs:197-200)
+    float smoothing, state;    // Adaptive only.  smoothing: derived from `timescale` at every set_sample_rate (shape.rs:197-200), or -- timescale 0 --
+    float timescale;           // the caller's own coefficient, which a change of rate then leaves alone.  timescale: seconds (Adaptive::new)
     template <class V> FD_HD void visit(V& v) {
         v.f(kind, PARAM, "shape"); v.f(p0, PARAM, "shape_p0"); v.f(p1, PARAM, "shape_p1");
         v.f(smoothing, PARAM, "shape_smoothing");
+        v.f(timescale, PARAM, "shape_timescale");
         v.f(state, STATE, "shape_state");
     }
-    FD_HD void init() { kind = (float)SH_TANH; p0 = 1.0f; p1 = 0.0f; smoothing = 0.0f; state = 0.0f; }  // Adaptive::new: state 0.0
+    FD_HD void init() { kind = (float)SH_TANH; p0 = 1.0f; p1 = 0.0f; smoothing = 0.0f; timescale = 0.0f; state = 0.0f; }  // Adaptive::new: state 0.0
+    FD_HD void update(double sr) {  // Adaptive::set_sample_rate :197-200: pow(0.5, 1.0 / (timescale.to_f64() * sample_rate)).to_f32()
+        if ((int)kind >= SH_ADAPTIVE_TANH && timescale > 0.0f) smoothing = (float)pow_f64(0.5, 1.0 / ((double)timescale * sr));
+    }
     FD_HD void reset() { if ((int)kind >= SH_ADAPTIVE_TANH) state = 1.0e-3f; }                            // shape.rs:193-196
     // Shape::shape (scalar path)
     FD_HD float shape(float input) {
@@ -2136,7 +2141,7 @@ struct Shaper {
     template <class V> FD_HD void visit(V& v) { sh.visit(v); }
     FD_HD void bind(Ctx&) {}
     FD_HD void init() { sh.init(); }
-    FD_HD void update(double) {}
+    FD_HD void update(double sr) { sh.update(sr); }
     FD_HD void reset() { sh.reset(); }
     FD_HD uint64_t ping(bool, uint64_t h) { return atto(h, ID); }
     FD_HD void begin_block(int) {}
@@ -2285,7 +2290,14 @@ struct NlBiquad {
         mode = (float)BQ_LOWPASS; center = 440.0f; q = 1.0f; gain = 1.0f; s1 = 0.0f; s2 = 0.0f;
         sh1.init(); sh2.init();
     }
-    FD_HD void update(double sample_rate) { sr = (float)sample_rate; coefs(); }
+    // biquad.rs:535-538, 678-681, 745-748, 898-901: none of the four passes set_sample_rate on to its shape, so an Adaptive shape keeps the smoothing
+    // Adaptive::new gave it at DEFAULT_SR (shape.rs:174-182) whatever the rate of the filter
+    FD_HD void update(double sample_rate) {
+        sr = (float)sample_rate;
+        coefs();
+        sh1.update(44100.0);
+        if (DIRTY) sh2.update(44100.0);
+    }
     FD_HD void reset() { s1 = 0.0f; s2 = 0.0f; sh1.reset(); if (DIRTY) sh2.reset(); }
     FD_HD uint64_t ping(bool, uint64_t h) { return atto(h, ID); }
     FD_HD void begin_block(int) {}

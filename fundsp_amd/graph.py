@@ -280,8 +280,10 @@ def rossler(): return _leaf("Chaos<false>", 1, 1)
 def lorenz(): return _leaf("Chaos<true>", 1, 1)
 def adsr_live(a, d, s, r): return _leaf("AdsrLive", 1, 1, attack=a, decay=d, sustain=s, release=r)
 def pan(p): return _leaf("Panner", 1, 2, pan=p)
-def shape(kind, p0=1.0, p1=0.0, smoothing=0.0):
-    return _leaf("Shaper", 1, 1, shape=float(SHAPES[kind]), shape_p0=p0, shape_p1=p1, shape_smoothing=smoothing)
+def shape(kind, p0=1.0, p1=0.0, smoothing=0.0, timescale=0.0):
+    """Adaptive shapes: `timescale` (seconds, Adaptive::new) lets the node derive its smoothing at every set_sample_rate as the reference does;
+    `smoothing` alone is a coefficient of the caller's that a change of rate leaves as it is."""
+    return _leaf("Shaper", 1, 1, shape=float(SHAPES[kind]), shape_p0=p0, shape_p1=p1, shape_smoothing=smoothing, shape_timescale=timescale)
 
 
 

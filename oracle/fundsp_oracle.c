@@ -704,11 +704,12 @@ static void leaf_set_sample_rate(onode *n, double sr) {
     case O_SHAPER:
         if (n->s.sh[0].kind >= O_SH_ADAPTIVE_TANH) n->s.sh[0].smoothing = (float)o_adaptive_smoothing(n->s.sh[0].ts, sr);
         break;
-    case O_NLBIQUAD: /* biquad.rs:535-538 */
+    case O_NLBIQUAD: /* biquad.rs:535-538, 678-681, 745-748, 898-901: the rate and the coefficients, NOT the shape -- an Adaptive shape keeps the
+                        smoothing Adaptive::new gave it at DEFAULT_SR (shape.rs:174-182) */
         n->s.sr = (float)sr;
         n->s.bc = bq_by_mode(n->s.nl_mode, n->s.sr, n->s.center, n->s.q, n->s.gain);
         for (int i = 0; i < 2; i++)
-            if (n->s.sh[i].kind >= O_SH_ADAPTIVE_TANH) n->s.sh[i].smoothing = (float)o_adaptive_smoothing(n->s.sh[i].ts, sr);
+            if (n->s.sh[i].kind >= O_SH_ADAPTIVE_TANH) n->s.sh[i].smoothing = (float)o_adaptive_smoothing(n->s.sh[i].ts, DEFAULT_SR);
         break;
     case O_DELAY: /* delay.rs:105-113 */
         if (n->s.dsr != sr) {

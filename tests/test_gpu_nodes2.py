@@ -127,8 +127,9 @@ def test_fixed_nonlinear_biquads(gpu, dirty):
         b.set_param(f"{which}:shape", np.array([O.SHAPES[SHAPE_CASES[s][0]] for s in shape_i], dtype=np.float32))
         b.set_param(f"{which}:shape_p0", np.array([SHAPE_CASES[s][1] for s in shape_i], dtype=np.float32))
         b.set_param(f"{which}:shape_p1", np.array([SHAPE_CASES[s][2] for s in shape_i], dtype=np.float32))
+        # (the four biquads never pass set_sample_rate on to their shape, biquad.rs:535-538: Adaptive keeps the smoothing of Adaptive::new's DEFAULT_SR)
         b.set_param(f"{which}:shape_smoothing", np.array(
-            [np.float32(O.lib().o_adaptive_smoothing(SHAPE_CASES[s][2], SR)) if SHAPE_CASES[s][0] == "adaptive_tanh" else 0.0
+            [np.float32(O.lib().o_adaptive_smoothing(SHAPE_CASES[s][2], O.DEFAULT_SR)) if SHAPE_CASES[s][0] == "adaptive_tanh" else 0.0
              for s in shape_i], dtype=np.float32))
     b.set_sample_rate(SR)
     x = noise_input(V, 1, T, seed=41)
